@@ -21,8 +21,16 @@ and ms, ranks in the RCCL communicator, NCCL_ALGO.  ``--parallelism viewshard`` 
 Tanks&Temples 1920x1056 N=7) instead of the single-stage M1; ``--workload T5`` times BASELINE config 5, one
 BlendedMVS-shaped training step (768x576, N=5, refine=True, data-parallel gradient all-reduce).
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (fused warp-aggregate kernel,
-HBM bound) and `cpu_baseline` (the CPU oracle timed on the host cores on a bounded sample) objects.
+Prints ONE JSON line on rank 0: `metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` (one timed step), the
+workload and the build.  A plain run does only that: set up, warm up, time --steps steps, write the outputs (--dump-outputs) and
+print the line.  ``--full`` adds everything else, measured after the timed region: per-kernel times and `roofline` (fused
+warp-aggregate kernel, HBM bound; HBM traffic re-measured with rocprofv3 at M1), `roofline_costreg`, `cpu_baseline` (the CPU
+oracle timed on the host cores), `other_workloads` (M1b / M2 / M3 / M4 / T5 and the K3 stage rooflines) and, with N > 1 ranks or
+--force-dist, the `viewshard` / `strong_scaling` objects.
+
+``--dump-outputs DIR`` writes what the timed path returned in its last step as ``DIR/<name>.npy`` (float32, or float64 where
+the path returns float64; at most 64 MB in all: a larger output is reduced to a fixed, seeded sample of its elements).  The
+inputs and weights are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import gc
@@ -315,7 +323,13 @@ def cpu_baseline(model_cpu, name, budget_frac, seed=0, gpu_depth=None):
     if avail and need > 0.8 * avail:
         budget_frac = min(budget_frac, 0.5)
     hs, ws = max(8, int(h * budget_frac) // 8 * 8), max(8, int(w * budget_frac) // 8 * 8)
-    cores = min(os.cpu_count() or 1, 64)
+    try:
+        cores = len(os.sched_getaffinity(0))
+    except (AttributeError, OSError):
+        cores = os.cpu_count() or 1
+    if os.environ.get("OMP_NUM_THREADS", "").isdigit() and int(os.environ["OMP_NUM_THREADS"]) > 0:
+        cores = min(cores, int(os.environ["OMP_NUM_THREADS"]))
+    cores = min(cores, 64)
     torch.set_num_threads(cores)
     feats = synth.make_pair_features(n_views - 1, C, hs, ws, seed=seed + 1)
     cams = synth.stage_cameras(n_views, hs, ws, seed=seed)
@@ -563,6 +577,46 @@ def strong_scaling_summary(vs):
     return s
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(outputs, out_dir, budget=DUMP_BUDGET_BYTES, seed=0):
+    """``outputs``: a (nested) dict of tensors -> ``out_dir/<dotted key>.npy``; float64 stays float64, everything else is
+    written as float32.  When the arrays together exceed ``budget`` bytes, every array larger than an equal share of it is
+    replaced by a fixed, seeded sample of its flattened elements (same positions on every run; ascending order)."""
+    import numpy as np
+    flat = {}
+
+    def walk(prefix, obj):
+        if isinstance(obj, torch.Tensor):
+            flat[prefix] = obj
+        elif isinstance(obj, dict):
+            for k in sorted(obj, key=str):
+                walk(f"{prefix}.{k}" if prefix else str(k), obj[k])
+        elif isinstance(obj, (list, tuple)):
+            for i, v in enumerate(obj):
+                walk(f"{prefix}.{i}" if prefix else str(i), v)
+    walk("", outputs)
+    arrays = {}
+    for k, t in flat.items():
+        t = t.detach()
+        arrays[k] = t.to("cpu", torch.float64 if t.dtype == torch.float64 else torch.float32).numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > budget:
+        small = sum(a.nbytes for a in arrays.values() if a.nbytes <= budget // len(arrays))
+        big = [k for k, a in arrays.items() if a.nbytes > budget // len(arrays)]
+        share = (budget - small) // len(big)
+        for k in big:
+            a = arrays[k].reshape(-1)
+            n = max(1, share // a.itemsize)
+            idx = np.sort(np.random.default_rng(seed).choice(a.size, size=n, replace=False))
+            arrays[k] = a[idx]
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k.replace(os.sep, "_") + ".npy"), a)
+    return {k: list(a.shape) for k, a in arrays.items()}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -575,14 +629,19 @@ def main():
                          "reduce_scatter = rows of the sum per rank + slab-parallel CostRegNet (the form that scales)")
     ap.add_argument("--train-act-storage", default="f32", choices=["f32", "bf16"],
                     help="--workload T5: storage of the FeatureNet activations between the passes (bf16 = bf16 storage / f32 accumulate)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the M1b / M2 / M3 / M4 side measurements")
-    ap.add_argument("--no-pmc", action="store_true", help="do not re-measure roofline.traffic with rocprofv3 in this run")
-    ap.add_argument("--no-viewshard", action="store_true", help="N > 1: skip the north-star view-shard measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: per-kernel times, rooflines, the CPU baseline, the other workloads and (N > 1 or "
+                         "--force-dist) the view-shard measurements; a plain run only times the steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last step as DIR/<name>.npy (float32/float64, <= 64 MB)")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip the M1b / M2 / M3 / M4 side measurements")
+    ap.add_argument("--no-pmc", action="store_true", help="--full: do not re-measure roofline.traffic with rocprofv3 in this run")
+    ap.add_argument("--no-viewshard", action="store_true", help="--full, N > 1: skip the north-star view-shard measurement")
     ap.add_argument("--streams", type=int, default=1,
                     help="depth maps in flight per GPU on separate HIP streams (a step = that many depth maps; "
                          "per-kernel event timing and the roofline object need 1)")
     ap.add_argument("--cpu-sample", type=float, default=1.0,
-                    help="linear window fraction for the CPU baseline (1 = the full workload once; 0 = skip)")
+                    help="--full: linear window fraction for the CPU baseline (1 = the full workload once; 0 = skip)")
     ap.add_argument("--viewshard-timeout", type=float, default=420.0,
                     help="N > 1: seconds the view-shard side measurement may take before a watchdog prints the headline line without it "
                          "and ends the process (below the process group's 10-minute timeout, which aborts without output)")
@@ -674,8 +733,8 @@ def main():
         metric, unit = f"training samples/sec ({W}x{H} N={n_views} step: forward + loss + backward + all-reduce + SGD)", "samples/s"
         b_alg = None
         def step():
-            l, _ = T.train_step(model, opt, sample, temperature=0.1, reducer=reducer, activation_storage=args.train_act_storage)
-            return {"depth": torch.tensor([l])}
+            l, dl = T.train_step(model, opt, sample, temperature=0.1, reducer=reducer, activation_storage=args.train_act_storage)
+            return {"depth": torch.tensor([l]), "losses": (l, dl)}
 
     if args.streams > 1:   # independent pipelines on separate streams: memory-bound and issue-bound kernels overlap
         one_map = step
@@ -700,7 +759,7 @@ def main():
         for _ in range(args.warmup):      # warm-up so that no idle gap sits between the warm-up steps and the timed ones
             out = step()
         ops.PROFILE.clear()
-        ops.PROFILE_ON = args.streams == 1
+        ops.PROFILE_ON = args.streams == 1 and args.full     # per-kernel HIP events: --full only
         barrier()
         t0 = time.perf_counter()
         for _ in range(args.steps):
@@ -717,6 +776,14 @@ def main():
     maps_per_step = (1 if viewshard_timed else world) * args.streams
     value = maps_per_step * args.steps / dt
     depth_mean = float(out["depth"].float().mean().item())
+    if args.dump_outputs and rank == 0:
+        if kind == "train":   # the step's two losses (train_step returns them as floats) and the weights it leaves behind
+            dumped = {"loss": torch.tensor([out["losses"][0]], dtype=torch.float64),
+                      "depth_loss": torch.tensor([out["losses"][1]], dtype=torch.float64),
+                      "param": {k: v for k, v in model.named_parameters()}}
+        else:
+            dumped = out
+        dump_outputs(dumped, args.dump_outputs)
 
     # per-kernel durations from the HIP events recorded inside the timed region (same stream as the launches); per STEP
     # (a cascade step launches every kernel family three times)
@@ -726,7 +793,7 @@ def main():
         t_k3 = kern["warp_aggregate"] * 1e-3
         achieved = b_alg / t_k3
         traffic, traffic_detail, traffic_note = None, None, "static"
-        if world == 1 and args.workload == "M1" and not args.no_extras and not args.no_pmc:
+        if world == 1 and args.workload == "M1" and args.full and not args.no_extras and not args.no_pmc:
             torch.cuda.synchronize()
             traffic_detail, traffic_note = measure_k3_traffic()
             if traffic_detail is not None:
@@ -770,7 +837,7 @@ def main():
     extra["kernel_ms"] = {k: round(v, 4) for k, v in sorted(kern.items())}
 
     others = None
-    if world == 1 and args.streams == 1 and args.workload == "M1" and not args.no_extras:
+    if args.full and world == 1 and args.streams == 1 and args.workload == "M1" and not args.no_extras:
         others = other_workloads(model, dev)
     def make_line(vs, cpu):
         line = {
@@ -795,9 +862,11 @@ def main():
                                                "exact-fp32 fmaf-chain kernels'; CDS_CONV_EXACT=1 selects those)")
                                               if __import__("cds_mvsnet_amd.model", fromlist=["x"]).USE_SPLIT_BF16
                                               else "exact fp32 (fmaf chains on the fp32 matrix / vector pipes)")},
-            "roofline": roof, "cpu_baseline": cpu, "build": build_id(),
+            "build": build_id(),
         }
-        line.update(extra)
+        if args.full:
+            line["roofline"], line["cpu_baseline"] = roof, cpu
+            line.update(extra)
         if others is not None:
             line["other_workloads"] = others
         if vs is not None:
@@ -806,7 +875,7 @@ def main():
         return line
 
     vs = None
-    if (world > 1 or args.force_dist) and kind != "train" and not args.no_viewshard:
+    if args.full and (world > 1 or args.force_dist) and kind != "train" and not args.no_viewshard:
         # The view-shard side measurement is the first code of a node run that exchanges data over RCCL between kernels.  It must not
         # take the timed headline down with it: an exception is recorded in the line; a HANG (ranks disagreeing about a collective) is
         # cut by a watchdog on every rank that prints the headline line with the failure noted and ends the process before the
@@ -840,7 +909,7 @@ def main():
             finished.set()
     if rank == 0:
         cpu = None
-        if world == 1 and args.cpu_sample > 0 and kind == "stage":
+        if args.full and world == 1 and args.cpu_sample > 0 and kind == "stage":
             cpu = cpu_baseline(model_cpu, args.workload, args.cpu_sample, seed=seed, gpu_depth=out["depth"][0] if args.streams == 1 else None)
         print(json.dumps(make_line(vs, cpu)))
     if dist is not None:

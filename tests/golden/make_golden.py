@@ -8,7 +8,9 @@ The reference is imported read-only; weights come from this repo's own seeded in
 (``cds_mvsnet_amd.seeded_init_``) and are loaded into the reference through the shared state-dict
 keys, so no reference weights or source text are vendored.  Only data (inputs + expected outputs) is
 written, as ``tests/golden/*.npz``.  Fixtures: G1 warp/aggregate, G2 CostRegNet,
-G3 regression, G4 hypotheses, G5 DynamicConv/FeatureNet/epipoles, G6 full forward.
+G3 regression, G4 hypotheses, G5 DynamicConv/FeatureNet/epipoles, G6 full forward.  The one exception is G12: the
+trained weights of the reference's three checkpoints outside CostRegNet (weights only, no pickled objects) with the
+reference's forward on them, so that trained-weight parity is checked from the repository alone.
 """
 import os
 import sys
@@ -493,9 +495,47 @@ def g11_loss():
     save("g11_loss", **out)
 
 
+G12_CHECKPOINTS = {"dtu_only": "dtu_only/checkpoint-epoch24.pth", "both_dtu_blended": "both_dtu_blended/cds_mvsnet.ckpt",
+                   "fine_tuning_on_blended": "fine_tuning_on_blended/cds_mvsnet.ckpt"}
+
+
+@torch.no_grad()
+def g12_trained_checkpoints():
+    """The reference's three TRAINED checkpoints.  Their CostRegNets (0.89 M of the 0.98 M parameters) are replaced by the seeded ones
+    of ``seeded_init_(CDSMVSNet(refine=True), SEED)`` so that a fixture stays small; every other entry (FeatureNet with its DynamicConv
+    blends, visibility network, refinement network: ``w.<key>``, 'module.' prefix stripped; ``module_prefix`` records whether the file
+    carried it) is the trained one.  Outputs: the reference forward with those weights on a synthetic 3-view 192x128 scene at
+    T = 0.01, refine=True (``out.<stageK>.<key>``, ``out.refined_depth``)."""
+    from cds_mvsnet_amd import CDSMVSNet
+    from cds_mvsnet_amd.infer import _placeholder_pickle
+    N, H, W = 3, 128, 192
+    imgs = synth.make_images(N, H, W, seed=4)
+    cams = synth.make_cameras(N, H, W, refine=True, seed=4)
+    dv = synth.make_depth_values()
+    seeded = seeded_init_(CDSMVSNet(refine=True, ndepths=(48, 32, 8), depth_interals_ratio=(4.0, 1.5, 0.75)), SEED).state_dict()
+    pretrained = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(sys.modules["models"].__file__))), "pretrained")
+    for tag, path in G12_CHECKPOINTS.items():
+        ck = torch.load(os.path.join(pretrained, path), map_location="cpu", weights_only=False,
+                        pickle_module=_placeholder_pickle)
+        raw = ck["state_dict"]
+        trained = {k.replace("module.", ""): v for k, v in raw.items()}
+        sd = {k: (seeded[k] if k.startswith("cost_regularization.") else v) for k, v in trained.items()}
+        m = RefNet(refine=True, ndepths=(48, 32, 8), depth_interals_ratio=(4.0, 1.5, 0.75))
+        m.load_state_dict(sd, strict=True)
+        out = m.eval()(imgs, cams, dv, temperature=0.01)
+        arrays = {"w." + k: v for k, v in sd.items() if not k.startswith("cost_regularization.")}
+        arrays["module_prefix"] = np.array(all(k.startswith("module.") for k in raw))
+        for s in range(3):
+            st = out[f"stage{s + 1}"]
+            for k in ("depth", "photometric_confidence", "norm_curv"):
+                arrays[f"out.stage{s + 1}.{k}"] = st[k]
+        arrays["out.refined_depth"] = out["refined_depth"]
+        save(f"g12_trained_{tag}", **arrays)
+
+
 if __name__ == "__main__":
     only = sys.argv[1:]
     for fn in (g1_warp_aggregate, g2_costreg, g3_regress, g4_hypotheses, g5_features, g6_forward, g7_training_step,
-               g8_fusion, g9_feature_noise, g10_formats, g11_loss):
+               g8_fusion, g9_feature_noise, g10_formats, g11_loss, g12_trained_checkpoints):
         if not only or fn.__name__.split("_")[0] in only:
             fn()

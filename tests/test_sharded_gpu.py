@@ -255,7 +255,7 @@ def test_bench_two_ranks_dry_run_on_one_device(tmp_path):
     env = dict(os.environ, CDS_BENCH_DEVICE="0", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--dist-backend", "gloo", "--no-extras", "--no-pmc", "--cpu-sample", "0.1"]
+           "--dist-backend", "gloo", "--full", "--no-extras", "--no-pmc", "--cpu-sample", "0.1"]
     res = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=1500)
     assert res.returncode == 0, res.stderr[-2000:]
     line = json.loads([l for l in res.stdout.splitlines() if l.startswith("{")][-1])
@@ -286,7 +286,7 @@ def test_bench_one_rank_over_rccl(tmp_path):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()), RANK="0", WORLD_SIZE="1", LOCAL_RANK="0",
                HSA_ENABLE_IPC_MODE_LEGACY="0")
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--force-dist", "--no-extras",
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--force-dist", "--full", "--no-extras",
            "--no-pmc", "--cpu-sample", "0"]
     res = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=1500)
     assert res.returncode == 0, res.stderr[-2000:]
@@ -309,7 +309,7 @@ def test_bench_watchdog_cuts_a_hung_side_measurement(tmp_path):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()), RANK="0", WORLD_SIZE="1", LOCAL_RANK="0",
                HSA_ENABLE_IPC_MODE_LEGACY="0", CDS_BENCH_TEST_HANG="1")
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--force-dist", "--no-extras",
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--force-dist", "--full", "--no-extras",
            "--no-pmc", "--cpu-sample", "0", "--viewshard-timeout", "3"]
     res = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=600)     # (the sleep is an hour)
     assert res.returncode == 0, res.stderr[-2000:]

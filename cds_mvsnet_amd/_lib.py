@@ -106,6 +106,12 @@ SIGNATURES = {
     "cds_bn3d_bwd_reduce_f32": [P, P, P, P, P, I, I, L, I, P],
     "cds_bn3d_bwd_norm_f32": [P, P, P, P, P, P, P, DB, P, P, P, I, I, L, I, P],
     "cds_conv3d_wgrad_f32": [P, P, P, I, I, I, I, I, I, I, I, I, I, P],
+    "cds_bn3d_norm_bound_f32": [P, P, P, P, DB, DB, F, P, P, P, P, P, P, P, P, I, I, L, I, P, P],
+    "cds_bn3d_bwd_norm_bound_f32": [P, P, P, P, P, P, P, DB, P, P, P, I, I, L, I, P, P],
+    "cds_absmax_bound_f32": [P, L, P, P],
+    "cds_sf16_pack_conv3d_f32": [P, P, P, P, I, I, I, P],
+    "cds_conv3d_k3_sf16_f32": [P, P, P, P, P, I, I, I, I, I, I, I, P],
+    "cds_conv3d_wgrad_sf16_f32": [P, P, P, P, P, I, I, I, I, I, I, I, I, I, I, P],
     "cds_conv2d_wgrad_f32": [P, P, P, I, I, I, I, I, I, I, I, I, I, P],
     "cds_conv2d_dgrad_s2_f32": [P, P, P, I, I, I, I, I, I, I, P],
     "cds_instnorm_bwd_f32": [P, P, P, P, P, I, I, I, I, I, I, P],

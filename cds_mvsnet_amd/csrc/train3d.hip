@@ -13,6 +13,7 @@
 #include <stdlib.h>
 
 #include "cds_common.hpp"
+#include "sbf_common.hpp"
 
 namespace {
 
@@ -20,6 +21,22 @@ __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
   return v;
+}
+
+// max |v| over the workgroup into `slot` with at most one atomic per workgroup (a relaxed read first: most workgroups raise nothing).
+// One atomic per WAVE on the one address was ~14 us per BatchNorm launch of the training step.  All threads of the workgroup call it.
+__device__ __forceinline__ void bn_publish_bound(float amax, float* slot) {
+  __shared__ float red[4];
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o));
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = amax;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    amax = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    unsigned int* u = reinterpret_cast<unsigned int*>(slot);
+    const unsigned int mine = __float_as_uint(amax);                 // non-negative floats order like their bit patterns
+    if (mine > __hip_atomic_load(u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(u, mine);
+  }
 }
 
 // grid (chunks, C, B); sums [C][2] fp64 (zeroed by the caller)
@@ -76,7 +93,8 @@ __global__ __launch_bounds__(256) void bn3d_norm_kernel(const float* __restrict_
                                                         float* __restrict__ running_var, const float* __restrict__ skip,
                                                         float* __restrict__ out, float* __restrict__ scale_out,
                                                         float* __restrict__ shift_out, double* __restrict__ mean_out,
-                                                        double* __restrict__ invstd_out, int C, size_t V, int relu) {
+                                                        double* __restrict__ invstd_out, int C, size_t V, int relu,
+                                                        float* __restrict__ out_bound = nullptr) {
   const int c = blockIdx.y, b = blockIdx.z;
   const double mean = sums[2 * c] / n;
   double var = sums[2 * c + 1] / n - mean * mean;                  // biased, like F.batch_norm in training
@@ -95,6 +113,7 @@ __global__ __launch_bounds__(256) void bn3d_norm_kernel(const float* __restrict_
     }
   }
   const size_t base = ((size_t)b * C + c) * V;
+  float amax = 0.f;                                                // max |out| of what this thread stores (out_bound: split-f16 mode)
   if (bn_vec4(V, y + base, out + base, skip ? skip + base : nullptr)) {
     const float4* __restrict__ y4 = reinterpret_cast<const float4*>(y + base);
     const float4* __restrict__ k4 = skip ? reinterpret_cast<const float4*>(skip + base) : nullptr;
@@ -108,7 +127,9 @@ __global__ __launch_bounds__(256) void bn3d_norm_kernel(const float* __restrict_
         v = make_float4(k.x + v.x, k.y + v.y, k.z + v.z, k.w + v.w);
       }
       o4[i] = v;
+      if (out_bound) amax = fmaxf(amax, fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))));
     }
+    if (out_bound) bn_publish_bound(amax, out_bound);
     return;
   }
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < V; i += (size_t)gridDim.x * 256) {
@@ -116,7 +137,9 @@ __global__ __launch_bounds__(256) void bn3d_norm_kernel(const float* __restrict_
     if (relu) v = fmaxf(v, 0.f);
     if (skip) v = skip[base + i] + v;
     out[base + i] = v;
+    amax = fmaxf(amax, fabsf(v));
   }
+  if (out_bound) bn_publish_bound(amax, out_bound);
 }
 
 // sums[c] = (sum g, sum g * y), g = dout * [y * scale + shift > 0]
@@ -163,7 +186,7 @@ __global__ __launch_bounds__(256) void bn3d_bwd_norm_kernel(const float* __restr
                                                             const double* __restrict__ sums, const double* __restrict__ mean,
                                                             const double* __restrict__ invstd, double n, float* __restrict__ dy,
                                                             float* __restrict__ dgamma, float* __restrict__ dbeta, int C, size_t V,
-                                                            int relu) {
+                                                            int relu, float* __restrict__ dy_bound = nullptr) {
   const int c = blockIdx.y, b = blockIdx.z;
   const size_t base = ((size_t)b * C + c) * V;
   const float sc = scale[c], sh = shift[c];
@@ -175,6 +198,7 @@ __global__ __launch_bounds__(256) void bn3d_bwd_norm_kernel(const float* __restr
     dgamma[c] = (float)dg;
     dbeta[c] = (float)db;
   }
+  float amax = 0.f;                                                // max |dy| of what this thread stores (dy_bound: split-f16 mode)
   if (bn_vec4(V, y + base, dout + base, dy + base)) {
     const float4* __restrict__ y4 = reinterpret_cast<const float4*>(y + base);
     const float4* __restrict__ d4 = reinterpret_cast<const float4*>(dout + base);
@@ -183,16 +207,22 @@ __global__ __launch_bounds__(256) void bn3d_bwd_norm_kernel(const float* __restr
       const float4 yv = y4[i], dv = d4[i];
       const float g0 = (!relu || fmaf(yv.x, sc, sh) > 0.f) ? dv.x : 0.f, g1 = (!relu || fmaf(yv.y, sc, sh) > 0.f) ? dv.y : 0.f;
       const float g2 = (!relu || fmaf(yv.z, sc, sh) > 0.f) ? dv.z : 0.f, g3 = (!relu || fmaf(yv.w, sc, sh) > 0.f) ? dv.w : 0.f;
-      o4[i] = make_float4(fmaf(g0, sc, fmaf(yv.x, a1, a0)), fmaf(g1, sc, fmaf(yv.y, a1, a0)), fmaf(g2, sc, fmaf(yv.z, a1, a0)),
-                          fmaf(g3, sc, fmaf(yv.w, a1, a0)));
+      const float4 v = make_float4(fmaf(g0, sc, fmaf(yv.x, a1, a0)), fmaf(g1, sc, fmaf(yv.y, a1, a0)), fmaf(g2, sc, fmaf(yv.z, a1, a0)),
+                                   fmaf(g3, sc, fmaf(yv.w, a1, a0)));
+      o4[i] = v;
+      if (dy_bound) amax = fmaxf(amax, fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))));
     }
+    if (dy_bound) bn_publish_bound(amax, dy_bound);
     return;
   }
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < V; i += (size_t)gridDim.x * 256) {
     const float yv = y[base + i];
     const float g = (!relu || fmaf(yv, sc, sh) > 0.f) ? dout[base + i] : 0.f;
-    dy[base + i] = fmaf(g, sc, fmaf(yv, a1, a0));
+    const float v = fmaf(g, sc, fmaf(yv, a1, a0));
+    dy[base + i] = v;
+    amax = fmaxf(amax, fabsf(v));
   }
+  if (dy_bound) bn_publish_bound(amax, dy_bound);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -452,6 +482,31 @@ extern "C" int cds_bn3d_bwd_norm_f32(const float* dout, const float* y, const fl
     return CDS_EINVAL;
   hipLaunchKernelGGL(bn3d_bwd_norm_kernel, ew_grid((size_t)V, C, B), dim3(256), 0, (hipStream_t)stream, dout, y, scale, shift, sums,
                      mean, invstd, n, dy, dgamma, dbeta, C, (size_t)V, relu);
+  return cds_launch_status();
+}
+
+// The same two passes publishing an upper bound of what they store (running max |out| / max |dy| into a zeroed device slot): the operand
+// bounds of the split-f16 convolutions (train3d_sf16.hip).
+extern "C" int cds_bn3d_norm_bound_f32(const float* y, const double* sums, const float* gamma, const float* beta, double n, double eps,
+                                       float momentum, float* running_mean, float* running_var, const float* skip, float* out, float* scale,
+                                       float* shift, double* mean, double* invstd, int B, int C, long long V, int relu, float* out_bound,
+                                       void* stream) {
+  if (!y || !sums || !gamma || !beta || !out || !scale || !shift || !mean || !invstd || !out_bound || B < 1 || C < 1 || V < 1 ||
+      n < 1.0 || (running_mean != nullptr) != (running_var != nullptr))
+    return CDS_EINVAL;
+  hipLaunchKernelGGL(bn3d_norm_kernel, ew_grid((size_t)V, C, B), dim3(256), 0, (hipStream_t)stream, y, sums, gamma, beta, n, eps,
+                     momentum, running_mean, running_var, skip, out, scale, shift, mean, invstd, C, (size_t)V, relu, out_bound);
+  return cds_launch_status();
+}
+
+extern "C" int cds_bn3d_bwd_norm_bound_f32(const float* dout, const float* y, const float* scale, const float* shift, const double* sums,
+                                           const double* mean, const double* invstd, double n, float* dy, float* dgamma, float* dbeta,
+                                           int B, int C, long long V, int relu, float* dy_bound, void* stream) {
+  if (!dout || !y || !scale || !shift || !sums || !mean || !invstd || !dy || !dgamma || !dbeta || !dy_bound || B < 1 || C < 1 ||
+      V < 1 || n < 1.0)
+    return CDS_EINVAL;
+  hipLaunchKernelGGL(bn3d_bwd_norm_kernel, ew_grid((size_t)V, C, B), dim3(256), 0, (hipStream_t)stream, dout, y, scale, shift, sums,
+                     mean, invstd, n, dy, dgamma, dbeta, C, (size_t)V, relu, dy_bound);
   return cds_launch_status();
 }
 

@@ -142,25 +142,29 @@ class GradAllReducer:
 
 def train_step(model: torch.nn.Module, optimizer: torch.optim.Optimizer, sample: Dict[str, object], temperature: float,
                dlossw: Sequence[float] = (0.5, 1.0, 2.0), reducer: Optional[GradAllReducer] = None,
-               activation_storage: Optional[str] = None) -> Tuple[float, float]:
+               activation_storage: Optional[str] = None, conv_arithmetic: Optional[str] = None) -> Tuple[float, float]:
     """One optimisation step on ``sample`` = {imgs, proj_matrices, depth_values, depth: {stageK}, mask: {stageK}}
     (already on the model's device).  Returns (loss, depth_loss) as Python floats.  activation_storage: None = the process default
-    (fp32 unless CDS_TRAIN_ACT_STORAGE=bf16), "f32" or "bf16" (module docstring)."""
-    loss, depth_loss = _step_tensors(model, optimizer, sample, temperature, dlossw, reducer, activation_storage)
+    (fp32 unless CDS_TRAIN_ACT_STORAGE=bf16), "f32" or "bf16" (module docstring).  conv_arithmetic: None = the process default (fp32
+    unless CDS_TRAIN_CONV=split_f16), "f32" or "split_f16": the CostRegNet convolutions (train_ops.conv_arithmetic)."""
+    loss, depth_loss = _step_tensors(model, optimizer, sample, temperature, dlossw, reducer, activation_storage,
+                                     conv_arithmetic=conv_arithmetic)
     return float(loss), float(depth_loss)
 
 
-def _step_tensors(model, optimizer, sample, temperature, dlossw, reducer, activation_storage, geo=None, update: bool = True):
+def _step_tensors(model, optimizer, sample, temperature, dlossw, reducer, activation_storage, geo=None, update: bool = True,
+                  conv_arithmetic: Optional[str] = None):
     """train_step without the host read of the loss: returns the two 0-dim device tensors.  geo: the step's geometry block
     (training.train_geometry, uploaded); None = built from the sample here.  update=False stops after the backward pass."""
-    from . import train2d_ops, training
+    from . import train2d_ops, train_ops, training
     if not model.training:                                   # walking ~1 400 modules costs 1 ms of a CPU-bound 28 ms step
         model.train()
     optimizer.zero_grad(set_to_none=True)
     imgs = sample["imgs"]
     if geo is None:
         geo = training.train_geometry(model, sample["proj_matrices"], sample["depth_values"], imgs.shape[1]).upload(imgs.device)
-    with (train2d_ops.activation_storage(activation_storage) if activation_storage is not None else contextlib.nullcontext()):
+    with (train2d_ops.activation_storage(activation_storage) if activation_storage is not None else contextlib.nullcontext()), \
+            (train_ops.conv_arithmetic(conv_arithmetic) if conv_arithmetic is not None else contextlib.nullcontext()):
         with torch.cuda.device(imgs.device):
             outputs = training.forward_train(model, imgs.float(), None, None, sample["depth"], temperature, geo=geo)
     outputs = _to_float(outputs)
@@ -250,7 +254,7 @@ class CapturedTrainStep:
      - and the loss read at its end keeps the host from running ahead.  Everything per-sample that the kernels
     need as NUMBERS (epipoles, homographies, depth range, spacings) is device data in the step's geometry block
     (training.train_geometry), so forward + loss + backward (+ the SGD update when there is one rank) are recorded ONCE per
-    ``(sample shapes, temperature, learning rate, weight decay, storage policy)`` key and replayed with
+    ``(sample shapes, temperature, learning rate, weight decay, storage policy, conv arithmetic)`` key and replayed with
 
         the sample copied into the graph's static input tensors, the geometry block rewritten, one hipGraphLaunch;
         with several ranks: the flat-bucket gradient all-reduce and the optimizer step, eagerly, after the replay.
@@ -265,9 +269,13 @@ class CapturedTrainStep:
 
     def __init__(self, model: torch.nn.Module, optimizer: torch.optim.Optimizer, reducer: Optional[GradAllReducer] = None,
                  dlossw: Sequence[float] = (0.5, 1.0, 2.0), activation_storage: Optional[str] = None, eager_steps: int = 2,
-                 max_graphs: int = 2):
+                 max_graphs: int = 2, conv_arithmetic: Optional[str] = None):
+        from . import train_ops
+        if conv_arithmetic is not None and conv_arithmetic not in train_ops.CONV_KINDS:
+            raise ValueError(f"conv arithmetic {conv_arithmetic!r}: expected 'f32' or 'split_f16'")
         self.model, self.optimizer, self.reducer = model, optimizer, reducer
         self.dlossw, self.activation_storage = tuple(dlossw), activation_storage
+        self.conv_arithmetic = conv_arithmetic               # None: the process default, read per call (part of the capture key)
         # the first backward of a model is the single-stream audit of `_backward`: with eager_steps = 0 and a model that has not run a
         # backward yet, that audit happens inside the capture and the graph keeps the weight gradients on one stream
         self.eager_steps = max(0, int(eager_steps))
@@ -289,7 +297,11 @@ class CapturedTrainStep:
     def _key(self, sample, temperature: float, geo) -> tuple:
         groups = tuple((g["lr"], g["weight_decay"], g.get("momentum", 0)) for g in self.optimizer.param_groups)
         shapes = tuple((n, tuple(t.shape), t.dtype) for n, t in self._sample_tensors(sample))
-        return (shapes, float(temperature), groups, geo.layout(), self.activation_storage, self._multi_rank())
+        return (shapes, float(temperature), groups, geo.layout(), self.activation_storage, self._multi_rank(), self._conv_mode())
+
+    def _conv_mode(self) -> str:
+        from . import train_ops
+        return self.conv_arithmetic if self.conv_arithmetic is not None else train_ops.get_conv_arithmetic()
 
     def _capture(self, sample, temperature: float, geo) -> dict:
         dev = sample["imgs"].device
@@ -311,7 +323,7 @@ class CapturedTrainStep:
             with torch.cuda.graph(e["graph"], stream=st):
                 e["loss"], e["depth_loss"] = _step_tensors(self.model, self.optimizer, st_sample, temperature, self.dlossw, None,
                                                            self.activation_storage, geo=geo.bind(e["block"]),
-                                                           update=not self._multi_rank())
+                                                           update=not self._multi_rank(), conv_arithmetic=self._conv_mode())
         cur.wait_stream(st)
         self.captures += 1
         e["calls"] = 0
@@ -333,7 +345,7 @@ class CapturedTrainStep:
                 if e["eager"] < self.eager_steps:            # real steps, eagerly: audit + warm-up
                     e["eager"] += 1
                     return _step_tensors(self.model, self.optimizer, sample, temperature, self.dlossw, self.reducer,
-                                         self.activation_storage, geo=geo.upload(imgs.device))
+                                         self.activation_storage, geo=geo.upload(imgs.device), conv_arithmetic=self._conv_mode())
                 e.update(self._capture(sample, temperature, geo))
             for name, t in self._sample_tensors(sample):
                 dst = e["static"][name]

@@ -576,6 +576,33 @@ int cds_bn3d_bwd_norm_f32(const float* dout, const float* y, const float* scale,
 int cds_conv3d_wgrad_f32(const float* g, const float* xin, float* dw, int B, int Ca, int Cb, int Do, int Ho, int Wo, int Di,
                          int Hi, int Wi, int stride, void* stream);
 
+/* ---- CostRegNet training convolutions in split-f16 (train_ops.conv_arithmetic("split_f16"); csrc/train3d_sf16.hip) -------------
+ * Every fp32 operand is two fp16 terms of (value x s), s the power of two of sf16_scale(bound) for a DEVICE-resident upper bound of
+ * max |x|; three v_mfma_f32_16x16x32_f16 products per K-step, fp32 accumulation, exact rescale.  No host reads: graph-capturable.
+ *   cds_bn3d_norm_bound_f32 / cds_bn3d_bwd_norm_bound_f32: cds_bn3d_norm_f32 / cds_bn3d_bwd_norm_f32 that also raise *out_bound /
+ *                             *dy_bound (zeroed by the caller) to the max |value| they store
+ *   cds_absmax_bound_f32:     *bound = max(*bound, max |x[0..n)|)
+ *   cds_sf16_pack_conv3d_f32: w [A][B][27] (mode 0 / 1: Conv3d stride 1 / 2, A = Cout; mode 2: ConvTranspose3d, A = Cin), A, B
+ *                             multiples of 8, <= 64: *w_inv = 1 / s_w from max |w| on the device, fwd / dgrad (either may be NULL) the
+ *                             hi / lo operands [C/8][28][2][Mpad][8] fp16 of the forward and of the data gradient (the stride-1
+ *                             convolution's flipped and transposed; the stride-2 convolution's for mode 2, the transposed one's for mode 1)
+ *   cds_conv3d_k3_sf16_f32:   y [B][M][..] from x [B][C][Di][Hi][Wi] and a pack; mode 0: stride-1 convolution, 1: stride 2 (pad 1),
+ *                             2: transposed k3 s2 (pad 1, output padding 1: [2Di][2Hi][2Wi]).  C a multiple of 8, M <= 64
+ *   cds_conv3d_wgrad_sf16_f32: cds_conv3d_wgrad_f32 (dw accumulated onto) with bounds of g and xin on the device */
+int cds_bn3d_norm_bound_f32(const float* y, const double* sums, const float* gamma, const float* beta, double n, double eps,
+                            float momentum, float* running_mean, float* running_var, const float* skip, float* out, float* scale,
+                            float* shift, double* mean, double* invstd, int B, int C, long long V, int relu, float* out_bound,
+                            void* stream);
+int cds_bn3d_bwd_norm_bound_f32(const float* dout, const float* y, const float* scale, const float* shift, const double* sums,
+                                const double* mean, const double* invstd, double n, float* dy, float* dgamma, float* dbeta, int B, int C,
+                                long long V, int relu, float* dy_bound, void* stream);
+int cds_absmax_bound_f32(const float* x, long long n, float* bound, void* stream);
+int cds_sf16_pack_conv3d_f32(const float* w, void* fwd, void* dgrad, float* w_inv, int A, int B, int mode, void* stream);
+int cds_conv3d_k3_sf16_f32(const float* x, const void* wpk, const float* w_inv, const float* x_bound, float* y, int B, int C, int M,
+                           int Di, int Hi, int Wi, int mode, void* stream);
+int cds_conv3d_wgrad_sf16_f32(const float* g, const float* xin, const float* g_bound, const float* x_bound, float* dw, int B, int Ca,
+                              int Cb, int Do, int Ho, int Wo, int Di, int Hi, int Wi, int stride, void* stream);
+
 /* ---- training step, 2D stacks (csrc/train2d.hip) ---------------------------------------------------------------
  * Backward kernels of FeatureNet / DynamicConv (models/dynamic_conv.py:97-122, models/module.py:28-71,234-267), the visibility CNN
  * (models/model.py:14,51), Refinement (models/module.py:318-370) and depth_regression (models/module.py:373-379); they replace what

@@ -10,7 +10,8 @@ keys, so no reference weights or source text are vendored.  Only data (inputs + 
 written, as ``tests/golden/*.npz``.  Fixtures: G1 warp/aggregate, G2 CostRegNet,
 G3 regression, G4 hypotheses, G5 DynamicConv/FeatureNet/epipoles, G6 full forward.  The one exception is G12: the
 trained weights of the reference's three checkpoints outside CostRegNet (weights only, no pickled objects) with the
-reference's forward on them, so that trained-weight parity is checked from the repository alone.
+reference's forward on them, so that trained-weight parity is checked from the repository alone; G13 adds one trained
+CostRegNet (the stage-3 one of the checkpoint with the largest BatchNorm fold factors) and the forward with it.
 """
 import os
 import sys
@@ -533,9 +534,70 @@ def g12_trained_checkpoints():
         save(f"g12_trained_{tag}", **arrays)
 
 
+def _bn_fold_factors(sd, prefix):
+    """max over the BatchNorms of one CostRegNet of the inference-time fold factors |gamma| / sqrt(running_var + eps)."""
+    return max((sd[k].abs() / torch.sqrt(sd[k[:-len("weight")] + "running_var"] + 1e-5)).max().item()
+               for k in sd if k.startswith(prefix) and k.endswith(".bn.weight"))
+
+
+def shuffle_bytes(a):
+    """float32 array -> uint8 [4, n]: byte plane j holds byte j of every value.  Lossless; the sign / exponent plane of trained
+    weights deflates far better apart from the mantissa bytes (tests/test_trained_checkpoints.py undoes it)."""
+    a = np.ascontiguousarray(np.asarray(a, dtype=np.float32))
+    return np.ascontiguousarray(a.view(np.uint8).reshape(-1, 4).T)
+
+
+@torch.no_grad()
+def g13_trained_costreg():
+    """ONE trained CostRegNet: the stage-3 one (cost_regularization.2, in_channels 8) of the checkpoint whose BatchNorm fold factors
+    |gamma| / sqrt(running_var + eps) reach furthest over all nine CostRegNets (``checkpoint``, ``max_fold``: the largest per tensor,
+    the one split-f16 inference scales its folded weights by).  ``w.<key>``: its state-dict entries, float32 ones byte-shuffled
+    (``shuffle_bytes``; ``shape.<key>`` their shapes): 293 k parameters only fit the repository's 1 MiB file limit that way.
+    g13_trained_costreg_out.npz: the reference forward of G12's scene (3 views, 192x128, seed 4, refine=True, T = 0.01) with that
+    checkpoint's G12 weights, this trained stage-3 CostRegNet and the seeded stage-1 / stage-2 CostRegNets (``out.*`` as in G12)."""
+    from cds_mvsnet_amd import CDSMVSNet
+    from cds_mvsnet_amd.infer import _placeholder_pickle
+    N, H, W = 3, 128, 192
+    imgs = synth.make_images(N, H, W, seed=4)
+    cams = synth.make_cameras(N, H, W, refine=True, seed=4)
+    dv = synth.make_depth_values()
+    seeded = seeded_init_(CDSMVSNet(refine=True, ndepths=(48, 32, 8), depth_interals_ratio=(4.0, 1.5, 0.75)), SEED).state_dict()
+    pretrained = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(sys.modules["models"].__file__))), "pretrained")
+    trained, folds = {}, {}
+    for tag, path in G12_CHECKPOINTS.items():
+        ck = torch.load(os.path.join(pretrained, path), map_location="cpu", weights_only=False, pickle_module=_placeholder_pickle)
+        trained[tag] = {k.replace("module.", ""): v for k, v in ck["state_dict"].items()}
+        folds[tag] = max(_bn_fold_factors(trained[tag], f"cost_regularization.{s}.") for s in range(3))
+        print(f"{tag}: largest BN fold factor over its CostRegNets {folds[tag]:.1f}, "
+              f"stage 3 {_bn_fold_factors(trained[tag], 'cost_regularization.2.'):.1f}")
+    tag = max(folds, key=folds.get)
+    cr = {k: v for k, v in trained[tag].items() if k.startswith("cost_regularization.2.")}
+    g12 = np.load(os.path.join(HERE, f"g12_trained_{tag}.npz"))
+    sd = {k[2:]: torch.from_numpy(g12[k]) for k in g12.files if k.startswith("w.")}
+    sd.update({k: v for k, v in seeded.items() if k.startswith("cost_regularization.")})
+    sd.update(cr)
+    m = RefNet(refine=True, ndepths=(48, 32, 8), depth_interals_ratio=(4.0, 1.5, 0.75))
+    m.load_state_dict(sd, strict=True)
+    out = m.eval()(imgs, cams, dv, temperature=0.01)
+    arrays = {"checkpoint": np.array(tag), "max_fold": np.array(_bn_fold_factors(cr, "cost_regularization.2."), dtype=np.float32)}
+    for k, v in cr.items():
+        if v.dtype == torch.float32:
+            arrays["w." + k], arrays["shape." + k] = shuffle_bytes(v.numpy()), np.array(v.shape, dtype=np.int64)
+        else:
+            arrays["w." + k] = v
+    save("g13_trained_costreg", **arrays)
+    outs = {"checkpoint": np.array(tag)}
+    for s in range(3):
+        st = out[f"stage{s + 1}"]
+        for k in ("depth", "photometric_confidence", "norm_curv"):
+            outs[f"out.stage{s + 1}.{k}"] = st[k]
+    outs["out.refined_depth"] = out["refined_depth"]
+    save("g13_trained_costreg_out", **outs)
+
+
 if __name__ == "__main__":
     only = sys.argv[1:]
     for fn in (g1_warp_aggregate, g2_costreg, g3_regress, g4_hypotheses, g5_features, g6_forward, g7_training_step,
-               g8_fusion, g9_feature_noise, g10_formats, g11_loss, g12_trained_checkpoints):
+               g8_fusion, g9_feature_noise, g10_formats, g11_loss, g12_trained_checkpoints, g13_trained_costreg):
         if not only or fn.__name__.split("_")[0] in only:
             fn()

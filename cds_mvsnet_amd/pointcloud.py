@@ -1,0 +1,279 @@
+"""Point-cloud primitives of the DTU evaluation on the GPU: capped nearest-neighbour distances, greedy thinning to a minimum
+spacing, and a PLY vertex reader.
+
+The hot paths are the HIP kernels of ``csrc/pointcloud.hip`` (``include/cds_mvsnet_hip.h``): a sparse uniform grid with 64-bit
+cell keys and a hash table, queried one point per lane.  torch is used for device memory and for the sort / unique / cumsum
+that lay the grid out.  Inputs must be float32 ROCm tensors; there is no CPU path.
+"""
+from __future__ import annotations
+
+import math
+from typing import Optional
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import check
+from .ops import _dev, _stream
+
+Tensor = torch.Tensor
+
+_MAX_AXIS = 1 << 21          # fine cells per axis that a key can address
+_LOCAL_BITS = 9              # fine position inside its coarse cell (3 bits per axis)
+_COARSE_FLAG = -(1 << 63)    # bit 63: coarse keys in the shared hash table
+
+
+def _points(t: Tensor, name: str) -> Tensor:
+    if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.shape[1] != 3:
+        raise ValueError(f"{name}: expected a [N,3] tensor, got {getattr(t, 'shape', type(t))}")
+    _dev(t.contiguous(), name)                         # device, dtype and current-device checks
+    if t.shape[0] > 2 ** 31 - 1:
+        raise ValueError(f"{name}: at most 2^31 - 1 points")
+    return t.contiguous()
+
+
+class PointGrid:
+    """A sparse uniform grid over ``points`` [N,3] (float32, device) with fine cells of side ``cell``.
+
+    Attributes (device tensors unless noted): ``pts`` [N,4] the points sorted by cell key (w = ``rank`` as int bits when
+    given), ``perm`` [N] int64 sorted position -> input index, ``cell_keys`` [F] int64, ``cell_start`` [F+1] int32,
+    ``coarse_start`` [C+1] int32, ``table_keys`` / ``table_vals`` the hash table, ``frame`` (CPU float32 [8]): origin,
+    cell side, slop, cells per axis."""
+
+    def __init__(self, points: Tensor, cell: Optional[float], rank: Optional[Tensor] = None,
+                 thin_dist: Optional[float] = None):
+        points = _points(points, "points")
+        n = points.shape[0]
+        if n == 0:
+            raise ValueError("PointGrid: no points")
+        lib = _lib.load()
+        lo, hi = torch.aminmax(points, dim=0)
+        lo, hi = lo.double().cpu().numpy(), hi.double().cpu().numpy()
+        if not (np.isfinite(lo).all() and np.isfinite(hi).all()):
+            raise ValueError("PointGrid: points must be finite")
+        ext = float((hi - lo).max())
+        self.slop = 2.0 ** -18 * (float(np.abs(np.concatenate([lo, hi])).max()) + ext) + 1e-30
+        if thin_dist is not None:       # thinning: above min_dist plus the binning error, so 27 cells cover min_dist
+            cell = thin_dist * (1.0 + 2.0 ** -10) + 4.0 * self.slop
+        if not (cell is not None and cell > 0 and math.isfinite(cell)):
+            raise ValueError(f"PointGrid: cell side must be positive, got {cell}")
+        self.cell = max(float(cell), ext / (_MAX_AXIS - 64))
+        origin = (lo - self.cell).astype(np.float32)
+        dims = np.floor((hi - origin) / self.cell).astype(np.int64) + 3
+        self.frame = torch.tensor([*origin.tolist(), self.cell, self.slop, *dims.tolist()], dtype=torch.float32)
+        self.device = points.device
+        stream = _stream(points)
+
+        keys = torch.empty(n, dtype=torch.int64, device=self.device)
+        check(lib.cds_grid_keys_f32(points.data_ptr(), n, self.frame.data_ptr(), keys.data_ptr(), stream), "cds_grid_keys_f32")
+        skeys, self.perm = torch.sort(keys, stable=True)
+        self.cell_keys, counts = torch.unique_consecutive(skeys, return_counts=True)
+        self.cell_start = _offsets(counts)
+        ckeys, ccounts = torch.unique_consecutive(self.cell_keys >> _LOCAL_BITS, return_counts=True)
+        self.coarse_start = _offsets(ccounts)
+        all_keys = torch.cat([self.cell_keys, ckeys | _COARSE_FLAG])
+        self.log2_slots = lib.cds_grid_hash_log2_slots(all_keys.numel())
+        if self.log2_slots < 0:
+            raise ValueError("PointGrid: too many cells")
+        self.table_keys = torch.empty(1 << self.log2_slots, dtype=torch.int64, device=self.device)
+        self.table_vals = torch.empty(1 << self.log2_slots, dtype=torch.int32, device=self.device)
+        check(lib.cds_grid_hash_build(all_keys.data_ptr(), all_keys.numel(), self.cell_keys.numel(), self.table_keys.data_ptr(),
+                                      self.table_vals.data_ptr(), self.log2_slots, stream), "cds_grid_hash_build")
+        self.pts = torch.zeros((n, 4), dtype=torch.float32, device=self.device)
+        self.pts[:, :3] = points[self.perm]
+        if rank is not None:             # integer copy: rank bits must not pass through float arithmetic
+            self.pts.view(torch.int32)[:, 3] = rank.to(self.device, torch.int32)[self.perm]
+        self.n = n
+
+    def keys(self, points: Tensor) -> Tensor:
+        """Fine cell keys of arbitrary points in this grid's frame (coordinates clamped to the grid)."""
+        keys = torch.empty(points.shape[0], dtype=torch.int64, device=self.device)
+        check(_lib.load().cds_grid_keys_f32(points.data_ptr(), points.shape[0], self.frame.data_ptr(), keys.data_ptr(),
+                                            _stream(points)), "cds_grid_keys_f32")
+        return keys
+
+
+def _offsets(counts: Tensor) -> Tensor:
+    out = torch.zeros(counts.numel() + 1, dtype=torch.int32, device=counts.device)
+    out[1:] = torch.cumsum(counts, 0).to(torch.int32)
+    return out
+
+
+def default_cell(points: Tensor) -> float:
+    """Fine cell side for nearest-neighbour grids: twice the spacing of N points spread over the largest face of the
+    bounding box (scanned clouds are surfaces; the coarse level absorbs a mismatch).  Only speed depends on it."""
+    lo, hi = torch.aminmax(points, dim=0)
+    e = sorted((hi - lo).double().cpu().tolist())
+    area = max(e[1] * e[2], 1e-12)
+    return max(2.0 * math.sqrt(area / max(points.shape[0], 1)), 1e-6 * max(e[2], 1.0))
+
+
+def nearest_distance(query: Tensor, target: Tensor, max_dist: float, grid: Optional[PointGrid] = None,
+                     cell: Optional[float] = None) -> Tensor:
+    """For every query point [M,3] the distance to its nearest target point [N,3], capped at ``max_dist``:
+    ``min(min_j |q - t_j|, max_dist)`` in fp32 with d2 = dx*dx + dy*dy + dz*dz (MaxDistCP.m, PointCompareMain.m:20-26;
+    inside its block grid MaxDistCP returns exactly this, outside it max_dist).  An empty target gives max_dist everywhere.
+    ``grid``: a PointGrid of ``target`` to reuse; ``cell``: its cell side (default: :func:`default_cell`)."""
+    query = _points(query, "query")
+    if not (max_dist >= 0):
+        raise ValueError(f"nearest_distance: max_dist must be >= 0, got {max_dist}")
+    m = query.shape[0]
+    if target.shape[0] == 0 or m == 0:
+        _points(target, "target")
+        return torch.full((m,), float(max_dist), dtype=torch.float32, device=query.device)
+    if grid is None:
+        target = _points(target, "target")
+        grid = PointGrid(target, cell if cell is not None else default_cell(target))
+    order = torch.sort(grid.keys(query), stable=True)[1]          # cell order: a wave's lanes search the same cells
+    out = torch.empty(m, dtype=torch.float32, device=query.device)
+    check(_lib.load().cds_nn_query_f32(query.data_ptr(), order.data_ptr(), m, grid.pts.data_ptr(), grid.cell_start.data_ptr(),
+                                       grid.cell_keys.data_ptr(), grid.coarse_start.data_ptr(), grid.table_keys.data_ptr(),
+                                       grid.table_vals.data_ptr(), grid.log2_slots, grid.frame.data_ptr(), float(max_dist),
+                                       out.data_ptr(), _stream(query)), "cds_nn_query_f32")
+    return out
+
+
+def thinning_order(n: int, seed: int = 0) -> Tensor:
+    """The visiting order of :func:`reduce_points`: ``torch.randperm`` from a CPU generator seeded with ``seed``, the same on
+    every machine (MATLAB's ``randperm`` of reducePts_haa.m:9 cannot be reproduced)."""
+    return torch.randperm(n, generator=torch.Generator().manual_seed(int(seed)))
+
+
+def reduce_points(points: Tensor, min_dist: float, order: Optional[Tensor] = None, seed: int = 0,
+                  check_every: int = 4, info: Optional[dict] = None) -> Tensor:
+    """Greedy thinning of reducePts_haa.m (PointCompareMain.m:7): visit the points in ``order`` (a permutation of range(N);
+    default :func:`thinning_order` of ``seed``); a point still kept removes every other point within ``min_dist``
+    (d2 <= min_dist^2 in fp32).  -> keep mask bool[N] on the points' device, the greedy maximal independent set in that
+    order.  Computed in parallel rounds (cds_thin_round_f32) that converge to the same set bit for bit; the host reads
+    the count of undecided points every ``check_every`` rounds.  ``info``: a dict that receives the number of rounds."""
+    points = _points(points, "points")
+    n = points.shape[0]
+    if not (min_dist > 0 and math.isfinite(min_dist)):
+        raise ValueError(f"reduce_points: min_dist must be positive, got {min_dist}")
+    if n == 0:
+        return torch.zeros(0, dtype=torch.bool, device=points.device)
+    if order is None:
+        order = thinning_order(n, seed).to(points.device)
+    else:
+        order = torch.as_tensor(order).to(points.device, torch.int64).reshape(-1)
+        if order.numel() != n or not bool(((order >= 0) & (order < n)).all()) or \
+                not bool((torch.bincount(order, minlength=n) == 1).all()):
+            raise ValueError("reduce_points: order must be a permutation of range(N)")
+    rank = torch.empty(n, dtype=torch.int32, device=points.device)
+    rank[order] = torch.arange(n, dtype=torch.int32, device=points.device)
+    lib = _lib.load()
+    f = float(np.float32(min_dist))
+    grid = PointGrid(points, None, rank=rank, thin_dist=f)
+    if grid.cell < f:
+        raise ValueError("reduce_points: cell side below min_dist")
+    state = torch.zeros(n, dtype=torch.uint8, device=points.device)
+    counter = torch.zeros(1, dtype=torch.int32, device=points.device)
+    stream = _stream(points)
+    rounds = 0
+    while True:
+        counter.zero_()
+        for k in range(check_every):
+            check(lib.cds_thin_round_f32(grid.pts.data_ptr(), grid.cell_start.data_ptr(), n, grid.table_keys.data_ptr(),
+                                         grid.table_vals.data_ptr(), grid.log2_slots, grid.frame.data_ptr(), f,
+                                         state.data_ptr(), counter.data_ptr() if k == check_every - 1 else None, stream),
+                  "cds_thin_round_f32")
+        rounds += check_every
+        if int(counter.item()) == 0:
+            break
+        if rounds > n + check_every:                    # each round decides the lowest-rank undecided point
+            raise RuntimeError("reduce_points: thinning rounds did not converge")
+    keep = torch.empty(n, dtype=torch.bool, device=points.device)
+    keep[grid.perm] = state == 1
+    if info is not None:
+        info["rounds"] = rounds
+    return keep
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+_PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2", "ushort": "u2",
+              "uint16": "u2", "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4",
+              "double": "f8", "float64": "f8"}
+
+
+def read_ply_points(path: str) -> np.ndarray:
+    """x, y, z of the ``vertex`` element of a PLY file as float32 [N,3]: ascii, binary_little_endian or binary_big_endian,
+    any scalar vertex properties (x, y, z picked by name), other elements before or after it skipped (what plyread.m
+    reads at BaseEvalMain_web.m:47-48 and PointCompareMain.m:12-13)."""
+    with open(path, "rb") as f:
+        if f.readline().strip() != b"ply":
+            raise ValueError(f"{path}: not a PLY file")
+        fmt, elements = None, []                      # elements: [name, count, [(prop, type) | (prop, (count_t, item_t))]]
+        while True:
+            line = f.readline()
+            if not line:
+                raise ValueError(f"{path}: PLY header without end_header")
+            tok = line.decode("ascii", "replace").split()
+            if not tok or tok[0] in ("comment", "obj_info"):
+                continue
+            if tok[0] == "end_header":
+                break
+            if tok[0] == "format":
+                fmt = tok[1]
+            elif tok[0] == "element":
+                elements.append([tok[1], int(tok[2]), []])
+            elif tok[0] == "property":
+                if not elements:
+                    raise ValueError(f"{path}: property before any element")
+                if tok[1] == "list":
+                    elements[-1][2].append((tok[4], (_ply_type(tok[2], path), _ply_type(tok[3], path))))
+                else:
+                    elements[-1][2].append((tok[2], _ply_type(tok[1], path)))
+        if fmt not in ("ascii", "binary_little_endian", "binary_big_endian"):
+            raise ValueError(f"{path}: unsupported PLY format {fmt}")
+        names = [e[0] for e in elements]
+        if "vertex" not in names:
+            raise ValueError(f"{path}: no vertex element")
+        end = ">" if fmt == "binary_big_endian" else "<"
+        for name, count, props in elements:
+            if name == "vertex":
+                pnames = [p[0] for p in props]
+                for c in "xyz":
+                    if c not in pnames:
+                        raise ValueError(f"{path}: vertex element has no property {c}")
+                if any(isinstance(p[1], tuple) for p in props):
+                    raise ValueError(f"{path}: list properties in the vertex element are not supported")
+                if fmt == "ascii":
+                    rows = [f.readline() for _ in range(count)]
+                    vals = np.array(b" ".join(rows).split(), dtype=np.float64)
+                    if vals.size != count * len(props):
+                        raise ValueError(f"{path}: truncated ascii vertex data")
+                    vals = vals.reshape(count, len(props))
+                    return np.stack([vals[:, pnames.index(c)] for c in "xyz"], 1).astype(np.float32)
+                dt = np.dtype([(p, end + t) for p, t in props])
+                raw = f.read(dt.itemsize * count)
+                if len(raw) != dt.itemsize * count:
+                    raise ValueError(f"{path}: truncated binary vertex data")
+                rec = np.frombuffer(raw, dtype=dt, count=count)
+                return np.stack([rec[c].astype(np.float32) for c in "xyz"], 1)
+            _skip_element(f, fmt, end, count, props, path)
+    raise AssertionError("unreachable")
+
+
+def _ply_type(t: str, path: str) -> str:
+    if t not in _PLY_TYPES:
+        raise ValueError(f"{path}: unknown PLY type {t}")
+    return _PLY_TYPES[t]
+
+
+def _skip_element(f, fmt, end, count, props, path):
+    if fmt == "ascii":
+        for _ in range(count):
+            f.readline()
+        return
+    if not any(isinstance(p[1], tuple) for p in props):
+        f.seek(np.dtype([(p, end + t) for p, t in props]).itemsize * count, 1)
+        return
+    for _ in range(count):
+        for _, t in props:
+            if isinstance(t, tuple):
+                cdt = np.dtype(end + t[0])
+                k = int(np.frombuffer(f.read(cdt.itemsize), cdt)[0])
+                f.seek(k * np.dtype(t[1]).itemsize, 1)
+            else:
+                f.seek(np.dtype(t).itemsize, 1)

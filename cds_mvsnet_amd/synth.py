@@ -141,3 +141,54 @@ def make_fusion_scene(n_views: int, h: int, w: int, seed: int = 0, outlier_frac:
     g = torch.Generator().manual_seed(seed + 5)
     return {"depths": torch.from_numpy(np.stack(depths)), "confs": torch.rand(n_views, 3, h, w, generator=g),
             "cams": cams.contiguous(), "imgs": torch.rand(n_views, h, w, 3, generator=g)}
+
+
+def fusion_surface(x, y):
+    """The height field of :func:`make_fusion_scene`: Z = 650 + 40 sin(X/60) cos(Y/50) (float64 numpy)."""
+    return 650.0 + 40.0 * np.sin(np.asarray(x, np.float64) / 60.0) * np.cos(np.asarray(y, np.float64) / 50.0)
+
+
+def make_dtu_scene(half_x: float, half_y: float, spacing: float, res: float, margin: float, plane_z: float = 630.0,
+                   n_pred: int = 0, noise: float = 0.0, outlier_frac: float = 0.0, outlier_range: float = 30.0,
+                   holes: int = 0, hole_radius: float = 0.0, seed: int = 0) -> Dict[str, np.ndarray]:
+    """Ground truth in the layout of the DTU evaluation files for the height field of :func:`make_fusion_scene`, over
+    |X| <= half_x, |Y| <= half_y:
+      stl      float32 [N,3]: the surface sampled on a jittered grid of pitch ``spacing``;
+      ObsMask  bool [X,Y,Z] voxels of side ``res`` over BB: set within ``margin`` of the surface, except for |X| > 0.8 half_x;
+      BB       float64 [2,3] (min row, max row), Res, P float64 [4]: the plane z = plane_z (points above it count);
+      pred     float32 [n_pred,3] (when n_pred > 0): uniform surface samples with N(0, noise) normal jitter, ``holes`` empty
+               discs of radius ``hole_radius`` and ``outlier_frac`` points moved up to ``outlier_range`` off the surface."""
+    rs = np.random.RandomState(seed)
+    xs = np.arange(-half_x, half_x + 1e-9, spacing)
+    ys = np.arange(-half_y, half_y + 1e-9, spacing)
+    gx, gy = np.meshgrid(xs, ys, indexing="ij")
+    gx = gx.reshape(-1) + rs.uniform(-0.25, 0.25, gx.size) * spacing
+    gy = gy.reshape(-1) + rs.uniform(-0.25, 0.25, gy.size) * spacing
+    stl = np.stack([gx, gy, fusion_surface(gx, gy)], 1).astype(np.float32)
+    lo = np.array([-half_x, -half_y, 610.0]) - margin - 2 * res
+    hi = np.array([half_x, half_y, 690.0]) + margin + 2 * res
+    bb = np.stack([lo, hi])
+    dims = np.floor((hi - lo) / res).astype(int) + 1
+    cx, cy, cz = [lo[a] + res * np.arange(dims[a]) for a in range(3)]          # voxel (i,j,k) centre: BB(1,:) + (ijk - 1) Res
+    surf = fusion_surface(cx[:, None], cy[None, :])
+    obs = np.abs(cz[None, None, :] - surf[:, :, None]) <= margin
+    obs[np.abs(cx) > 0.8 * half_x] = False
+    out = {"stl": stl, "ObsMask": obs, "BB": bb, "Res": float(res), "P": np.array([0.0, 0.0, 1.0, -plane_z])}
+    if n_pred > 0:
+        g = torch.Generator().manual_seed(seed + 1)
+        u = torch.rand(n_pred, 2, generator=g, dtype=torch.float64).numpy()
+        px, py = (u[:, 0] * 2 - 1) * half_x, (u[:, 1] * 2 - 1) * half_y
+        pz = fusion_surface(px, py) + noise * torch.randn(n_pred, generator=g, dtype=torch.float64).numpy()
+        pred = np.stack([px, py, pz], 1)
+        if holes:
+            centres = rs.uniform(-0.7, 0.7, (holes, 2)) * np.array([half_x, half_y])
+            inside = np.zeros(pred.shape[0], bool)
+            for c in centres:
+                inside |= ((pred[:, 0] - c[0]) ** 2 + (pred[:, 1] - c[1]) ** 2) <= hole_radius ** 2
+            pred = pred[~inside]
+        n_out = int(outlier_frac * pred.shape[0])
+        if n_out:
+            idx = rs.choice(pred.shape[0], n_out, replace=False)
+            pred[idx] += rs.uniform(-outlier_range, outlier_range, (n_out, 3))
+        out["pred"] = pred.astype(np.float32)
+    return out

@@ -707,6 +707,41 @@ int cds_feat_target_f32(const float* hyp, const float* gt, const float* di, floa
 int cds_bn_running_update_f32(const float* batch_mean, const float* batch_var, const float* group_weights, float keep, int G, int C,
                               float* running_mean, float* running_var, void* stream);
 
+/*
+ * Point-cloud evaluation (the DTU Acc / Comp protocol, the .m files of evaluations/dtu; cds_mvsnet_amd/pointcloud.py, dtu_eval.py).
+ * A sparse uniform grid over a point set: fine cells of side h addressed by 63-bit keys, coarse cell (8 x 8 x 8 fine cells) in
+ * the high bits, so that points sorted by key lie cell by cell and the fine cells of a coarse cell are contiguous too.
+ *   frame_host  8 floats, HOST: origin x y z, cell side h, slop (bound on how far fp32 binning puts a point outside its nominal
+ *               cell; every pruning test is widened by it), fine cells per axis nx ny nz (integers, each <= 2^21)
+ *   points      [n][3] fp32; pts [n][4] = the grid's points sorted by key (w: the rank as int bits for thinning, unused by
+ *               the queries); cell_start [F+1] int32 point offsets of the F unique fine keys cell_keys [F] (int64, ascending);
+ *               coarse_start [C+1] int32 offsets into the fine cells of the C unique coarse keys (cell_keys >> 9)
+ *   table_keys [2^log2_slots] int64 / table_vals [2^log2_slots] int32: hash table of the fine keys (value = fine index) and the
+ *               coarse keys with bit 63 set (value = coarse index); indices are int32, so point counts up to 2^31 - 1
+ * cds_grid_hash_log2_slots  size query: log2 of the table size for n_keys keys (load <= 1/2), or CDS_EINVAL
+ * cds_grid_keys_f32         keys[i] = the fine key of point i, cell coordinates floor((p - o) / h) clamped to the grid
+ * cds_grid_hash_build       clear the table and insert keys[0..n_keys) (unique; the first n_fine are fine keys)
+ * cds_nn_query_f32          dist[order[i]] = min(distance from query[order[i]] to its nearest grid point, max_dist), in fp32 with
+ *                           d2 = dx*dx + dy*dy + dz*dz: MaxDistCP.m with the block grid dropped (capped exact nearest neighbour;
+ *                           PointCompareMain.m:20-26).  order: a permutation of the m queries (cell order keeps a wave's
+ *                           lanes in the same cells) or NULL
+ * cds_thin_round_f32        one round of the greedy thinning of reducePts_haa.m:19-31 (PointCompareMain.m:7): state [n] in
+ *                           sorted order, 0 undecided / 1 kept / 2 removed.  An undecided point is removed once a lower-rank
+ *                           point within min_dist (d2 <= min_dist^2, fp32) is kept and kept once none is undecided; the rounds
+ *                           converge to the greedy maximal independent set in rank order bit for bit.  undecided (device int,
+ *                           or NULL) is incremented for every point left undecided.  Requires h >= min_dist (27 cells cover it).
+ */
+int cds_grid_hash_log2_slots(long long n_keys);
+int cds_grid_keys_f32(const float* points, long long n, const float* frame_host, long long* keys, void* stream);
+int cds_grid_hash_build(const long long* keys, long long n_keys, long long n_fine, long long* table_keys, int* table_vals,
+                        int log2_slots, void* stream);
+int cds_nn_query_f32(const float* query, const long long* order, long long m, const float* pts, const int* cell_start,
+                     const long long* cell_keys, const int* coarse_start, const long long* table_keys, const int* table_vals,
+                     int log2_slots, const float* frame_host, float max_dist, float* dist, void* stream);
+int cds_thin_round_f32(const float* pts, const int* cell_start, long long n, const long long* table_keys, const int* table_vals,
+                       int log2_slots, const float* frame_host, float min_dist, unsigned char* state, int* undecided,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -141,6 +141,11 @@ SIGNATURES = {
     "cds_grid_hash_build": [P, L, L, P, P, I, P],
     "cds_nn_query_f32": [P, P, L, P, P, P, P, P, P, I, P, F, P, P],
     "cds_thin_round_f32": [P, P, L, P, P, I, P, F, P, P, P],
+    "cds_gipuma_tiles": [L],
+    "cds_gipuma_prob_filter_f32": [P, P, P, I, I, I, P, P, P, P],
+    "cds_gipuma_fuse_view_f32": [P, P, P, P, I, I, I, I, F, F, F, I, P, P, P, P],
+    "cds_gipuma_scan": [P, I, P, P, P, P],
+    "cds_gipuma_compact_f32": [P, P, P, I, I, P, P, P, P],
 }
 
 _lib = None

@@ -6,7 +6,8 @@
 One process per GPU: with `python -m torch.distributed.run --nproc-per-node N -m cds_mvsnet_amd.infer ...` every rank takes
 the reference views `idx % world == rank` (independent depth maps, no collective).  Outputs follow the reference layout:
 `<out>/<scan>/depth_est/%08d.pfm`, `confidence/%08d.pfm` (3 channels = stage 1-3 confidences), `cams/%08d_cam.txt`,
-`images/%08d.jpg`, ready for the fusion step.
+`images/%08d.jpg`, ready for the fusion step.  `--fuse` then writes `<out>/<scan>.ply` with the normal fusion (fusion.py) or,
+with `--filter_method gipuma`, the gipuma-style one (gipuma.py; `--prob_threshold`, `--disp_threshold`, `--num_consistent`).
 """
 from __future__ import annotations
 
@@ -145,12 +146,20 @@ def run(args) -> float:
     if args.fuse:
         # step 2 of the reference's test.py (pcd_filter, test.py:386-396): scans are independent -> shard over ranks
         from .fusion import filter_depth
+        from .gipuma import filter_scan
         if world > 1:  # every rank's depth maps must be on disk before any scan is fused
             if not torch.distributed.is_initialized():
                 torch.distributed.init_process_group("nccl", device_id=dev)
             torch.distributed.barrier()
         for i, scan in enumerate(scans):
             if i % world != rank:
+                continue
+            if args.filter_method == "gipuma":
+                # the reference's gipuma_filter (test.py:419-426) without fusibile: cds_mvsnet_amd.gipuma
+                info = filter_scan(os.path.join(args.outdir, scan), os.path.join(args.outdir, f"{scan}.ply"),
+                                   prob_threshold=[float(p) for p in args.prob_threshold.split(",")],
+                                   disp_threshold=args.disp_threshold, num_consistent=args.num_consistent, device=str(dev))
+                print(f"[{rank}] {scan}.ply: {info['points']} points from {info['views']} views (gipuma)", flush=True)
                 continue
             info = filter_depth(os.path.join(args.testpath, scan), os.path.join(args.outdir, scan),
                                 os.path.join(args.outdir, f"{scan}.ply"), conf=[float(c) for c in args.conf.split(",")],
@@ -159,7 +168,7 @@ def run(args) -> float:
     return avg
 
 
-def main(argv=None):
+def parse_args(argv=None) -> argparse.Namespace:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--testpath", required=True)
     ap.add_argument("--testlist", required=True)
@@ -179,7 +188,16 @@ def main(argv=None):
     ap.add_argument("--conf", default="0.0,0.0,0.0", help="per-stage confidence thresholds (test.py:61)")
     ap.add_argument("--thres_view", type=int, default=3)
     ap.add_argument("--thres_disp", type=float, default=1.0)
-    run(ap.parse_args(argv))
+    ap.add_argument("--filter_method", default="normal", choices=["normal", "gipuma"],
+                    help="--fuse with the normal fusion (fusion.py) or the gipuma-style one (gipuma.py)")
+    ap.add_argument("--prob_threshold", default="0.0,0.0,0.0", help="gipuma: per-stage confidence thresholds (test.py:68)")
+    ap.add_argument("--disp_threshold", type=float, default=0.2, help="gipuma: disparity threshold (test.py:69)")
+    ap.add_argument("--num_consistent", type=int, default=3, help="gipuma: consistent views a point needs (test.py:70)")
+    return ap.parse_args(argv)
+
+
+def main(argv=None):
+    run(parse_args(argv))
 
 
 if __name__ == "__main__":

@@ -1422,3 +1422,82 @@ def feat_target(hyp: Tensor, gt: Tensor, interval: Tensor, scale: float, thresh:
     check(_lib.load().cds_feat_target_f32(hyp.data_ptr(), gt.data_ptr(), interval.data_ptr(), float(scale), float(thresh), B, D, h * w,
                                           out.data_ptr(), _stream(hyp)), "cds_feat_target_f32")
     return out
+
+
+# ---- gipuma-style fusion (csrc/gipuma.hip; cds_mvsnet_amd/gipuma.py drives these) ----
+def gipuma_prob_filter(depths: Tensor, confs: Tensor, rgb8: Tensor, prob_thresh) -> Tuple[Tensor, Tensor]:
+    """All views at once: depths [V,h,w], confs [V,3,h,w] (fp32), rgb8 [V,h,w,3] (uint8) on the device -> (D' [V,h,w] fp32 with
+    the pixels whose confidences do not all exceed prob_thresh set to 0, rgb [V,h,w] int32 = r | g << 8 | b << 16)."""
+    V, h, w = depths.shape
+    if tuple(confs.shape) != (V, 3, h, w) or tuple(rgb8.shape) != (V, h, w, 3):
+        raise ValueError(f"gipuma_prob_filter: confs {tuple(confs.shape)} / images {tuple(rgb8.shape)} do not match depths "
+                         f"{tuple(depths.shape)}")
+    th = torch.tensor([float(p) for p in prob_thresh], dtype=torch.float32)
+    if th.numel() != 3:
+        raise ValueError("gipuma_prob_filter: three probability thresholds expected")
+    out = torch.empty_like(depths)
+    rgb = torch.empty((V, h, w), dtype=torch.int32, device=depths.device)
+    check(_lib.load().cds_gipuma_prob_filter_f32(_dev(depths, "depths"), _dev(confs, "confs"), _dev_int(rgb8, torch.uint8, "images"),
+                                                 V, h, w, _host(th, "prob_thresh"), out.data_ptr(), rgb.data_ptr(), _stream(depths)),
+          "cds_gipuma_prob_filter_f32")
+    return out, rgb
+
+
+def gipuma_fuse_view(r: int, depths: Tensor, rgb: Tensor, views: Tensor, fb: Tensor, depth_min: float, depth_max: float,
+                     disp_thresh: float, num_consistent: int, used: Tensor, emit: Tensor, records: Tensor) -> None:
+    """Reference view r of the rule in csrc/gipuma.hip: reads D' = depths [V,h,w], rgb [V,h,w] (int32), views [V,24], fb [V,V];
+    updates used [V,h,w] (uint8) of the other views and writes emit (uint8, tiles x 4096) / records [V,h,w,4] (int32) of view r.
+    Asynchronous: the caller runs r = 0 .. V-1 in order on one stream."""
+    V, h, w = depths.shape
+    if tuple(views.shape) != (V, 24) or tuple(fb.shape) != (V, V) or tuple(rgb.shape) != (V, h, w) or \
+            tuple(used.shape) != (V, h, w) or tuple(records.shape) != (V, h, w, 4) or emit.numel() < V * h * w:
+        raise ValueError("gipuma_fuse_view: inconsistent shapes")
+    if not 0 <= r < V:
+        raise ValueError(f"gipuma_fuse_view: reference view {r} out of range [0, {V})")
+    check(_lib.load().cds_gipuma_fuse_view_f32(_dev(depths, "depths"), _dev_int(rgb, torch.int32, "rgb"), _dev(views, "views"),
+                                               _dev(fb, "fb"), int(r), V, h, w, float(depth_min), float(depth_max),
+                                               float(disp_thresh), int(num_consistent), _dev_int(used, torch.uint8, "used"),
+                                               _dev_int(emit, torch.uint8, "emit"), _dev_int(records, torch.int32, "records"),
+                                               _stream(depths)), "cds_gipuma_fuse_view_f32")
+
+
+def _dev_int(t: Tensor, dtype: torch.dtype, name: str) -> int:
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype and t.is_contiguous()):
+        raise ValueError(f"{name}: expected a contiguous {dtype} device tensor")
+    return t.data_ptr()
+
+
+def gipuma_tiles(n: int) -> int:
+    t = _lib.load().cds_gipuma_tiles(int(n))
+    check(min(t, 0), "cds_gipuma_tiles")
+    return t
+
+
+def gipuma_scan(emit: Tensor) -> Tuple[Tensor, Tensor]:
+    """emit (uint8, tiles x 4096 flags) -> (tile_off [tiles] exclusive offsets of the set flags, total [1]), both int32 on the
+    device; nothing is read back."""
+    tiles = emit.numel() // 4096
+    if emit.numel() != tiles * 4096 or tiles < 1:
+        raise ValueError("gipuma_scan: emit must hold whole 4096-flag tiles")
+    _dev_int(emit, torch.uint8, "emit")
+    count = torch.empty(tiles, dtype=torch.int32, device=emit.device)
+    off = torch.empty(tiles, dtype=torch.int32, device=emit.device)
+    total = torch.empty(1, dtype=torch.int32, device=emit.device)
+    check(_lib.load().cds_gipuma_scan(emit.data_ptr(), tiles, count.data_ptr(), off.data_ptr(), total.data_ptr(),
+                                      _stream(emit)), "cds_gipuma_scan")
+    return off, total
+
+
+def gipuma_compact(emit: Tensor, records: Tensor, tile_off: Tensor, n_points: int) -> Tuple[Tensor, Tensor, Tensor]:
+    """The n_points emitted points in order (r, y, x): -> points [n,3] fp32, colours [n] int32 (packed), ref_view [n] int32."""
+    V, h, w, _ = records.shape
+    dev = records.device
+    points = torch.empty((n_points, 3), dtype=torch.float32, device=dev)
+    colors = torch.empty(n_points, dtype=torch.int32, device=dev)
+    ref = torch.empty(n_points, dtype=torch.int32, device=dev)
+    if n_points > 0:
+        check(_lib.load().cds_gipuma_compact_f32(_dev_int(emit, torch.uint8, "emit"), _dev_int(records, torch.int32, "records"),
+                                                 _dev_int(tile_off, torch.int32, "tile_off"), tile_off.numel(), h * w,
+                                                 points.data_ptr(), colors.data_ptr(), ref.data_ptr(), _stream(records)),
+              "cds_gipuma_compact_f32")
+    return points, colors, ref

@@ -111,16 +111,18 @@ def make_hypotheses(D: int, h: int, w: int, lo: float = 425.0, hi: float = 902.5
     return (planes + jitter * torch.rand(1, D, h, w, generator=g)).contiguous()
 
 
-def make_fusion_scene(n_views: int, h: int, w: int, seed: int = 0, outlier_frac: float = 0.15) -> Dict[str, Tensor]:
+def make_fusion_scene(n_views: int, h: int, w: int, seed: int = 0, outlier_frac: float = 0.15,
+                      pixel_offset: float = 0.5) -> Dict[str, Tensor]:
     """Geometrically consistent depth maps for the filtering / fusion step: every camera of ``make_cameras`` looks at
     the height field Z = 650 + 40 sin(X/60) cos(Y/50) (world = reference-camera frame); per-view depth = camera-frame z of
-    the ray/surface intersection (fixed-point iteration in float64).  A fraction of the pixels gets a ±(2..6)% depth
+    the ray/surface intersection (fixed-point iteration in float64) through image point (x + pixel_offset, y + pixel_offset)
+    of pixel (x, y) (0.0: gipuma's convention, integer pixel coordinates).  A fraction of the pixels gets a ±(2..6)% depth
     error so that the geometric masks are mixed; confidences are uniform in [0,1).
     -> depths [N,h,w], confs [N,3,h,w], cams [N,2,4,4] (intrinsic [3,3] = 1), imgs [N,h,w,3]."""
     cams = make_cameras(n_views, h, w, refine=False, seed=seed)["stage3"][0].clone()
     cams[:, 1, 3, 3] = 1.0
     rs = np.random.RandomState(seed + 77)
-    ys, xs = np.meshgrid(np.arange(h) + 0.5, np.arange(w) + 0.5, indexing="ij")
+    ys, xs = np.meshgrid(np.arange(h) + pixel_offset, np.arange(w) + pixel_offset, indexing="ij")
     pix = np.stack([xs, ys, np.ones_like(xs)], 0).reshape(3, -1)
     depths = []
     for i in range(n_views):

@@ -742,6 +742,32 @@ int cds_thin_round_f32(const float* pts, const int* cell_start, long long n, con
                        int log2_slots, const float* frame_host, float min_dist, unsigned char* state, int* undecided,
                        void* stream);
 
+/*
+ * Gipuma-style depth-map fusion (the reference's --filter_method gipuma, gipuma.py:153-195, which runs the external fusibile;
+ * cds_mvsnet_amd/gipuma.py).  The rule, its fp32 operation order and the points where it fixes behaviour fusibile leaves open
+ * are in the header comment of csrc/gipuma.hip.  Views share one h x w; V h w < 2^31.
+ *   depths [V][h][w], confs [V][3][h][w] fp32, rgb8 [V][h][w][3] uint8 (device); prob_thresh_host 3 floats (HOST)
+ *   views [V][24]: per view P (3x4 row-major, float32 of K E[:3] in float64), Minv = inverse(P[:, :3]) (3x3), 3 unused
+ *   fb [V][V]: fb[r][j] = K_r[0][0] |c_r - c_j|, c_v = -Minv_v P_v[:, 3]
+ *   used [V][h][w] uint8 (0 on entry to the first view); emit [tiles * 4096] uint8, zeroed, 16-byte aligned;
+ *   records [V][h][w][4] words (16-byte aligned): x y z bits and packed colour of every emitted pixel
+ * cds_gipuma_tiles            size query: compaction tiles (4096 flags each) for n = V h w flags, or CDS_EINVAL
+ * cds_gipuma_prob_filter_f32  depth_out = the probability-filtered depths D'; rgb_out [V][h][w] = r | g << 8 | b << 16
+ * cds_gipuma_fuse_view_f32    reference view r: emit / records of its pixels, used marks of the other views.  Call for
+ *                             r = 0 .. V-1 in order on one stream (the views depend on each other through `used`)
+ * cds_gipuma_scan             tile_count [tiles], tile_off [tiles] (exclusive offsets of the emitted points), *total (device)
+ * cds_gipuma_compact_f32      the emitted points in order r, y, x: points [total][3], colors [total] packed, ref_view [total]
+ */
+int cds_gipuma_tiles(long long n);
+int cds_gipuma_prob_filter_f32(const float* depths, const float* confs, const unsigned char* rgb8, int V, int h, int w,
+                               const float* prob_thresh_host, float* depth_out, unsigned* rgb_out, void* stream);
+int cds_gipuma_fuse_view_f32(const float* depths, const unsigned* rgb, const float* views, const float* fb, int r, int V, int h,
+                             int w, float depth_min, float depth_max, float disp_thresh, int num_consistent, unsigned char* used,
+                             unsigned char* emit, unsigned* records, void* stream);
+int cds_gipuma_scan(const unsigned char* emit, int tiles, int* tile_count, int* tile_off, int* total, void* stream);
+int cds_gipuma_compact_f32(const unsigned char* emit, const unsigned* records, const int* tile_off, int tiles, int hw,
+                           float* points, unsigned* colors, int* ref_view, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

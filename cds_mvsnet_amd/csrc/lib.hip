@@ -6,7 +6,7 @@ extern "C" int cds_version(void) { return 100; /* 0.1.0 */ }
 // workgroup on that CU left there: reproducible as long as the same kernels run in the same order on one stream, different as soon as
 // another stream's kernels share the CUs.  With CDS_DEBUG_POISON_LDS=<hex pattern> in the environment every entry point of the library
 // synchronises and poisons the LDS after its launch (cds_launch_status), so the NEXT kernel starts on poisoned LDS whatever ran before;
-// tests/test_hip_parity.py::test_results_do_not_depend_on_stale_lds runs the stages under two patterns and compares bit for bit.
+// tests/test_k3_depth_march_gpu.py::test_results_do_not_depend_on_stale_lds runs K1 / K3 over several chunks under two patterns and compares bit for bit.
 namespace {
 __global__ __launch_bounds__(1024) void poison_lds_kernel(unsigned pattern, int words) {
   extern __shared__ unsigned lds_words[];

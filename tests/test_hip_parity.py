@@ -439,9 +439,13 @@ def _random_stage(ops, dev, V, C, D, h, w, seed, sharp=True):
 
 @pytest.mark.parametrize("V,C,D,h,w", [(1, 8, 7, 9, 70), (4, 8, 33, 12, 130), (6, 8, 5, 16, 24), (3, 16, 9, 10, 50),
                                        (2, 32, 4, 8, 66), (4, 8, 2, 5, 3),
-                                       # C = 8 with 2 / 3 views: the LDS kernels are specialised per view count; D = 70
-                                       # spans three chunks (32 + 32 + 6) and an odd plane pair at the end
-                                       (2, 8, 70, 11, 67), (3, 8, 35, 6, 129),
+                                       # C = 8 with 2 / 3 views: the LDS kernels are specialised per view count; D = 70 is two
+                                       # 48-plane chunks (48 + 22) of K3 in two depth segments - one chunk per workgroup - and 64 + 6
+                                       # of K1.  D = 150 (48 + 48 + 48 + 6 in four segments; K1: 64 + 64 + 22 in one workgroup) and
+                                       # D = 99 (48 + 48 + 3, an odd last plane pair; K1: 64 + 35) restore the "three chunks and an odd
+                                       # pair" this case was written for when chunks had 32 planes; a K3 workgroup that marches
+                                       # over several chunks is the subject of tests/test_k3_depth_march_gpu.py
+                                       (2, 8, 70, 11, 67), (3, 8, 35, 6, 129), (2, 8, 150, 11, 67), (3, 8, 99, 6, 129),
                                        # 5 - 7 views (BASELINE config 4: N = 7): two launches, the second accumulating onto the first
                                        (5, 8, 50, 20, 90), (6, 32, 10, 16, 40), (6, 16, 49, 24, 72), (7, 8, 12, 12, 70)])
 @pytest.mark.parametrize("exact", POSITION_MODES)

@@ -32,14 +32,22 @@ __device__ __attribute__((aligned(32))) float g_zmg_zeros[8];   // what an out-o
 // second wave's K-loop covers the first one's exchange / epilogue / barrier time.
 // F16_: split-f16 arithmetic (two fp16 terms per operand, three products per K-step, tensor scales from device bounds: sbf_common.hpp)
 // instead of split-bf16 (three bf16 terms, six products); same staging geometry, term 2 of a position / weight vector unused.
-template <int S_, int RD_, int MB_, bool PAIR_, int TXO_, int TYO_, int G_, int NG_, int CW_ = 4, bool F16_ = false>
+// RPW_: 8-channel rounds a consumer wave keeps (the K dimension is split over RD / RPW waves; the deep layers' Cin = 32 / 64 would
+// otherwise need more consumer waves than a workgroup has).  YS_: the cout blocks are split over gridDim.y (every one of the YS
+// workgroups of a column stages the whole input ring and computes MB / YS cout blocks: Cout = 64).  PF_: K-steps the LDS operand
+// reads run ahead of their MFMAs (2: a wave with ONE N-tile per step has only three MFMAs to cover an LDS round trip).
+template <int S_, int RD_, int MB_, bool PAIR_, int TXO_, int TYO_, int G_, int NG_, int CW_ = 4, bool F16_ = false, int RPW_ = 1,
+          int YS_ = 1, int PF_ = 1>
 struct ZG {
   static constexpr int S = S_, RD = RD_, MB = MB_, TXO = TXO_, TYO = TYO_, G = G_, NG = NG_;
   static constexpr bool F16 = F16_;
   static constexpr int NT = F16_ ? 2 : 3;                          // terms per operand
   static constexpr bool PAIR = PAIR_, DEINT = PAIR_ || S_ == 2;
   static constexpr int CW = CW_, PW = 4, THREADS = (CW + PW) * 64;
-  static constexpr int KSPL = RD, MBS = MB;                       // wave = (round, cout block, row part)
+  static constexpr int RPW = RPW_, YS = YS_, PF = PF_;
+  static_assert(PF == 1 || (PF == 2 && 2 * NG_ * (F16_ ? 2 : 3) <= 15), "operand prefetch distance (lgkmcnt is a 4-bit count)");
+  static_assert(RD % RPW == 0 && MB % YS == 0, "rounds per wave / cout split");
+  static constexpr int KSPL = RD / RPW, MBS = MB / YS;            // wave = (RPW rounds, cout block, row part)
   static_assert(CW % (KSPL * MBS) == 0 && (KSPL == 1 || KSPL == 2 || KSPL == 4), "consumer waves");
   static constexpr int PARTS = CW / (KSPL * MBS);
   static constexpr int ROWS = TYO / PARTS;                        // output rows per consumer wave
@@ -213,21 +221,23 @@ __global__ __launch_bounds__(Cfg::THREADS, 1) void conv3d_zmg_kernel(const float
 #endif
   // byte offset of this lane inside a slice: its slice (round k), first row of its part, voxel j; PAIR: + the x' of its lane group
   // (x' = 0, 2, 1, 3: de-interleaved parity plane + half index), the (kz, ky) of a K-step being uniform
-  const int lane_base = k * Cfg::SLICEB + (part * Cfg::ROWS * S * Cfg::IXP + j) * POSB +
+  const int lane_base = k * Cfg::RPW * Cfg::SLICEB + (part * Cfg::ROWS * S * Cfg::IXP + j) * POSB +
                         (PAIR ? (((g & 1) * 2 + (g >> 1)) & 1) * Cfg::IXH * POSB + ((((g & 1) * 2 + (g >> 1))) >> 1) * POSB : 0);
-  // this wave's weights: [round k][K-step][cout block mbi][term][lane]
-  BV wres[KS][NT];
+  // this wave's weights: [round k RPW + rr][K-step][cout block][term][lane]
+  constexpr int RPW = Cfg::RPW;
+  const int mbg = (Cfg::YS > 1 ? blockIdx.y * Cfg::MBS : 0) + mbi;   // cout block in the layer
+  BV wres[RPW * KS][NT];
   {
     const uint4* __restrict__ wl = wsp + lane;
 #pragma unroll
-    for (int t = 0; t < KS; ++t) {
-      const size_t o = (size_t)(((k * KS + t) * Cfg::MB + mbi) * 3) * 64;
+    for (int t = 0; t < RPW * KS; ++t) {
+      const size_t o = (size_t)(((k * RPW * KS + t) * Cfg::MB + mbg) * 3) * 64;
 #pragma unroll
       for (int tm = 0; tm < NT; ++tm) wres[t][tm].u = wl[o + 64 * tm];
     }
   }
   float amax = 0.f;                                    // running maximum of the magnitudes this lane stores (split-f16: the output's bound)
-  const int co = PAIR ? 4 * (g & 1) : mbi * 16 + 4 * g;
+  const int co = PAIR ? 4 * (g & 1) : mbg * 16 + 4 * g;
   const float4 bv = (bias && co < Cout) ? *reinterpret_cast<const float4*>(bias + co) : make_float4(0.f, 0.f, 0.f, 0.f);
   // N-tile n of this wave = (row r, x run xt, plane i): n = (r XT + xt) G + i
   constexpr int XW = PAIR ? 32 : 16;
@@ -252,6 +262,9 @@ __global__ __launch_bounds__(Cfg::THREADS, 1) void conv3d_zmg_kernel(const float
   unsigned char* xch = lds + Cfg::RINGB;                 // [buffer][sender wave][N-tile of its partner's half][lane] x 16 B
   constexpr int NH = NTW / 2;
   f32x4 acc[NTW];
+  // K split in four with two rounds of weights per wave (112 registers): the finalising wave's own partial sum goes through the
+  // exchange buffer too instead of staying in registers across the next K-loop
+  constexpr bool KEEP4 = Cfg::RPW == 1;
   f32x4 keep[Cfg::KSPL == 2 ? NH : Cfg::NFIN];          // this wave's partial sums of the N-tiles it finalises, across the barrier
   // K split in four: N-tile n known only at run time (n = 4 j + k)
   auto store_tile_rt = [&](int n, int st, const f32x4& a) {
@@ -283,9 +296,9 @@ __global__ __launch_bounds__(Cfg::THREADS, 1) void conv3d_zmg_kernel(const float
         const int n = jf * 4 + k;
         if (n >= NTW) continue;                                      // wave-uniform
         const unsigned char* src = xch + (sp & 1) * Cfg::XCH1 + ((xgrp + n) * 4) * 1024 + lane * 16;
-        f32x4 total = k == 0 ? keep[jf] : *reinterpret_cast<const f32x4*>(src);
+        f32x4 total = KEEP4 && k == 0 ? keep[jf] : *reinterpret_cast<const f32x4*>(src);
 #pragma unroll
-        for (int kk = 1; kk < 4; ++kk) total = total + (kk == k ? keep[jf] : *reinterpret_cast<const f32x4*>(src + kk * 1024));
+        for (int kk = 1; kk < 4; ++kk) total = total + (KEEP4 && kk == k ? keep[jf] : *reinterpret_cast<const f32x4*>(src + kk * 1024));
         store_tile_rt(n, sp, total);
       }
     } else {
@@ -323,22 +336,24 @@ __global__ __launch_bounds__(Cfg::THREADS, 1) void conv3d_zmg_kernel(const float
           }
       }
     }
-    constexpr int NGRP = NTW / NG, NS = KS * NGRP;
-    BV bd[2][NG][NT];
+    constexpr int NGRP = NTW / NG, NS = RPW * KS * NGRP;   // the wave's rounds one after the other into the same accumulators
+    constexpr int PF = Cfg::PF;
+    BV bd[PF + 1][NG][NT];
     auto load_b = [&](int buf, int ss) {
-      const int t = ss / NGRP, grp = ss % NGRP;
+      const int t = (ss / NGRP) % KS, rr = ss / (NGRP * KS), grp = ss % NGRP;
 #pragma unroll
       for (int q = 0; q < NG; ++q) {
         const int n = grp * NG + q, i = n % G, rx = n / G, xt = rx % Cfg::XT, r = rx / Cfg::XT;
         // PAIR: K-step t = (kz, ky) = (t / 3, t % 3)
         const unsigned char* b = lds + (PAIR ? vpl[PAIR ? S * i + t / 3 : 0] + (t % 3) * Cfg::IXP * POSB : vaddr[PAIR ? 0 : t][PAIR ? 0 : i]) +
-                                 (r * S * Cfg::IXP + xt * 16) * POSB;
+                                 (r * S * Cfg::IXP + xt * 16) * POSB + rr * Cfg::SLICEB;
         bd[buf][q][0].u = *reinterpret_cast<const uint4*>(b);
         bd[buf][q][1].u = *reinterpret_cast<const uint4*>(b + 16);
         if (!F16) bd[buf][q][NT - 1].u = *reinterpret_cast<const uint4*>(b + 32);
       }
     };
     load_b(0, 0);
+    if (PF == 2 && NS > 1) load_b(1, 1);
     // a wave that issues MFMAs back to back starves the other waves of its SIMD of issue slots (the producers' deposit went from
     // ~7000 to ~1100 cycles per stage once they outranked the consumers): the K-loop runs at the lowest priority, a consumer's
     // address set-up / exchange / epilogue above it, the producers above both
@@ -347,13 +362,14 @@ __global__ __launch_bounds__(Cfg::THREADS, 1) void conv3d_zmg_kernel(const float
     for (int t = 0; t < NTW; ++t) acc[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int ss = 0; ss < NS; ++ss) {
-      const int t = ss / NGRP, grp = ss % NGRP, db = ss & 1;
-      if (ss + 1 < NS) load_b(db ^ 1, ss + 1);
+      const int t = ss / NGRP, grp = ss % NGRP, db = ss % (PF + 1);   // t = rr KS + K-step
+      if (ss + PF < NS) load_b((ss + PF) % (PF + 1), ss + PF);
       __builtin_amdgcn_sched_barrier(0);
 #ifndef CDS_ZMG_LAZYWAIT
-      // ONE wait for all operands of this step (they were requested a whole step ago) instead of the compiler's lgkmcnt waits
+      // ONE wait for all operands of this step (they were requested PF steps ago) instead of the compiler's lgkmcnt waits
       // BETWEEN the dependent MFMAs: an issue slot between two MFMAs on the same accumulator costs ~40 cycles of matrix pipe
-      if (ss + 1 < NS) __builtin_amdgcn_s_waitcnt(0xC07F | ((NT * NG) << 8));   // lgkmcnt(NT NG): the next step's requests stay in flight
+      if (ss + PF < NS) __builtin_amdgcn_s_waitcnt(0xC07F | ((PF * NT * NG) << 8));   // lgkmcnt(PF NT NG): the next steps' requests stay in flight
+      else if (PF == 2 && ss + 1 < NS) __builtin_amdgcn_s_waitcnt(0xC07F | ((NT * NG) << 8));
       else __builtin_amdgcn_s_waitcnt(0xC07F);
       __builtin_amdgcn_sched_barrier(0);
 #endif
@@ -374,11 +390,11 @@ __global__ __launch_bounds__(Cfg::THREADS, 1) void conv3d_zmg_kernel(const float
         keep[m] = acc[k * NH + m];
       }
     } else if (Cfg::KSPL == 4) {
-      if (st > 0) finish(st - 1);
+      if (!late && st > 0) finish(st - 1);
       unsigned char* dst = xch + (st & 1) * Cfg::XCH1 + (xgrp * 4 + k) * 1024 + lane * 16;
 #pragma unroll
       for (int n = 0; n < NTW; ++n) {
-        if ((n & 3) == k) keep[n >> 2] = acc[n];                     // wave-uniform
+        if (KEEP4 && (n & 3) == k) keep[n >> 2] = acc[n];            // wave-uniform
         else *reinterpret_cast<f32x4*>(dst + n * 4096) = acc[n];
       }
     } else if (!late) {
@@ -409,18 +425,19 @@ inline int zmg_pick_nseg(int cols, int Do, int G) {
 
 template <class Cfg>
 int launch_zmg(const float* x, const void* wsp, const float* b, float* out, int Cout, int D, int H, int W, int act, hipStream_t st,
-               const float* in_bound = nullptr, float w_inv = 1.f, float* out_bound = nullptr) {
+               const float* in_bound = nullptr, float w_inv = 1.f, float* out_bound = nullptr, int min_wgs = 0) {
   constexpr int S = Cfg::S;
   const int Do = (D - 1) / S + 1, Ho = (H - 1) / S + 1, Wo = (W - 1) / S + 1;
   const int tx = cds_ceil_div(Wo, Cfg::TXO), ty = cds_ceil_div(Ho, Cfg::TYO);
-  int nseg = zmg_pick_nseg(tx * ty, Do, Cfg::G);
+  int nseg = zmg_pick_nseg(tx * ty * Cfg::YS, Do, Cfg::G);
   const int zseg = cds_ceil_div(cds_ceil_div(Do, nseg), Cfg::G) * Cfg::G;
   nseg = cds_ceil_div(Do, zseg);
+  if (min_wgs > 0 && tx * ty * nseg * Cfg::YS < min_wgs) return CDS_ZMG_UNSUPPORTED;   // too few columns to fill the chip
   auto kern = conv3d_zmg_kernel<Cfg>;
   static std::atomic<unsigned long long> lds_ok{0};     // per instantiation
   if (int e_lds = cds_allow_lds(reinterpret_cast<const void*>(kern), Cfg::LDSB, lds_ok)) return e_lds;
-  hipLaunchKernelGGL(kern, dim3(tx * ty * nseg), dim3(Cfg::THREADS), Cfg::LDSB, st, x, reinterpret_cast<const uint4*>(wsp), b, out,
-                     Cout, D, H, W, Do, Ho, Wo, act, tx, ty, zseg, in_bound, w_inv, out_bound);
+  hipLaunchKernelGGL(kern, dim3(tx * ty * nseg, Cfg::YS), dim3(Cfg::THREADS), Cfg::LDSB, st, x, reinterpret_cast<const uint4*>(wsp), b,
+                     out, Cout, D, H, W, Do, Ho, Wo, act, tx, ty, zseg, in_bound, w_inv, out_bound);
   return cds_launch_status();
 }
 
@@ -443,6 +460,19 @@ int cds_conv3d_zmg_dispatch(const float* x, const void* wsp, const float* bias, 
       return launch_zmg<ZG<2, 1, 1, false, 16, 8, 1, 1, 8, true>>(x, wsp, bias, out, Cout, D, H, W, act, st, in_bound, w_inv, out_bound);
     if (stride == 2 && Cin == 16 && Cout == 32)
       return launch_zmg<ZG<2, 2, 2, false, 16, 4, 1, 1, 8, true>>(x, wsp, bias, out, Cout, D, H, W, act, st, in_bound, w_inv, out_bound);
+    // The deep stride-1 layers (conv4 32 -> 32, conv6 64 -> 64).  CDS_ZMG_DEEP (A/B knob): 0 = tiled kernels, 1 = z-march where
+    // columns x segments fill the 256 CUs (the few tiles of the cascade stages' deep layers stay on the tiled kernels and their
+    // cout split), 2 = z-march whatever the size.
+    const int deep = cds_env_is("CDS_ZMG", '0') ? 0 : cds_env_int("CDS_ZMG_DEEP", 1);
+    const int min_wgs = deep == 2 ? 0 : 256;
+    // conv4: K split over four waves x two cout blocks, 16 x 4 columns (ring 81 KB + 2 x 32 KB exchange)
+    if (deep > 0 && stride == 1 && Cin == 32 && Cout == 32)
+      return launch_zmg<ZG<1, 4, 2, false, 16, 4, 1, 1, 8, true, 1, 1, 2>>(x, wsp, bias, out, Cout, D, H, W, act, st, in_bound, w_inv, out_bound, min_wgs);
+    // conv6: two rounds of weights per wave (K split over four waves), two cout blocks per workgroup and two workgroups (gridDim.y)
+    // per 16 x 2 column: the input is staged twice from L2 / the memory-side cache, against four times and stages of 42 MFMAs per
+    // wave for a K split over eight waves with one cout block per workgroup (ring 108 KB + 2 x 16 KB exchange)
+    if (deep > 0 && stride == 1 && Cin == 64 && Cout == 64)
+      return launch_zmg<ZG<1, 8, 4, false, 16, 2, 1, 1, 8, true, 2, 2>>(x, wsp, bias, out, Cout, D, H, W, act, st, in_bound, w_inv, out_bound, min_wgs);
     return CDS_ZMG_UNSUPPORTED;
   }
   const bool off = cds_env_is("CDS_ZMG", '0');   // A/B knob: 0 = tiled kernels only

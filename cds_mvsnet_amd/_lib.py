@@ -146,6 +146,11 @@ SIGNATURES = {
     "cds_gipuma_fuse_view_f32": [P, P, P, P, I, I, I, I, F, F, F, I, P, P, P, P],
     "cds_gipuma_scan": [P, I, P, P, P, P],
     "cds_gipuma_compact_f32": [P, P, P, I, I, P, P, P, P],
+    "cds_colmap_score_quantum_log2": [],
+    "cds_colmap_score_limbs": [DB, DB, DB],
+    "cds_colmap_pair_scores_f64": [P, P, P, P, P, P, L, L, I, DB, DB, DB, I, P, P],
+    "cds_colmap_obs_depth_f64": [P, P, P, P, L, P, P],
+    "cds_colmap_depth_ranges_f64": [P, P, P, P, I, P, P],
 }
 
 _lib = None

@@ -1501,3 +1501,121 @@ def gipuma_compact(emit: Tensor, records: Tensor, tile_off: Tensor, n_points: in
                                                  points.data_ptr(), colors.data_ptr(), ref.data_ptr(), _stream(records)),
               "cds_gipuma_compact_f32")
     return points, colors, ref
+
+
+# ---- COLMAP sparse model -> MVSNet scene (csrc/colmap.hip; cds_mvsnet_amd/colmap.py drives these) ----
+COLMAP_SCORE_QUANTUM = 2.0 ** -80            # q: bound of a term's error in the multi-limb fixed-point sums (cds_colmap_score_quantum_log2)
+COLMAP_SCORE_MAX_LIMBS = 28                  # int64 limbs of 40 bits per score (limb k in units of 2^-40(k+1)): see colmap_score_limbs
+COLMAP_MAX_TERMS_PER_PAIR = 1 << 22          # a limb takes < 2^40 per term: int64 holds 2^23 of them; half of that is accepted
+
+
+def _colmap_index_range(obs_img: Tensor, N: int, obs_pt: Tensor, P: int, what: str) -> None:
+    # the kernels index xyz, centres and the score matrix with these: nothing outside [0, N) x [0, P) reaches them
+    lo_i, hi_i, lo_p, hi_p = (int(v.item()) for v in (obs_img.min(), obs_img.max(), obs_pt.min(), obs_pt.max()))
+    if lo_i < 0 or hi_i >= N or lo_p < 0 or hi_p >= P:
+        raise ValueError(f"{what}: image indices [{lo_i}, {hi_i}] / point indices [{lo_p}, {hi_p}] outside [0, {N}) / [0, {P})")
+
+
+def colmap_score_limbs(theta0: float, sigma1: float, sigma2: float) -> int:
+    """The limbs a score needs so that the smallest weight these parameters can produce (theta = 0 or 180 degrees) still enters
+    with its two leading limbs: 7 at the defaults (w >= e^-153 = 2^-221), at most 28 (every nonzero double)."""
+    n = _lib.load().cds_colmap_score_limbs(float(theta0), float(sigma1), float(sigma2))
+    check(min(n, 0), "cds_colmap_score_limbs")
+    return n
+
+
+def colmap_point_csr(obs_img: Tensor, obs_pt: Tensor, N: int, P: int) -> Tuple[Tensor, Tensor, Tensor, Tensor, int]:
+    """The kernel's view of the observations (torch sort / unique / prefix sums): (pair_off [P+1], ptr [P+1] int64, img [U],
+    cnt [U] int32, T) with the U unique (point, image) pairs sorted by point, then image; T = pair_off[P] is read back."""
+    keys, cnt = torch.unique(obs_pt * N + obs_img.long(), sorted=True, return_counts=True)
+    pt = torch.div(keys, N, rounding_mode="floor")
+    img = (keys - pt * N).to(torch.int32).contiguous()
+    L = torch.bincount(pt, minlength=P)
+    zero = torch.zeros(1, dtype=torch.int64, device=obs_pt.device)
+    ptr = torch.cat([zero, torch.cumsum(L, 0)]).contiguous()
+    pair_off = torch.cat([zero, torch.cumsum(L * (L - 1) // 2, 0)]).contiguous()
+    return pair_off, ptr, img, cnt.to(torch.int32).contiguous(), int(pair_off[-1].item())
+
+
+def colmap_pair_scores_csr(pair_off: Tensor, ptr: Tensor, img: Tensor, cnt: Tensor, T: int, xyz: Tensor, centres: Tensor,
+                           theta0: float, sigma1: float, sigma2: float) -> Tensor:
+    """cds_colmap_pair_scores_f64 on the CSR of :func:`colmap_point_csr` (which guarantees the index ranges the kernel relies
+    on) -> acc [colmap_score_limbs(...),N,N] int64, upper triangles: limb k in units of 2^-40(k+1)."""
+    P, N = xyz.shape[0], centres.shape[0]
+    if pair_off.numel() != P + 1 or ptr.numel() != P + 1 or img.numel() != cnt.numel():
+        raise ValueError("colmap_pair_scores_csr: the CSR does not match xyz")
+    _dev_int(pair_off, torch.int64, "pair_off"), _dev_int(ptr, torch.int64, "ptr")
+    _dev_int(img, torch.int32, "img"), _dev_int(cnt, torch.int32, "cnt")
+    limbs = colmap_score_limbs(theta0, sigma1, sigma2)
+    acc = torch.zeros((limbs, N, N), dtype=torch.int64, device=xyz.device)
+    check(_lib.load().cds_colmap_pair_scores_f64(pair_off.data_ptr(), ptr.data_ptr(), img.data_ptr(), cnt.data_ptr(),
+                                                 _dev64(xyz, "xyz"), _dev64(centres, "centres"), P, int(T), N, float(theta0),
+                                                 float(sigma1), float(sigma2), limbs, acc.data_ptr(), _stream(xyz)),
+          "cds_colmap_pair_scores_f64")
+    return acc
+
+
+def colmap_scores_from_limbs(acc: Tensor) -> Tensor:
+    """acc [limbs,N,N] int64 -> S [N,N] float64, symmetric: the limbs summed from the smallest up."""
+    S = torch.zeros(acc.shape[1:], dtype=torch.float64, device=acc.device)
+    for k in range(acc.shape[0] - 1, -1, -1):
+        S = S + acc[k].to(torch.float64) * 2.0 ** (-40 * (k + 1))
+    return S + S.t()
+
+
+def colmap_pair_scores(obs_img: Tensor, obs_pt: Tensor, xyz: Tensor, centres: Tensor, theta0: float, sigma1: float,
+                       sigma2: float) -> Tuple[Tensor, Tensor]:
+    """View-selection scores of the reference's ``calc_score`` for all image pairs at once.  obs_img [E] (int32, image index
+    0..N-1) and obs_pt [E] (int64, point index 0..P-1): the valid observations in any order, duplicates included; xyz [P,3],
+    centres [N,3] float64, all on the device.  -> (S [N,N] float64, symmetric, zero diagonal; acc [limbs,N,N]
+    int64, the exact limbs of its upper triangle).  The sort / unique / prefix sums that build the point CSR run in torch; the
+    arithmetic is cds_colmap_pair_scores_f64.  The integer accumulation makes the result bit-identical from run to run.
+    One host read-back (the number of terms)."""
+    E, (P, N) = obs_img.numel(), (xyz.shape[0], centres.shape[0])
+    if tuple(xyz.shape) != (P, 3) or tuple(centres.shape) != (N, 3) or obs_pt.numel() != E or E < 1 or P < 1 or N < 1:
+        raise ValueError(f"colmap_pair_scores: obs_img {tuple(obs_img.shape)}, obs_pt {tuple(obs_pt.shape)}, xyz "
+                         f"{tuple(xyz.shape)} and centres {tuple(centres.shape)} do not fit together")
+    _dev_int(obs_img, torch.int32, "obs_img"), _dev_int(obs_pt, torch.int64, "obs_pt")
+    _dev64(xyz, "xyz"), _dev64(centres, "centres")
+    if not (sigma1 > 0 and sigma2 > 0):
+        raise ValueError("colmap_pair_scores: sigma1 and sigma2 must be positive")
+    _colmap_index_range(obs_img, N, obs_pt, P, "colmap_pair_scores")
+    per_image = torch.bincount(obs_img.long(), minlength=N)
+    if int(per_image.max().item()) >= COLMAP_MAX_TERMS_PER_PAIR:
+        raise ValueError(f"colmap_pair_scores: an image has {int(per_image.max().item())} valid observations; a pair's "
+                         f"fixed-point sum (40-bit limbs in int64) is only guaranteed below {COLMAP_MAX_TERMS_PER_PAIR}")
+    csr = colmap_point_csr(obs_img, obs_pt, N, P)
+    acc = colmap_pair_scores_csr(*csr, xyz, centres, theta0, sigma1, sigma2)
+    return colmap_scores_from_limbs(acc), acc
+
+
+def colmap_depth_ranges(obs_img: Tensor, obs_pt: Tensor, xyz: Tensor, zrow: Tensor, num_min: Tensor,
+                        num_max: Tensor) -> Tensor:
+    """Per image the reference's relaxed depth range: z of every valid observation (cds_colmap_obs_depth_f64), sorted ascending
+    inside each image (torch), then the mean of the lowest num_min[i] and of the highest num_max[i] values, each clipped at the
+    image's count and summed in ascending order (cds_colmap_depth_ranges_f64).  obs_img [E] int32 / obs_pt [E] int64 as in
+    :func:`colmap_pair_scores`; zrow [N,4] float64 = row 2 of [R | t]; num_min, num_max [N] int32 >= 1.  Every image needs at
+    least one observation.  -> [N,2] float64 (depth_min, depth_max)."""
+    E, N = obs_img.numel(), zrow.shape[0]
+    if tuple(zrow.shape) != (N, 4) or xyz.dim() != 2 or xyz.shape[1] != 3 or obs_pt.numel() != E or E < 1 or \
+            num_min.numel() != N or num_max.numel() != N:
+        raise ValueError("colmap_depth_ranges: inconsistent shapes")
+    _dev_int(obs_img, torch.int32, "obs_img"), _dev_int(obs_pt, torch.int64, "obs_pt")
+    _dev_int(num_min, torch.int32, "num_min"), _dev_int(num_max, torch.int32, "num_max")
+    _dev64(xyz, "xyz"), _dev64(zrow, "zrow")
+    _colmap_index_range(obs_img, N, obs_pt, xyz.shape[0], "colmap_depth_ranges")
+    counts = torch.bincount(obs_img.long(), minlength=N)
+    if int(counts.min().item()) < 1 or int(torch.minimum(num_min, num_max).min().item()) < 1:
+        raise ValueError("colmap_depth_ranges: every image needs an observation and num_min, num_max >= 1")
+    dev = xyz.device
+    lib = _lib.load()
+    z = torch.empty(E, dtype=torch.float64, device=dev)
+    check(lib.cds_colmap_obs_depth_f64(obs_img.data_ptr(), obs_pt.data_ptr(), xyz.data_ptr(), zrow.data_ptr(), E, z.data_ptr(),
+                                       _stream(xyz)), "cds_colmap_obs_depth_f64")
+    zs, order = torch.sort(z, stable=True)
+    zs = zs[torch.sort(obs_img[order].long(), stable=True)[1]].contiguous()      # ascending z inside ascending image
+    obs_ptr = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), torch.cumsum(counts, 0)]).contiguous()
+    out = torch.empty((N, 2), dtype=torch.float64, device=dev)
+    check(lib.cds_colmap_depth_ranges_f64(zs.data_ptr(), obs_ptr.data_ptr(), num_min.data_ptr(), num_max.data_ptr(), N,
+                                          out.data_ptr(), _stream(xyz)), "cds_colmap_depth_ranges_f64")
+    return out

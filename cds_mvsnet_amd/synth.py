@@ -194,3 +194,128 @@ def make_dtu_scene(half_x: float, half_y: float, spacing: float, res: float, mar
             pred[idx] += rs.uniform(-outlier_range, outlier_range, (n_out, 3))
         out["pred"] = pred.astype(np.float32)
     return out
+
+
+def _min_track_angle(centres: np.ndarray, xyz: np.ndarray, pt: np.ndarray, img: np.ndarray) -> float:
+    """Smallest angle (degrees) at a point between two camera centres that both observe it, over all tracks."""
+    N, P = len(centres), len(xyz)
+    key = np.unique(pt.astype(np.int64) * N + img)
+    p, i = key // N, key % N
+    L = np.bincount(p, minlength=P)
+    start = np.concatenate([[0], np.cumsum(L)])
+    best = 180.0
+    for length in np.unique(L[L >= 2]):
+        pts = np.nonzero(L == length)[0]
+        a, b = np.triu_indices(int(length), 1)
+        chunk = max(1, 1_000_000 // len(a))
+        for c in range(0, len(pts), chunk):
+            q = pts[c:c + chunk]
+            im = i[start[q][:, None] + np.arange(length)]
+            u = centres[im[:, a]] - xyz[q][:, None, :]
+            v = centres[im[:, b]] - xyz[q][:, None, :]
+            cos = (u * v).sum(-1) / np.linalg.norm(u, axis=-1) / np.linalg.norm(v, axis=-1)
+            best = min(best, float(np.degrees(np.arccos(np.clip(cos, -1.0, 1.0))).min()))
+    return best
+
+
+def make_colmap_model(n_images: int, n_points: int, seed: int = 0, mean_track: float = 6.0, long_frac: float = 0.01,
+                      n_isolated: int = 2, invalid_frac: float = 0.02, dup_frac: float = 0.0, min_angle_deg=0.1,
+                      width: int = 96, height: int = 64, ext: str = ".jpg", decimals=None):
+    """A COLMAP sparse model (cameras, images, Points3D of ``cds_mvsnet_amd.colmap``) for the converter's tests and timings:
+    ``n_images`` cameras on an arc of radius 20 (with some height jitter) look at a slab of ``n_points`` points around the origin.
+
+    * Visibility: every point is seen by a window of consecutive cameras.  Its length is 2 + Poisson for most points and
+      uniform in [2, n_images] for a fraction ``long_frac`` (so track lengths range from 2 to all images), with a mean near
+      ``mean_track``.  The last ``n_isolated`` cameras of the arc are almost isolated: they see three points each.
+    * COLMAP image ids and point ids are ascending with gaps; the ``images`` dict is filled in a shuffled order.
+    * ``invalid_frac`` of every image's observations (at least two) carry point id -1; ``dup_frac`` of the valid observations
+      are repeated in the same image (same point id, not in the track).
+    * Two cameras, PINHOLE (id 1) and SIMPLE_RADIAL (id 3), alternate over the images.
+    * ``decimals``: round the point coordinates to this many decimals (shorter text models for fixtures).
+    * ``min_angle_deg``: asserts that every pair of cameras sharing a point subtends at least this angle at it (None skips
+      the check, which visits every term of the pair score)."""
+    from .colmap import Camera, Image, Points3D
+    rs = np.random.RandomState(seed)
+    N, P = int(n_images), int(n_points)
+    n_iso = min(int(n_isolated), max(0, N - 2))
+    M = N - n_iso                                           # cameras that take part in the windows
+    # ---- cameras ----
+    span = np.radians(min(300.0, max(90.0, 0.5 * N)))
+    phi = np.linspace(-span / 2, span / 2, N) + rs.uniform(-0.2, 0.2, N) * span / max(N - 1, 1)
+    centres = np.stack([20.0 * np.sin(phi), rs.uniform(-1.5, 1.5, N), -20.0 * np.cos(phi)], 1)
+    qvecs, tvecs = np.zeros((N, 4)), np.zeros((N, 3))
+    rots = np.zeros((N, 3, 3))
+    for i in range(N):
+        z = -centres[i] / np.linalg.norm(centres[i])
+        x = np.cross([0.0, 1.0, 0.0], z)
+        x /= np.linalg.norm(x)
+        R = np.stack([x, np.cross(z, x), z])                # rows: camera axes in the world
+        tr = np.trace(R)                                    # > -1 here: the cameras stay near upright
+        w = 0.5 * math.sqrt(max(1e-12, 1.0 + tr))
+        q = np.array([w, (R[2, 1] - R[1, 2]) / (4 * w), (R[0, 2] - R[2, 0]) / (4 * w), (R[1, 0] - R[0, 1]) / (4 * w)])
+        qvecs[i] = q / np.linalg.norm(q)
+        from .colmap import rotation_matrix
+        rots[i] = rotation_matrix(qvecs[i])
+        tvecs[i] = -rots[i] @ centres[i]
+    centres = -np.einsum("nji,nj->ni", rots, tvecs)         # the centres the poses really have
+    f = 0.9 * width
+    cameras = {1: Camera(1, "PINHOLE", width, height, np.array([f, f * 1.01, width / 2.0, height / 2.0])),
+               3: Camera(3, "SIMPLE_RADIAL", width, height, np.array([f * 0.98, width / 2.0 + 0.5, height / 2.0 - 0.5, 0.01]))}
+    cam_of = np.where(np.arange(N) % 2 == 0, 1, 3)
+    image_ids = np.cumsum(rs.randint(1, 4, N)) + 2
+    # ---- points and tracks ----
+    xyz = rs.uniform(-1.0, 1.0, (P, 3)) * np.array([4.0, 2.0, 0.5])
+    if decimals is not None:
+        xyz = np.round(xyz, decimals)
+    point_ids = np.cumsum(rs.randint(1, 4, P)).astype(np.int64) + 10
+    lam = max(0.5, mean_track - 2.0 - long_frac * M / 2.0)
+    L = 2 + rs.poisson(lam, P)
+    long_ = rs.rand(P) < long_frac
+    L[long_] = rs.randint(2, M + 1, int(long_.sum()))
+    if P:
+        L[rs.randint(P)] = M                                # at least one track through every camera of the arc
+    L = np.minimum(L, M)
+    first = (rs.rand(P) * (M - L + 1)).astype(np.int64)
+    pt = np.repeat(np.arange(P), L)
+    img = np.repeat(first - np.concatenate([[0], np.cumsum(L)[:-1]]), L) + np.arange(L.sum())
+    if n_iso:
+        pt = np.concatenate([pt, rs.randint(0, P, 3 * n_iso)])
+        img = np.concatenate([img, np.repeat(np.arange(M, N), 3)])
+        key = np.unique(pt.astype(np.int64) * N + img)
+        pt, img = key // N, key % N
+    if min_angle_deg is not None:
+        got = _min_track_angle(centres, xyz, pt, img)
+        assert got >= min_angle_deg, f"make_colmap_model: smallest triangulation angle {got} < {min_angle_deg} degrees"
+    # ---- observations: tracked, duplicated, invalid; shuffled inside every image ----
+    E0 = pt.size
+    dup = rs.choice(E0, int(dup_frac * E0), replace=False) if dup_frac > 0 else np.zeros(0, np.int64)
+    n_inv = np.maximum(2, (invalid_frac * np.bincount(img, minlength=N)).astype(np.int64)) if invalid_frac > 0 else \
+        np.zeros(N, np.int64)
+    o_pt = np.concatenate([pt, pt[dup], np.full(int(n_inv.sum()), -1)])
+    o_img = np.concatenate([img, img[dup], np.repeat(np.arange(N), n_inv)])
+    tracked = np.concatenate([np.ones(E0, bool), np.zeros(o_pt.size - E0, bool)])
+    perm = rs.permutation(o_pt.size)
+    perm = perm[np.argsort(o_img[perm], kind="stable")]
+    o_pt, o_img, tracked = o_pt[perm], o_img[perm], tracked[perm]
+    iptr = np.concatenate([[0], np.cumsum(np.bincount(o_img, minlength=N))])
+    idx2d = np.arange(o_pt.size) - iptr[o_img]
+    X = xyz[np.maximum(o_pt, 0)]
+    cam = np.einsum("eij,ej->ei", rots[o_img], X) + tvecs[o_img]
+    K = np.stack([np.array([[c.params[0], c.params[1 if c.model == "PINHOLE" else 0]],
+                            [c.params[2 if c.model == "PINHOLE" else 1], c.params[3 if c.model == "PINHOLE" else 2]]])
+                  for c in (cameras[k] for k in cam_of)])               # [N, (f, c), (x, y)]
+    xy = K[o_img, 0] * cam[:, :2] / cam[:, 2:3] + K[o_img, 1] + rs.normal(0, 0.3, (o_pt.size, 2))
+    xy[o_pt < 0] = rs.uniform(0, 1, (int((o_pt < 0).sum()), 2)) * np.array([width, height])
+    xy = np.round(xy, 2 if decimals is None else min(2, decimals))
+    images = {}
+    for i in rs.permutation(N):
+        s, e = iptr[i], iptr[i + 1]
+        ids = np.where(o_pt[s:e] >= 0, point_ids[np.maximum(o_pt[s:e], 0)], -1).astype(np.int64)
+        images[int(image_ids[i])] = Image(int(image_ids[i]), qvecs[i].copy(), tvecs[i].copy(), int(cam_of[i]),
+                                          "img_%04d%s" % (i, ext), xy[s:e].copy(), ids)
+    t = np.nonzero(tracked)[0]
+    t = t[np.argsort(o_pt[t], kind="stable")]
+    tptr = np.concatenate([[0], np.cumsum(np.bincount(o_pt[t], minlength=P))])
+    points = Points3D(point_ids, xyz, rs.randint(0, 256, (P, 3)), np.round(rs.uniform(0.1, 2.0, P), 3), tptr,
+                      image_ids[o_img[t]], idx2d[t])
+    return cameras, images, points

@@ -768,6 +768,38 @@ int cds_gipuma_scan(const unsigned char* emit, int tiles, int* tile_count, int* 
 int cds_gipuma_compact_f32(const unsigned char* emit, const unsigned* records, const int* tile_off, int tiles, int hw,
                            float* points, unsigned* colors, int* ref_view, void* stream);
 
+/*
+ * COLMAP sparse model -> MVSNet scene (the reference's colmap2mvsnet.py; cds_mvsnet_amd/colmap.py).  float64 throughout;
+ * the rule and the operation order are in the header comment of csrc/colmap.hip.  All pointers are device memory.
+ *   Images are numbered 0 .. N-1 and points 0 .. P-1 by the caller.
+ *   ptr [P+1], img [ptr[P]], cnt [ptr[P]]: CSR over points of the (point, image) observations, sorted and unique, the images
+ *   of a point ascending, cnt = how often that image observes that point;  pair_off [P+1]: exclusive prefix sum of
+ *   L_p (L_p - 1) / 2 with L_p = ptr[p+1] - ptr[p], T = pair_off[P];  xyz [P][3];  centres [N][3] = -R^T t
+ *   acc [limbs][N][N] int64, 2 <= limbs <= CDS_COLMAP_SCORE_MAX_LIMBS, zeroed by the caller: only entries i < j are written; limb k is in units of
+ *   2^-40(k+1), and S[i][j] = sum_k acc[k][i][j] 2^-40(k+1).  The caller guarantees that no pair can reach 2^23 cnt-weighted terms.
+ * cds_colmap_score_limbs        the limbs that keep the two leading limbs of the smallest weight the rule can produce for
+ *                                these parameters (7 at theta0 5, sigma 1 / 10; at most 28, which covers every nonzero double)
+ * cds_colmap_score_quantum_log2  80: every term enters with an absolute error below q = 2^-80 per occurrence
+ * cds_colmap_pair_scores_f64     for every point that images i < j share: the first nonzero 40-bit limb of w and the next
+ *                                one, times cnt_i, are added to their acc[k][i][j]
+ * cds_colmap_obs_depth_f64       z[e] = ((r0 x + r1 y) + r2 z) + r3 with r = zrow[obs_img[e]] (row 2 of [R | t]) and
+ *                                (x, y, z) = xyz[obs_pt[e]], for the n valid observations
+ * cds_colmap_depth_ranges_f64    z_sorted: per image (obs_ptr [N+1]) its z values ascending; out [N][2] = the mean of the
+ *                                lowest min(num_min[i], n_i) and of the highest min(num_max[i], n_i), summed ascending;
+ *                                every image needs n_i >= 1 and num_min, num_max >= 1
+ */
+#define CDS_COLMAP_SCORE_QUANTUM_LOG2 80
+#define CDS_COLMAP_SCORE_MAX_LIMBS 28
+int cds_colmap_score_quantum_log2(void);
+int cds_colmap_score_limbs(double theta0, double sigma1, double sigma2);
+int cds_colmap_pair_scores_f64(const long long* pair_off, const long long* ptr, const int* img, const int* cnt,
+                               const double* xyz, const double* centres, long long P, long long T, int N, double theta0,
+                               double sigma1, double sigma2, int limbs, long long* acc, void* stream);
+int cds_colmap_obs_depth_f64(const int* obs_img, const long long* obs_pt, const double* xyz, const double* zrow, long long n,
+                             double* z, void* stream);
+int cds_colmap_depth_ranges_f64(const double* z_sorted, const long long* obs_ptr, const int* num_min, const int* num_max,
+                                int N, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

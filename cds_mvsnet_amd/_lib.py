@@ -22,6 +22,8 @@ WARP_FAST_POSITIONS = AGG_FAST_POSITIONS
 MAX_VIEWS = 8
 MAX_IMAGES = 16
 STAGE_STATE_WORDS = 2080
+DEPTH_METRICS_MAX_T = 8
+DEPTH_METRICS_MAX_GROUPS = 1024
 EINVAL = -1000
 
 P = c_void_p
@@ -151,6 +153,8 @@ SIGNATURES = {
     "cds_colmap_pair_scores_f64": [P, P, P, P, P, P, L, L, I, DB, DB, DB, I, P, P],
     "cds_colmap_obs_depth_f64": [P, P, P, P, L, P, P],
     "cds_colmap_depth_ranges_f64": [P, P, P, P, I, P, P],
+    "cds_depth_metrics_f32": [P, P, P, P, F, I, L, I, P, L, P, P],
+    "cds_gt_pyramid_f32": [P, P, I, I, I, P, P, I, I, I, P, P, P],
 }
 
 _lib = None

@@ -8,6 +8,8 @@ the reference views `idx % world == rank` (independent depth maps, no collective
 `<out>/<scan>/depth_est/%08d.pfm`, `confidence/%08d.pfm` (3 channels = stage 1-3 confidences), `cams/%08d_cam.txt`,
 `images/%08d.jpg`, ready for the fusion step.  `--fuse` then writes `<out>/<scan>.ply` with the normal fusion (fusion.py) or,
 with `--filter_method gipuma`, the gipuma-style one (gipuma.py; `--prob_threshold`, `--disp_threshold`, `--num_consistent`).
+`--save_stages` also writes the three stages' own depth maps, `<out>/<scan>/depth_stage{1,2,3}/%08d.pfm`, at their resolutions
+(what evaluations/precision.py scores stage by stage; `python -m cds_mvsnet_amd.depth_eval --folders ...`).
 """
 from __future__ import annotations
 
@@ -19,7 +21,7 @@ import numpy as np
 import torch
 
 from . import CDSMVSNet, seeded_init_
-from .mvs_io import EvalScenes, save_outputs
+from .mvs_io import EvalScenes, save_outputs, write_pfm
 
 
 class _Opaque:
@@ -140,6 +142,11 @@ def run(args) -> float:
                      out["photometric_confidence"][0].cpu().numpy()]
             save_outputs(args.outdir, s["filename"], out["refined_depth"][0].cpu().numpy(), confs,
                          s["proj_matrices"][last][0], s["imgs"][0])
+            if args.save_stages:
+                for k in (1, 2, 3):
+                    p = os.path.join(args.outdir, s["filename"].format(f"depth_stage{k}", ".pfm"))
+                    os.makedirs(os.path.dirname(p), exist_ok=True)
+                    write_pfm(p, out[f"stage{k}"]["depth"][0].float().cpu().numpy())
             print(f"[{rank}] {idx + 1}/{len(data)} {s['filename'].format('depth_est', '.pfm')} {times[-1] * 1e3:.1f} ms", flush=True)
     avg = float(np.mean(times)) if times else 0.0
     print(f"[{rank}] average time: {avg:.4f} s over {len(times)} depth maps")
@@ -184,6 +191,8 @@ def parse_args(argv=None) -> argparse.Namespace:
     ap.add_argument("--max_w", type=int, default=640)
     ap.add_argument("--temperature", type=float, default=0.01)
     ap.add_argument("--dataset", default="dtu", choices=["dtu", "tt", "general"])
+    ap.add_argument("--save_stages", action="store_true",
+                    help="also write depth_stage{1,2,3}/%%08d.pfm: the depth map of each stage at its own resolution")
     ap.add_argument("--fuse", action="store_true", help="filter + fuse the saved depth maps into <outdir>/<scan>.ply")
     ap.add_argument("--conf", default="0.0,0.0,0.0", help="per-stage confidence thresholds (test.py:61)")
     ap.add_argument("--thres_view", type=int, default=3)

@@ -1619,3 +1619,122 @@ def colmap_depth_ranges(obs_img: Tensor, obs_pt: Tensor, xyz: Tensor, zrow: Tens
     check(lib.cds_colmap_depth_ranges_f64(zs.data_ptr(), obs_ptr.data_ptr(), num_min.data_ptr(), num_max.data_ptr(), N,
                                           out.data_ptr(), _stream(xyz)), "cds_colmap_depth_ranges_f64")
     return out
+
+
+# ---- depth maps against ground truth (csrc/depth_metrics.hip; cds_mvsnet_amd/depth_eval.py drives these) ----
+DEPTH_METRICS_MAX_T = _lib.DEPTH_METRICS_MAX_T
+
+
+def _metric_thresholds(thr, B: int, device) -> Tuple[Optional[Tensor], int]:
+    """thr of depth_metric_sums -> (float32 device tensor [B,T] or None at T = 0, T).  Host values (sequence, numpy array, CPU tensor;
+    [T] for all images or [B,T]) are rounded to float32, checked to ascend and uploaded without a host wait; a device tensor must be
+    float32 [B,T] and is taken as it is (checking its order would cost the host read this op exists to avoid)."""
+    if isinstance(thr, torch.Tensor) and thr.is_cuda:
+        if thr.dtype != torch.float32 or thr.dim() != 2 or thr.shape[0] != B or not thr.is_contiguous() or thr.device != device:
+            raise ValueError(f"depth_metric_sums: device thresholds must be a contiguous float32 [{B},T] tensor on {device}")
+        T = int(thr.shape[1])
+        if T > DEPTH_METRICS_MAX_T:
+            raise ValueError(f"depth_metric_sums: {T} thresholds, at most {DEPTH_METRICS_MAX_T} are supported")
+        return (thr if T else None), T
+    t = torch.as_tensor(thr, dtype=torch.float64).detach().to(torch.float32)      # nearest float32, as ATen rounds a Python scalar
+    if t.dim() == 1:
+        t = t.unsqueeze(0).expand(B, t.shape[0])
+    if t.dim() != 2 or t.shape[0] != B:
+        raise ValueError(f"depth_metric_sums: thresholds must be [T] or [{B},T], got {tuple(t.shape)}")
+    T = int(t.shape[1])
+    if T > DEPTH_METRICS_MAX_T:
+        raise ValueError(f"depth_metric_sums: {T} thresholds, at most {DEPTH_METRICS_MAX_T} are supported")
+    if T == 0:
+        return None, 0
+    if bool(torch.isnan(t).any()) or (T > 1 and bool((t[:, 1:] < t[:, :-1]).any())):
+        raise ValueError("depth_metric_sums: thresholds must ascend (and not be NaN)")
+    return geo(t.contiguous(), device, "thresholds"), T
+
+
+def depth_metric_sums(est: Tensor, gt: Tensor, mask: Tensor, thr, cap: float) -> Tensor:
+    """The sums every depth-map metric is made of, for all images in one pass: est, gt, mask [B,h,w] float32 on the device (mask > 0.5
+    selects), thr: T <= 8 ascending thresholds ([T], [B,T]; see :func:`_metric_thresholds`), cap: upper end of the last band ->
+    [B, 3T+5] float64 on the device, per image: n, sum e, sum e^2, #{e > thr_t} (T), then (count, sum e) of the T+1 bands
+    [0,thr0], [thr0,thr1], ..., [thr_{T-1},cap], inclusive at both ends, with e = |est - gt| in float32 and float32 comparisons
+    (include/cds_mvsnet_hip.h: cds_depth_metrics_f32).  Nothing is read back."""
+    if not (isinstance(est, torch.Tensor) and isinstance(gt, torch.Tensor) and isinstance(mask, torch.Tensor)):
+        raise TypeError("depth_metric_sums: est, gt and mask must be tensors")
+    if est.dim() != 3 or est.numel() == 0 or tuple(gt.shape) != tuple(est.shape) or tuple(mask.shape) != tuple(est.shape):
+        raise ValueError(f"depth_metric_sums: est, gt, mask must share one non-empty [B,h,w] shape, got {tuple(est.shape)}, "
+                         f"{tuple(gt.shape)}, {tuple(mask.shape)}")
+    pe, pg, pm = _dev(est, "est"), _dev(gt, "gt"), _dev(mask, "mask")
+    if gt.device != est.device or mask.device != est.device:
+        raise RuntimeError("depth_metric_sums: est, gt and mask must live on one device")
+    B, hw = int(est.shape[0]), int(est.shape[1] * est.shape[2])
+    st = _stream(est)
+    thr_dev, T = _metric_thresholds(thr, B, est.device)
+    ws_doubles = B * max(1, _lib.DEPTH_METRICS_MAX_GROUPS // B) * (3 * DEPTH_METRICS_MAX_T + 5)
+    ws = torch.empty(ws_doubles, dtype=torch.float64, device=est.device)
+    out = torch.empty((B, 3 * T + 5), dtype=torch.float64, device=est.device)
+    check(_lib.load().cds_depth_metrics_f32(pe, pg, pm, thr_dev.data_ptr() if thr_dev is not None else None, float(cap), B, hw, T,
+                                            ws.data_ptr(), ws_doubles, out.data_ptr(), st), "cds_depth_metrics_f32")
+    return out
+
+
+def index_tables(rows, cols, Hs: int, Ws: int, device) -> Tuple[Tensor, Tensor]:
+    """The (rows, cols) source-index tables of :func:`gt_pyramid` on the device: host sequences / arrays / CPU tensors of integers,
+    checked against the Hs x Ws source here, uploaded once -> two int32 device tensors that any number of gt_pyramid calls on sources
+    of that size can share (a loader builds them once per dataset, not once per view)."""
+    r = torch.as_tensor(rows).detach().cpu().reshape(-1)
+    c = torch.as_tensor(cols).detach().cpu().reshape(-1)
+    if r.is_floating_point() or c.is_floating_point() or r.numel() == 0 or c.numel() == 0:
+        raise ValueError("gt_pyramid: rows and cols must be non-empty integer tables")
+    if int(r.min()) < 0 or int(r.max()) >= Hs or int(c.min()) < 0 or int(c.max()) >= Ws:
+        raise ValueError(f"gt_pyramid: index tables reach outside the {Hs} x {Ws} source")
+    tab = torch.cat((r, c)).to(torch.int32).contiguous().pin_memory().to(device, non_blocking=True)
+    return tab[:r.numel()], tab[r.numel():]
+
+
+def gt_pyramid(depth_src: Tensor, rows, cols, levels: int = 4, mask_src: Optional[Tensor] = None, mask_thresh: int = 10):
+    """Multi-scale ground truth in one launch: depth_src [Hs,Ws] float32 on the device; rows [h], cols [w]: integer source indices of
+    the finest level - host sequences / arrays / CPU tensors (checked against the source size and uploaded here, through
+    :func:`index_tables`), or the two int32 device tensors index_tables returned earlier (used as they are: the kernel gives depth 0,
+    mask 0 for an entry outside the source); level k < levels <= 4 is every 2^k-th pixel of the finest, so h and w must be
+    multiples of 2^(levels-1).  mask_src: uint8 [Hs,Ws] on the device, mask = value > mask_thresh; None: mask = depth > 0.
+    -> (depths, masks): lists of `levels` float32 tensors, finest first, views of two packed buffers
+    (include/cds_mvsnet_hip.h: cds_gt_pyramid_f32)."""
+    if not isinstance(depth_src, torch.Tensor) or depth_src.dim() != 2 or depth_src.numel() == 0:
+        raise ValueError("gt_pyramid: depth_src must be a non-empty [Hs,Ws] tensor")
+    ps = _dev(depth_src, "depth_src")
+    Hs, Ws = int(depth_src.shape[0]), int(depth_src.shape[1])
+    levels = int(levels)
+    if not 1 <= levels <= 4:
+        raise ValueError(f"gt_pyramid: levels must be 1..4, got {levels}")
+    dev = depth_src.device
+    on_dev = [isinstance(t, torch.Tensor) and t.is_cuda for t in (rows, cols)]
+    if any(on_dev):
+        if not all(on_dev) or rows.device != dev or cols.device != dev or rows.dim() != 1 or cols.dim() != 1 or \
+                rows.numel() == 0 or cols.numel() == 0:
+            raise ValueError(f"gt_pyramid: device tables must both be non-empty 1-d tensors on {dev} (ops.index_tables)")
+        _dev_int(rows, torch.int32, "rows"), _dev_int(cols, torch.int32, "cols")
+    else:
+        rows, cols = index_tables(rows, cols, Hs, Ws, dev)
+    h, w = int(rows.numel()), int(cols.numel())
+    step = 1 << (levels - 1)
+    if h % step or w % step:
+        raise ValueError(f"gt_pyramid: {h} x {w} is not a multiple of {step} in both directions, as {levels} levels need")
+    pmask = None
+    if mask_src is not None:
+        if tuple(mask_src.shape) != (Hs, Ws) or mask_src.device != depth_src.device:
+            raise ValueError(f"gt_pyramid: mask_src must be [{Hs},{Ws}] on {depth_src.device}")
+        pmask = _dev_int(mask_src, torch.uint8, "mask_src")
+        if not 0 <= int(mask_thresh) <= 255:
+            raise ValueError("gt_pyramid: mask_thresh must be 0..255")
+    st = _stream(depth_src)
+    sizes = [(h >> k, w >> k) for k in range(levels)]
+    total = sum(a * b for a, b in sizes)
+    dout = torch.empty(total, dtype=torch.float32, device=dev)
+    mout = torch.empty(total, dtype=torch.float32, device=dev)
+    check(_lib.load().cds_gt_pyramid_f32(ps, pmask, int(mask_thresh), Hs, Ws, rows.data_ptr(), cols.data_ptr(), h, w, levels,
+                                         dout.data_ptr(), mout.data_ptr(), st), "cds_gt_pyramid_f32")
+    depths, masks, off = [], [], 0
+    for a, b in sizes:
+        depths.append(dout[off:off + a * b].view(a, b))
+        masks.append(mout[off:off + a * b].view(a, b))
+        off += a * b
+    return depths, masks

@@ -800,6 +800,36 @@ int cds_colmap_obs_depth_f64(const int* obs_img, const long long* obs_pt, const 
 int cds_colmap_depth_ranges_f64(const double* z_sorted, const long long* obs_ptr, const int* num_min, const int* num_max,
                                 int N, double* out, void* stream);
 
+/* Depth maps scored against ground truth, and the multi-scale ground truth itself (csrc/depth_metrics.hip; reference: utils.py:134-167
+ * as trainer/trainer.py:140-164 calls them, evaluations/precision.py:8-13,87-91, datasets/dtu_yao.py:79-128,
+ * datasets/blended_dataset.py:79-120).
+ *
+ * cds_depth_metrics_f32   est, gt, mask [B][hw]; thr [B][T] on the DEVICE, ascending per image, 0 <= T <= CDS_DEPTH_METRICS_MAX_T (NULL
+ *                         at T = 0).  Per image b, over the pixels with mask > 0.5, e = fabsf(est - gt) in fp32, out [b][3T + 5]:
+ *                           [0] n   [1] sum e   [2] sum e^2 (the fp32 e squared in fp64)   [3 + t] #{e > thr[b][t]}
+ *                           [3 + T + 2k], [3 + T + 2k + 1]: count and sum of e over lo_k <= e <= hi_k for the T + 1 bands
+ *                           [0, thr0], [thr0, thr1], ..., [thr_{T-1}, cap] - inclusive at BOTH ends (utils.py:164): an error exactly on
+ *                           a threshold lies in two bands.
+ *                         Every comparison is fp32 against the fp32 threshold; sums are fp64 in a fixed order (per-workgroup records in
+ *                         ws, reduced by a second pass; no atomics): bit-reproducible.  A NaN error counts in n and makes the two sums
+ *                         NaN; it exceeds no threshold and lies in no band.  One call handles all B images; any hw >= 1.
+ *                         ws: ws_doubles >= CDS_DEPTH_METRICS_WS_DOUBLES(B) doubles of workspace.
+ * cds_gt_pyramid_f32      src [Hs][Ws]: a depth map.  Level 0 pixel (y, x) = src(rows[y], cols[x]) (rows [h], cols [w]: int32 tables on
+ *                         the DEVICE - the resize / crop rule is the host's), level k < levels <= 4 pixel (y, x) = level 0 pixel
+ *                         (y 2^k, x 2^k): cv2.resize(INTER_NEAREST) to (w / 2^k, h / 2^k) when h and w are multiples of 2^(levels-1),
+ *                         which is required.  mask = mask_src(rows[y], cols[x]) > mask_thresh ? 1 : 0 (mask_src [Hs][Ws] uint8; DTU: 10,
+ *                         dtu_yao.py:99), or with mask_src NULL depth > 0 ? 1 : 0 (blended_dataset.py:110).  depth_out, mask_out: the
+ *                         levels packed one after the other, level k = (h >> k) x (w >> k) floats.  One launch writes everything.  A
+ *                         table entry outside the source yields depth 0, mask 0. */
+#define CDS_DEPTH_METRICS_MAX_T 8
+#define CDS_DEPTH_METRICS_MAX_GROUPS 1024 /* workgroups of the first pass over all images (at least one per image) */
+#define CDS_DEPTH_METRICS_WS_DOUBLES(B) \
+  ((long long)(B) * (CDS_DEPTH_METRICS_MAX_GROUPS / (B) < 1 ? 1 : CDS_DEPTH_METRICS_MAX_GROUPS / (B)) * (3 * CDS_DEPTH_METRICS_MAX_T + 5))
+int cds_depth_metrics_f32(const float* est, const float* gt, const float* mask, const float* thr, float cap, int B, long long hw, int T,
+                          double* ws, long long ws_doubles, double* out, void* stream);
+int cds_gt_pyramid_f32(const float* src, const unsigned char* mask_src, int mask_thresh, int Hs, int Ws, const int* rows, const int* cols,
+                       int h, int w, int levels, float* depth_out, float* mask_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

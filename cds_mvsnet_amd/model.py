@@ -59,7 +59,7 @@ def _side_stream(device) -> "torch.cuda.Stream":
     idx = device.index if device.index is not None else torch.cuda.current_device()
     if idx not in _SIDE_STREAMS:
         _SIDE_STREAMS[idx] = torch.cuda.Stream(device=device)
-    return _SIDE_STREAMS[idx]   # A/B knob: the prob layer as a z-marching matrix-core kernel
+    return _SIDE_STREAMS[idx]
 
 
 # ------------------------------------------------------------------------------------------------
@@ -214,6 +214,113 @@ class ConvBn3d(nn.Module):
         self.bn = nn.BatchNorm3d(out_c)
 
 
+# The ten ConvBn3d layers of CostRegNet in network order: the packer of the matrix-core kernel each one runs on and the key suffix that
+# kernel's split-bf16 operand is stored under (the split-f16 operand of the same kernel: ".wh", with its inverse scale ".whs").
+COSTREG_KERNELS = {
+    "conv0": (ops.split_pack_conv3d_pair, ".ws"),     # Cout = 8, stride 1: voxel-pair columns (no matrix row multiplies padding)
+    "conv1": (ops.split_pack_conv3d, ".ws"),
+    "conv2": (ops.split_pack_conv3d, ".ws"),
+    "conv3": (ops.split_pack_conv3d, ".ws"),
+    "conv4": (ops.split_pack_conv3d, ".ws"),
+    "conv5": (ops.split_pack_conv3d, ".ws"),
+    "conv6": (ops.split_pack_conv3d, ".ws"),
+    "conv7": (ops.split_pack_deconv3d, ".ws"),
+    "conv9": (ops.split_pack_deconv_cls, ".wc"),      # 32 -> 16: z-marching class-per-wave kernel (csrc/deconv3d_zm.hip)
+    "conv11": (ops.split_pack_deconv_prob, ".wz"),    # fused with the conv0 residual and prob (csrc/deconv_prob_zm.hip)
+}
+# slab.py exchanges halo rows between conv11 and prob, so it cannot fuse them, and keeps the tiled transposed kernel for conv9 as well
+COSTREG_SLAB_KERNELS = {**COSTREG_KERNELS, "conv9": (ops.split_pack_deconv3d, ".ws"), "conv11": (ops.split_pack_deconv3d, ".ws")}
+
+
+def costreg_unet(layers, vol, refresh=None):
+    """The wiring of CostRegNet (module.py:305-315), stated once for every way of running it: three stride-2 levels down, three
+    transposed layers with their skips back up, prob.  The tensors' layout is the layers' business (planar, channels-last, batched).
+
+    layers: ``conv(name, x, stride)``, ``deconv(name, x, skip)`` (transposed layer + residual) and ``tail(x, skip, refresh)``: conv11 +
+    the conv0 residual, then prob -- one step, because the product path fuses the two layers into one kernel.
+    refresh(y, level, need_top, need_bot): called on every layer output the next layer reads across a slab border (slab.py's halo
+    exchange; level = number of stride-2 layers above y); the one between conv11 and prob is the tail's to call.
+    An intermediate goes as soon as its last reader ran: c1, c3, c5 after the next layer, c4 after conv7, c2 after conv9, c0 last."""
+    refresh = refresh or (lambda y, level, need_top, need_bot: None)
+    c0 = layers.conv("conv0", vol, 1)
+    refresh(c0, 0, True, False)                           # conv1 (stride 2) reads one row above
+    c1 = layers.conv("conv1", c0, 2)
+    refresh(c1, 1, True, True)
+    c2 = layers.conv("conv2", c1, 1)
+    del c1
+    refresh(c2, 1, True, False)
+    c3 = layers.conv("conv3", c2, 2)
+    refresh(c3, 2, True, True)
+    c4 = layers.conv("conv4", c3, 1)
+    del c3
+    refresh(c4, 2, True, False)
+    c5 = layers.conv("conv5", c4, 2)
+    refresh(c5, 3, True, True)
+    x = layers.conv("conv6", c5, 1)
+    del c5
+    refresh(x, 3, False, True)                            # a transposed layer reads one coarse row below
+    x = layers.deconv("conv7", x, c4)
+    del c4
+    refresh(x, 2, False, True)
+    x = layers.deconv("conv9", x, c2)
+    del c2
+    refresh(x, 1, False, True)
+    return layers.tail(x, c0, refresh)
+
+
+class _ExactLayers:
+    """costreg_unet on the exact-fp32 kernels (one fmaf chain per output), planar volumes [C,D,h,w]."""
+
+    def __init__(self, p: Dict[str, Tensor]):
+        self.p = p
+
+    def conv(self, name: str, x: Tensor, stride: int) -> Tensor:
+        return ops.conv3d_k3(x, self.p[name + ".w"], self.p[name + ".b"], stride=stride, wcl=self.p.get(name + ".wcl"))
+
+    def deconv(self, name: str, x: Tensor, skip: Tensor) -> Tensor:
+        return ops.deconv3d_k3s2(x, self.p[name + ".w"], self.p[name + ".b"], skip=skip)
+
+    def tail(self, x: Tensor, skip: Tensor, refresh) -> Tensor:
+        return ops.conv3d_k3(self.deconv("conv11", x, skip), self.p["prob.w"], None, relu=False)[0]
+
+
+class SplitLayers:
+    """costreg_unet on the matrix-core kernels, channels-last volumes [D,h,w,C]; every layer runs on the kernel `kernels` names for it.
+    With a bound (>= max |volume|) the whole network runs in split-f16: every layer leaves max |output| in its slot of one tensor
+    zeroed per forward, and the next layer scales its input by it.  Without one: split-bf16."""
+
+    def __init__(self, p: Dict[str, Tensor], bound: Optional[Tensor] = None, kernels=COSTREG_KERNELS):
+        self.p, self.kernels, self.in_bound = p, kernels, None
+        if bound is not None and ops.USE_SPLIT_F16 and all(name + ".wh" in p for name in kernels):
+            self.in_bound, self.slots, self.used = bound, torch.zeros((16,), dtype=torch.float32, device=bound.device), 0
+
+    def _layer(self, name: str, publish: bool = True):
+        """(packer of the layer's kernel, operand, bias, the split-f16 keywords of its wrapper)."""
+        packer, key = self.kernels[name]
+        if self.in_bound is None:
+            return packer, self.p[name + key], self.p[name + ".b"], {}
+        kw = {"in_bound": self.in_bound, "w_inv_scale": self.p[name + ".whs"]}
+        if publish:
+            self.in_bound = kw["out_bound"] = self.slots[self.used:self.used + 1]
+            self.used += 1
+        return packer, self.p[name + ".wh"], self.p[name + ".b"], kw
+
+    def conv(self, name: str, x: Tensor, stride: int) -> Tensor:
+        packer, w, b, kw = self._layer(name)
+        return ops.conv3d_sbf(x, w, b, b.shape[0], stride=ops.SBF_PAIR if packer is ops.split_pack_conv3d_pair else stride, **kw)
+
+    def deconv(self, name: str, x: Tensor, skip: Tensor, out_planar: bool = False) -> Tensor:
+        packer, w, b, kw = self._layer(name)
+        if packer is ops.split_pack_deconv_cls:
+            return ops.deconv3d_zm(x, w, b, skip=skip, **kw)
+        return ops.deconv3d_sbf(x, w, b, b.shape[0], skip=skip, out_planar=out_planar, **kw)
+
+    def tail(self, x: Tensor, skip: Tensor, refresh) -> Tensor:
+        # conv11 + the conv0 residual + prob: one z-marching kernel, the 8-channel volume between them never reaches HBM
+        _, w, b, kw = self._layer("conv11", publish=False)
+        return ops.deconv_prob_zm(x, w, b, skip, self.p["prob.tab"], **kw)
+
+
 class CostRegNet(_PackedHolder):
     """3D U-Net regulariser (module.py:270-315); forward runs on the HIP conv kernels."""
 
@@ -243,53 +350,37 @@ class CostRegNet(_PackedHolder):
 
     def _pack(self) -> Dict[str, Tensor]:
         out: Dict[str, Tensor] = {}
-        for name in ("conv0", "conv1", "conv2", "conv3", "conv4", "conv5", "conv6", "conv7", "conv9", "conv11"):
+        sbf = self.split_bf16_supported()
+        for name, kernel in COSTREG_KERNELS.items():
             unit: ConvBn3d = getattr(self, name)
             scale, shift = _bn_fold(unit.bn)
-            w = unit.conv.weight.detach()
-            if unit.transposed:   # [Cin,Cout,3,3,3]
-                w = (w * scale.view(1, -1, 1, 1, 1)).permute(0, 2, 3, 4, 1)
-            else:                 # [Cout,Cin,3,3,3]
-                w = (w * scale.view(-1, 1, 1, 1, 1)).permute(1, 2, 3, 4, 0)
-            out[name + ".w"] = w.reshape(w.shape[0], 27, w.shape[-1]).contiguous()
+            # the BN-folded weight in the holder's own layout: ConvTranspose3d [Cin,Cout,3,3,3], Conv3d [Cout,Cin,3,3,3]
+            wf = unit.conv.weight.detach() * (scale.view(1, -1, 1, 1, 1) if unit.transposed else scale.view(-1, 1, 1, 1, 1))
+            w = wf.permute(0, 2, 3, 4, 1) if unit.transposed else wf.permute(1, 2, 3, 4, 0)      # [Cin,3,3,3,Cout]
+            cin, cout = w.shape[0], w.shape[-1]
+            out[name + ".w"] = w.reshape(cin, 27, cout).contiguous()
             out[name + ".b"] = shift.contiguous()
-            if not unit.transposed and unit.stride == 1 and w.shape[0] % 16 == 0 and w.shape[-1] % 16 == 0:
+            if not unit.transposed and unit.stride == 1 and cin % 16 == 0 and cout % 16 == 0:
                 # ci-fastest copy [27,Cout,Cin] for the channels-last MFMA kernel (conv2, conv4, conv6)
-                out[name + ".wcl"] = w.permute(1, 2, 3, 4, 0).reshape(27, w.shape[-1], w.shape[0]).contiguous()
+                out[name + ".wcl"] = w.permute(1, 2, 3, 4, 0).reshape(27, cout, cin).contiguous()
+            if not sbf:
+                continue
+            # operands of the split-bf16 matrix-core kernels (csrc/conv3d_sbf.hip): the folded weights split exactly into three bf16
+            # terms, laid out per MFMA lane; the slab-parallel form (slab.py) also wants those of the kernels it swaps in
+            kernels = [kernel]
+            if self._slab_operands and COSTREG_SLAB_KERNELS[name] != kernel:
+                kernels.append(COSTREG_SLAB_KERNELS[name])
+            for packer, key in kernels:
+                out[name + key] = packer(wf)
+            # split-f16 operand (two fp16 terms of w x a power-of-two scale, + 1 / scale) where the layer's kernel has the form
+            packer = kernel[0]
+            code = ops.SBF_PAIR if packer is ops.split_pack_conv3d_pair else unit.stride
+            if ops.USE_SPLIT_F16 if unit.transposed else ops.conv3d_sf16_supported(cin, cout, code):
+                out[name + ".wh"], out[name + ".whs"] = packer(wf, f16=True)
         w = self.prob.weight.detach().permute(1, 2, 3, 4, 0)
         out["prob.w"] = w.reshape(w.shape[0], 27, 1).contiguous()
-        if self.split_bf16_supported():
-            # operands of the split-bf16 matrix-core kernels (csrc/conv3d_sbf.hip): BN-folded weights split exactly into
-            # three bf16 terms, laid out per MFMA lane
-            for name in ("conv0", "conv1", "conv2", "conv3", "conv4", "conv5", "conv6", "conv7", "conv9", "conv11"):
-                unit = getattr(self, name)
-                scale, _ = _bn_fold(unit.bn)
-                if name == "conv11":    # fused with the residual and prob (csrc/deconv_prob_zm.hip); the slab-parallel form
-                    # (slab.py) exchanges halo rows between the two layers and keeps the separate kernels (".ws" below)
-                    out[name + ".wz"] = ops.split_pack_deconv_prob(unit.conv.weight.detach() * scale.view(1, -1, 1, 1, 1))
-                    out["prob.tab"] = ops.pack_prob_table(self.prob.weight)
-                    if ops.USE_SPLIT_F16:
-                        out[name + ".wh"], out[name + ".whs"] = ops.split_pack_deconv_prob(unit.conv.weight.detach() * scale.view(1, -1, 1, 1, 1), f16=True)
-                if name == "conv9":     # 32 -> 16: z-marching class-per-wave kernel (csrc/deconv3d_zm.hip); ".ws" stays for slab.py
-                    out[name + ".wc"] = ops.split_pack_deconv_cls(unit.conv.weight.detach() * scale.view(1, -1, 1, 1, 1))
-                    if ops.USE_SPLIT_F16:
-                        out[name + ".wh"], out[name + ".whs"] = ops.split_pack_deconv_cls(unit.conv.weight.detach() * scale.view(1, -1, 1, 1, 1), f16=True)
-                if name == "conv7" and ops.USE_SPLIT_F16:
-                    out[name + ".wh"], out[name + ".whs"] = ops.split_pack_deconv3d(unit.conv.weight.detach() * scale.view(1, -1, 1, 1, 1), f16=True)
-                if unit.transposed:
-                    if name != "conv7" and not self._slab_operands:
-                        continue        # conv9 / conv11 run their z-marching forms; the tiled operands are slab.py's
-                    out[name + ".ws"] = ops.split_pack_deconv3d(unit.conv.weight.detach() * scale.view(1, -1, 1, 1, 1))
-                elif name == "conv0":   # Cout = 8, stride 1: voxel-pair columns (no matrix row multiplies padding)
-                    out[name + ".ws"] = ops.split_pack_conv3d_pair(unit.conv.weight.detach() * scale.view(-1, 1, 1, 1, 1))
-                else:
-                    out[name + ".ws"] = ops.split_pack_conv3d(unit.conv.weight.detach() * scale.view(-1, 1, 1, 1, 1))
-                # split-f16 operands (two fp16 terms of w x a power-of-two scale, + 1 / scale) of the layers that have the kernel
-                if not unit.transposed:
-                    wf = unit.conv.weight.detach() * scale.view(-1, 1, 1, 1, 1)
-                    code = ops.SBF_PAIR if name == "conv0" else unit.stride
-                    if ops.conv3d_sf16_supported(wf.shape[1], wf.shape[0], code):
-                        out[name + ".wh"], out[name + ".whs"] = (ops.split_pack_conv3d_pair if name == "conv0" else ops.split_pack_conv3d)(wf, f16=True)
+        if sbf:
+            out["prob.tab"] = ops.pack_prob_table(self.prob.weight)
         return out
 
     def split_bf16_supported(self) -> bool:
@@ -301,7 +392,7 @@ class CostRegNet(_PackedHolder):
         """volume [C,D,h,w] (one batch item; [D,h,w,C] with channels_last) -> [D,h,w].  D, h, w must be multiples of 8.
         The channels-last form runs the split-bf16 matrix-core kernels (fp32-class arithmetic, csrc/conv3d_sbf.hip), the
         planar form the exact-fp32 kernels (one fmaf chain per output).
-        bound: a 1-element device tensor >= max |volume| (channels-last form): conv0 - conv3 then run in split-f16 arithmetic (half
+        bound: a 1-element device tensor >= max |volume| (channels-last form): the network then runs in split-f16 arithmetic (half
         the matrix-pipe work at fp32-class error, csrc/sbf_common.hpp), each layer scaling its input by the bound its producer
         measured; None: split-bf16 throughout."""
         if self.training:
@@ -317,8 +408,8 @@ class CostRegNet(_PackedHolder):
             if channels_last:
                 if "conv0.ws" not in p:
                     raise RuntimeError("CostRegNet: channels-last input needs the split-bf16 kernels (CDS_CONV_EXACT=1 disables them)")
-                return self._run_cl(volume, p, bound)
-            return self._run(volume, p)
+                return costreg_unet(SplitLayers(p, bound), volume)
+            return costreg_unet(_ExactLayers(p), volume)
 
     def regress(self, volume_cl: Tensor, hyp: Tensor, bound: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
         """volume [D,h,w,C] channels-last + hypotheses [D,h,w] -> (depth [h,w], confidence [h,w]): CostRegNet followed by the
@@ -326,70 +417,6 @@ class CostRegNet(_PackedHolder):
         if self.training:
             raise RuntimeError("CostRegNet.regress is the inference path")
         return ops.softargmin_conf(self.forward(volume_cl, channels_last=True, bound=bound), hyp)
-
-    @staticmethod
-    def _run_cl(v: Tensor, p: Dict[str, Tensor], bound: Optional[Tensor] = None) -> Tensor:
-        f16 = bound is not None and all(f"conv{i}.wh" in p for i in (0, 1, 2, 3, 4, 5, 6, 7, 9, 11)) and ops.USE_SPLIT_F16
-        if f16:
-            # the whole network in split-f16: every layer leaves max |output| in its slot of `bnd` (zeroed once), the next one scales by it
-            bnd = torch.zeros((16,), dtype=torch.float32, device=v.device)
-            c0 = ops.conv3d_sbf(v, p["conv0.wh"], p["conv0.b"], 8, stride=ops.SBF_PAIR, in_bound=bound, w_inv_scale=p["conv0.whs"],
-                                out_bound=bnd[0:1])
-            c1 = ops.conv3d_sbf(c0, p["conv1.wh"], p["conv1.b"], 16, stride=2, in_bound=bnd[0:1], w_inv_scale=p["conv1.whs"],
-                                out_bound=bnd[1:2])
-            c2 = ops.conv3d_sbf(c1, p["conv2.wh"], p["conv2.b"], 16, in_bound=bnd[1:2], w_inv_scale=p["conv2.whs"], out_bound=bnd[2:3])
-            del c1
-            c3 = ops.conv3d_sbf(c2, p["conv3.wh"], p["conv3.b"], 32, stride=2, in_bound=bnd[2:3], w_inv_scale=p["conv3.whs"],
-                                out_bound=bnd[3:4])
-            c4 = ops.conv3d_sbf(c3, p["conv4.wh"], p["conv4.b"], 32, in_bound=bnd[3:4], w_inv_scale=p["conv4.whs"], out_bound=bnd[4:5])
-            del c3
-            c5 = ops.conv3d_sbf(c4, p["conv5.wh"], p["conv5.b"], 64, stride=2, in_bound=bnd[4:5], w_inv_scale=p["conv5.whs"],
-                                out_bound=bnd[5:6])
-            x = ops.conv3d_sbf(c5, p["conv6.wh"], p["conv6.b"], 64, in_bound=bnd[5:6], w_inv_scale=p["conv6.whs"], out_bound=bnd[6:7])
-            del c5
-            x = ops.deconv3d_sbf(x, p["conv7.wh"], p["conv7.b"], 32, skip=c4, in_bound=bnd[6:7], w_inv_scale=p["conv7.whs"],
-                                 out_bound=bnd[7:8])
-            del c4
-            x = ops.deconv3d_zm(x, p["conv9.wh"], p["conv9.b"], skip=c2, in_bound=bnd[7:8], w_inv_scale=p["conv9.whs"], out_bound=bnd[8:9])
-            del c2
-            return ops.deconv_prob_zm(x, p["conv11.wh"], p["conv11.b"], c0, p["prob.tab"], in_bound=bnd[8:9], w_inv_scale=p["conv11.whs"])
-        else:
-            c0 = ops.conv3d_sbf(v, p["conv0.ws"], p["conv0.b"], 8, stride=ops.SBF_PAIR)
-            c1 = ops.conv3d_sbf(c0, p["conv1.ws"], p["conv1.b"], 16, stride=2)
-            c2 = ops.conv3d_sbf(c1, p["conv2.ws"], p["conv2.b"], 16)
-            del c1
-            c3 = ops.conv3d_sbf(c2, p["conv3.ws"], p["conv3.b"], 32, stride=2)
-            c4 = ops.conv3d_sbf(c3, p["conv4.ws"], p["conv4.b"], 32)
-            del c3
-            c5 = ops.conv3d_sbf(c4, p["conv5.ws"], p["conv5.b"], 64, stride=2)
-            x = ops.conv3d_sbf(c5, p["conv6.ws"], p["conv6.b"], 64)
-            del c5
-        x = ops.deconv3d_sbf(x, p["conv7.ws"], p["conv7.b"], 32, skip=c4)
-        del c4
-        x = ops.deconv3d_zm(x, p["conv9.wc"], p["conv9.b"], skip=c2)
-        del c2
-        # conv11 + the conv0 residual + prob: one z-marching kernel, the 8-channel volume between them never reaches HBM
-        return ops.deconv_prob_zm(x, p["conv11.wz"], p["conv11.b"], c0, p["prob.tab"])
-
-    @staticmethod
-    def _run(volume: Tensor, p: Dict[str, Tensor]) -> Tensor:
-        c0 = ops.conv3d_k3(volume, p["conv0.w"], p["conv0.b"])
-        c1 = ops.conv3d_k3(c0, p["conv1.w"], p["conv1.b"], stride=2)
-        c2 = ops.conv3d_k3(c1, p["conv2.w"], p["conv2.b"], wcl=p.get("conv2.wcl"))
-        del c1
-        c3 = ops.conv3d_k3(c2, p["conv3.w"], p["conv3.b"], stride=2)
-        c4 = ops.conv3d_k3(c3, p["conv4.w"], p["conv4.b"], wcl=p.get("conv4.wcl"))
-        del c3
-        c5 = ops.conv3d_k3(c4, p["conv5.w"], p["conv5.b"], stride=2)
-        x = ops.conv3d_k3(c5, p["conv6.w"], p["conv6.b"], wcl=p.get("conv6.wcl"))
-        del c5
-        x = ops.deconv3d_k3s2(x, p["conv7.w"], p["conv7.b"], skip=c4)
-        del c4
-        x = ops.deconv3d_k3s2(x, p["conv9.w"], p["conv9.b"], skip=c2)
-        del c2
-        x = ops.deconv3d_k3s2(x, p["conv11.w"], p["conv11.b"], skip=c0)
-        del c0
-        return ops.conv3d_k3(x, p["prob.w"], None, relu=False)[0]
 
 
 class Refinement(_PackedHolder):

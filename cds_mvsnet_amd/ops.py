@@ -586,6 +586,11 @@ def split_pack_deconv3d(w: Tensor, f16: bool = False):
     return _split2_f16(a) if f16 else _split3(a)      # f16: (tensor, 1 / weight scale) for cds_deconv3d_sf16_f32
 
 
+def _sf16_bounds(in_bound: Tensor, w_inv_scale: float, out_bound: Optional[Tensor]) -> tuple:
+    """The arguments every split-f16 layer entry takes after those of its split-bf16 form."""
+    return _dev(in_bound, "in_bound"), float(w_inv_scale), _dev(out_bound, "out_bound") if out_bound is not None else None
+
+
 def deconv3d_sbf(x_cl: Tensor, wsplit: Tensor, bias: Optional[Tensor], cout: int, relu: bool = True,
                  skip: Optional[Tensor] = None, out_planar: bool = False, in_bound: Optional[Tensor] = None, w_inv_scale: float = 1.0,
                  out_bound: Optional[Tensor] = None) -> Tensor:
@@ -598,19 +603,16 @@ def deconv3d_sbf(x_cl: Tensor, wsplit: Tensor, bias: Optional[Tensor], cout: int
         raise ValueError("deconv3d_sbf: residual shape mismatch")
     if wsplit.dtype != torch.int16 or not wsplit.is_cuda or not wsplit.is_contiguous():
         raise ValueError("deconv3d_sbf: wsplit must be the contiguous int16 device tensor from split_pack_deconv3d")
-    if in_bound is not None:       # split-f16 arithmetic (cout == 32: conv7 of CostRegNet); operands from split_pack_deconv3d(..., f16=True)
-        if cout != 32 or out_planar:
-            raise ValueError("deconv3d_sbf: the split-f16 form exists for cout == 32, channels-last output")
-        check(_lib.load().cds_deconv3d_sf16_f32(_dev(x_cl, "x"), wsplit.data_ptr(), _dev(bias, "bias") if bias is not None else None,
-                                                _dev(skip, "skip") if skip is not None else None, out.data_ptr(), Cin, cout, D, H, W,
-                                                ACT_RELU if relu else ACT_NONE, _dev(in_bound, "in_bound"), float(w_inv_scale),
-                                                _dev(out_bound, "out_bound") if out_bound is not None else None, _stream(x_cl)),
-              "cds_deconv3d_sf16_f32")
-        return out
-    check(_lib.load().cds_deconv3d_sbf_f32(_dev(x_cl, "x"), wsplit.data_ptr(), _dev(bias, "bias") if bias is not None else None,
-                                           _dev(skip, "skip") if skip is not None else None, out.data_ptr(), Cin, cout,
-                                           D, H, W, ACT_RELU if relu else ACT_NONE, 1 if out_planar else 0, _stream(x_cl)),
-          "cds_deconv3d_sbf_f32")
+    # in_bound given: split-f16 arithmetic (cout == 32: conv7 of CostRegNet); operands from split_pack_deconv3d(..., f16=True)
+    if in_bound is not None and (cout != 32 or out_planar):
+        raise ValueError("deconv3d_sbf: the split-f16 form exists for cout == 32, channels-last output")
+    lib = _lib.load()
+    args = (_dev(x_cl, "x"), wsplit.data_ptr(), _dev(bias, "bias") if bias is not None else None,
+            _dev(skip, "skip") if skip is not None else None, out.data_ptr(), Cin, cout, D, H, W, ACT_RELU if relu else ACT_NONE)
+    if in_bound is not None:
+        check(lib.cds_deconv3d_sf16_f32(*args, *_sf16_bounds(in_bound, w_inv_scale, out_bound), _stream(x_cl)), "cds_deconv3d_sf16_f32")
+    else:
+        check(lib.cds_deconv3d_sbf_f32(*args, 1 if out_planar else 0, _stream(x_cl)), "cds_deconv3d_sbf_f32")
     return out
 
 
@@ -647,16 +649,13 @@ def deconv3d_zm(x_cl: Tensor, wcls: Tensor, bias: Optional[Tensor], relu: bool =
         raise ValueError("deconv3d_zm: residual shape mismatch")
     if wcls.dtype != torch.int16 or not wcls.is_cuda or not wcls.is_contiguous() or wcls.numel() != 8 * 4 * 2 * 3 * 64 * 8:
         raise ValueError("deconv3d_zm: wcls must be the contiguous int16 device tensor from split_pack_deconv_cls")
+    lib = _lib.load()
+    args = (_dev(x_cl, "x"), wcls.data_ptr(), _dev(bias, "bias") if bias is not None else None,
+            _dev(skip, "skip") if skip is not None else None, out.data_ptr(), Cin, 16, D, H, W, ACT_RELU if relu else ACT_NONE)
     if in_bound is not None:
-        check(_lib.load().cds_deconv3d_zm_sf16_f32(_dev(x_cl, "x"), wcls.data_ptr(), _dev(bias, "bias") if bias is not None else None,
-                                                   _dev(skip, "skip") if skip is not None else None, out.data_ptr(), Cin, 16, D, H, W,
-                                                   ACT_RELU if relu else ACT_NONE, _dev(in_bound, "in_bound"), float(w_inv_scale),
-                                                   _dev(out_bound, "out_bound") if out_bound is not None else None, _stream(x_cl)),
-              "cds_deconv3d_zm_sf16_f32")
-        return out
-    check(_lib.load().cds_deconv3d_zm_f32(_dev(x_cl, "x"), wcls.data_ptr(), _dev(bias, "bias") if bias is not None else None,
-                                          _dev(skip, "skip") if skip is not None else None, out.data_ptr(), Cin, 16, D, H, W,
-                                          ACT_RELU if relu else ACT_NONE, _stream(x_cl)), "cds_deconv3d_zm_f32")
+        check(lib.cds_deconv3d_zm_sf16_f32(*args, *_sf16_bounds(in_bound, w_inv_scale, out_bound), _stream(x_cl)), "cds_deconv3d_zm_sf16_f32")
+    else:
+        check(lib.cds_deconv3d_zm_f32(*args, _stream(x_cl)), "cds_deconv3d_zm_f32")
     return out
 
 
@@ -707,20 +706,19 @@ def deconv_prob_zm(x_cl: Tensor, wsplit: Tensor, bias: Tensor, skip: Tensor, pro
     if prob_table.numel() != 216 or bias.numel() != 8:
         raise ValueError("deconv_prob_zm: prob_table from pack_prob_table, bias [8]")
     out = torch.empty((2 * D, 2 * H, 2 * W), dtype=torch.float32, device=x_cl.device)
+    lib = _lib.load()
+    args = (_dev(x_cl, "x"), wsplit.data_ptr(), _dev(bias, "bias"), _dev(skip, "skip"), _dev(prob_table, "prob_table"), out.data_ptr(), D, H, W)
     if in_bound is not None:
-        check(_lib.load().cds_deconv_prob_zm_sf16_f32(_dev(x_cl, "x"), wsplit.data_ptr(), _dev(bias, "bias"), _dev(skip, "skip"),
-                                                      _dev(prob_table, "prob_table"), out.data_ptr(), D, H, W, _dev(in_bound, "in_bound"),
-                                                      float(w_inv_scale), _stream(x_cl)), "cds_deconv_prob_zm_sf16_f32")
-        return out
-    check(_lib.load().cds_deconv_prob_zm_f32(_dev(x_cl, "x"), wsplit.data_ptr(), _dev(bias, "bias"), _dev(skip, "skip"),
-                                             _dev(prob_table, "prob_table"), out.data_ptr(), D, H, W, _stream(x_cl)),
-          "cds_deconv_prob_zm_f32")
+        check(lib.cds_deconv_prob_zm_sf16_f32(*args, _dev(in_bound, "in_bound"), float(w_inv_scale), _stream(x_cl)),
+              "cds_deconv_prob_zm_sf16_f32")
+    else:
+        check(lib.cds_deconv_prob_zm_f32(*args, _stream(x_cl)), "cds_deconv_prob_zm_f32")
     return out
 
 
 SBF_PAIR = 101   # CDS_SBF_PAIR: stride code of the pair-packed stride-1, Cout = 8 form
 # split-f16 arithmetic (two fp16 terms, three products: half the matrix-pipe work of split-bf16 at fp32-class error) for the layers that
-# have it (round 6: conv0 - conv3 of CostRegNet); CDS_SPLIT_F16=0: split-bf16 everywhere (A/B, and the arithmetic of rounds 2-5)
+# have it (every layer of CostRegNet); CDS_SPLIT_F16=0: split-bf16 everywhere (A/B, and the arithmetic of rounds 2-5)
 USE_SPLIT_F16 = os.environ.get("CDS_SPLIT_F16", "1") != "0"
 
 
@@ -771,18 +769,15 @@ def conv3d_sbf(x_cl: Tensor, wsplit: Tensor, bias: Optional[Tensor], cout: int, 
     if Cin % 8 or wsplit.numel() != want:
         raise ValueError(f"conv3d_sbf: wsplit has {wsplit.numel()} entries, the packer gives {want} for Cin={Cin}, cout={cout}, "
                          f"stride code {stride}")
+    if in_bound is not None and (skip is not None or not conv3d_sf16_supported(Cin, cout, stride)):
+        raise ValueError(f"conv3d_sbf: no split-f16 kernel for Cin={Cin}, cout={cout}, stride code {stride}, skip={skip is not None}")
+    lib = _lib.load()
+    head = (_dev(x_cl, "x"), wsplit.data_ptr(), _dev(bias, "bias") if bias is not None else None)
+    dims = (out.data_ptr(), Cin, cout, D, H, W, stride, ACT_RELU if relu else ACT_NONE)
     if in_bound is not None:
-        if skip is not None or not conv3d_sf16_supported(Cin, cout, stride):
-            raise ValueError(f"conv3d_sbf: no split-f16 kernel for Cin={Cin}, cout={cout}, stride code {stride}, skip={skip is not None}")
-        check(_lib.load().cds_conv3d_sf16_f32(_dev(x_cl, "x"), wsplit.data_ptr(), _dev(bias, "bias") if bias is not None else None,
-                                              out.data_ptr(), Cin, cout, D, H, W, stride, ACT_RELU if relu else ACT_NONE,
-                                              _dev(in_bound, "in_bound"), float(w_inv_scale),
-                                              _dev(out_bound, "out_bound") if out_bound is not None else None, _stream(x_cl)),
-              "cds_conv3d_sf16_f32")
-        return out
-    check(_lib.load().cds_conv3d_sbf_f32(_dev(x_cl, "x"), wsplit.data_ptr(), _dev(bias, "bias") if bias is not None else None,
-                                         _dev(skip, "skip") if skip is not None else None, out.data_ptr(), Cin, cout,
-                                         D, H, W, stride, ACT_RELU if relu else ACT_NONE, _stream(x_cl)), "cds_conv3d_sbf_f32")
+        check(lib.cds_conv3d_sf16_f32(*head, *dims, *_sf16_bounds(in_bound, w_inv_scale, out_bound), _stream(x_cl)), "cds_conv3d_sf16_f32")
+    else:
+        check(lib.cds_conv3d_sbf_f32(*head, _dev(skip, "skip") if skip is not None else None, *dims, _stream(x_cl)), "cds_conv3d_sbf_f32")
     return out
 
 

@@ -21,17 +21,21 @@ Buffers (round 3, second form): the first version rebuilt every layer's input wi
 copies doubled the slab CostRegNet (6.8 vs 3.5 ms at 256 rows of the M1 volume).  Now every level-L activation is ONE dense buffer with
 8 >> L halo rows on each side (`slab_cost_regularization`), layers run on whole buffers and an exchanged row is written in place.
 
-The layer arithmetic itself is not in this file: `layers` is any object with conv / deconv / prob methods on dense channels-last
-tensors (product: `HipCostRegLayers`, the split-bf16 matrix-core kernels; the CPU tests plug in torch reference ops to check the
-slab bookkeeping and the exchanges against the unsharded network over gloo).
+Neither the network's wiring nor the layer arithmetic is in this file: the wiring is `model.costreg_unet`, and `layers` is any object
+with conv / deconv / prob methods on dense channels-last tensors (product: `HipCostRegLayers`, the split-bf16 matrix-core kernels; the
+CPU tests plug in torch reference ops to check the slab bookkeeping and the exchanges against the unsharded network over gloo).
 """
 from __future__ import annotations
 
 import contextlib
+from types import SimpleNamespace
 from typing import List, Optional, Tuple
 
 import torch
 import torch.distributed as dist
+
+from . import ops
+from .model import COSTREG_SLAB_KERNELS, SplitLayers, costreg_unet
 
 Tensor = torch.Tensor
 
@@ -116,9 +120,8 @@ class HaloComm:
             side.wait_stream(main)                                   # the producing layer
         ctx = torch.cuda.stream(side) if nccl else contextlib.nullcontext()
         recv_top = recv_bot = None
-        from . import ops as _ops
         t_host = ev0 = None
-        if _ops.PROFILE_ON:                                          # bench.py: measured us per exchange (events on the communication stream)
+        if ops.PROFILE_ON:                                          # bench.py: measured us per exchange (events on the communication stream)
             if nccl:
                 ev0 = torch.cuda.Event(enable_timing=True)
                 ev0.record(side)
@@ -160,12 +163,12 @@ class HaloComm:
                     recv_bot = self._row(own, row_dim, "recv_bot_dev", False).copy_(recv_bot)
         if t_host is not None:
             import time as _time
-            _ops.PROFILE_HOST_MS.setdefault("halo_exchange", []).append((_time.perf_counter() - t_host) * 1e3)
+            ops.PROFILE_HOST_MS.setdefault("halo_exchange", []).append((_time.perf_counter() - t_host) * 1e3)
         if nccl:
             ev = torch.cuda.Event(enable_timing=ev0 is not None)
             ev.record(side)
             if ev0 is not None:
-                _ops.PROFILE.setdefault("halo_exchange", []).append((ev0, ev))
+                ops.PROFILE.setdefault("halo_exchange", []).append((ev0, ev))
             main.wait_event(ev)                                      # the consuming layer waits for the rows, the host does not
             for t in (recv_top, recv_bot):
                 if t is not None:
@@ -205,7 +208,7 @@ def slab_cost_regularization(layers, comm: HaloComm, vol: Tensor, a: int, b: int
     if vol.shape[1] != top[0] + n + bot[0]:
         raise ValueError(f"slab volume has {vol.shape[1]} rows, expected the window {slab_window(a, b, h)}")
 
-    def refresh(buf: Tensor, L: int, row_dim: int, need_top: bool, need_bot: bool) -> None:
+    def refresh(buf: Tensor, L: int, need_top: bool, need_bot: bool, row_dim: int = 1) -> None:
         """Overwrite the row just above / below the own rows of a level-L buffer with the neighbour's edge row."""
         t, m = top[L], own[L]
         view = buf.narrow(row_dim, t, m)
@@ -215,59 +218,28 @@ def slab_cost_regularization(layers, comm: HaloComm, vol: Tensor, a: int, b: int
         if r_bot is not None:
             buf.narrow(row_dim, t + m, 1).copy_(r_bot)
 
+    def tail(x: Tensor, skip: Tensor, refresh) -> Tensor:  # two layers here: conv11's border rows are exchanged before prob reads them
+        planar = bool(getattr(layers, "conv11_planar", False))
+        x = layers.deconv("conv11", x, skip, planar)
+        refresh(x, 0, True, True, row_dim=2 if planar else 1)
+        return layers.prob(x)
+
+    steps = SimpleNamespace(conv=layers.conv, deconv=lambda name, x, skip: layers.deconv(name, x, skip, False), tail=tail)
     comm.exchanges += 1                                   # conv0's halo rows are valid already: no message (counted as a no-op)
-    c0 = layers.conv("conv0", vol, 1)
-    refresh(c0, 0, 1, True, False)                        # conv1 (stride 2) reads one row above
-    c1 = layers.conv("conv1", c0, 2)
-    refresh(c1, 1, 1, True, True)
-    c2 = layers.conv("conv2", c1, 1)
-    del c1
-    refresh(c2, 1, 1, True, False)
-    c3 = layers.conv("conv3", c2, 2)
-    refresh(c3, 2, 1, True, True)
-    c4 = layers.conv("conv4", c3, 1)
-    del c3
-    refresh(c4, 2, 1, True, False)
-    c5 = layers.conv("conv5", c4, 2)
-    refresh(c5, 3, 1, True, True)
-    x = layers.conv("conv6", c5, 1)
-    del c5
-    refresh(x, 3, 1, False, True)                         # a transposed layer reads one coarse row below
-    x = layers.deconv("conv7", x, c4, False)
-    del c4
-    refresh(x, 2, 1, False, True)
-    x = layers.deconv("conv9", x, c2, False)
-    del c2
-    refresh(x, 1, 1, False, True)
-    planar = bool(getattr(layers, "conv11_planar", False))
-    x = layers.deconv("conv11", x, c0, planar)
-    del c0
-    refresh(x, 0, 2 if planar else 1, True, True)
-    y = layers.prob(x)
+    y = costreg_unet(steps, vol, refresh)
     return y[:, top[0]:top[0] + n]
 
 
-class HipCostRegLayers:
-    """The product layer ops of `slab_cost_regularization`: the split-bf16 matrix-core kernels (csrc/conv3d_sbf.hip) exactly as
-    CostRegNet._run_cl calls them, conv11 writing planar for the prob kernel."""
+class HipCostRegLayers(SplitLayers):
+    """The product layers of `slab_cost_regularization`: CostRegNet's split-bf16 matrix-core kernels (csrc/conv3d_sbf.hip) with the
+    tiled transposed kernels for conv9 / conv11, conv11 writing planar for the exact prob kernel once its border rows are in."""
     conv11_planar = True
 
     def __init__(self, cost_reg):
-        from . import ops
-        self.ops = ops
         if not cost_reg.split_bf16_supported():
             raise RuntimeError("slab-parallel CostRegNet needs the split-bf16 kernels (base channels 8, CDS_CONV_EXACT unset)")
         cost_reg.want_slab_operands()
-        self.p = cost_reg._packed.get(cost_reg, cost_reg._pack)
-        self.cout = {name: getattr(cost_reg, name).conv.out_channels for name in
-                     ("conv0", "conv1", "conv2", "conv3", "conv4", "conv5", "conv6", "conv7", "conv9", "conv11")}
-
-    def conv(self, name: str, x: Tensor, stride: int) -> Tensor:
-        code = self.ops.SBF_PAIR if name == "conv0" else stride
-        return self.ops.conv3d_sbf(x, self.p[name + ".ws"], self.p[name + ".b"], self.cout[name], stride=code)
-
-    def deconv(self, name: str, x: Tensor, skip: Tensor, planar: bool) -> Tensor:
-        return self.ops.deconv3d_sbf(x, self.p[name + ".ws"], self.p[name + ".b"], self.cout[name], skip=skip, out_planar=planar)
+        super().__init__(cost_reg._packed.get(cost_reg, cost_reg._pack), kernels=COSTREG_SLAB_KERNELS)
 
     def prob(self, x: Tensor) -> Tensor:
-        return self.ops.conv3d_k3(x, self.p["prob.w"], None, relu=False)[0]
+        return ops.conv3d_k3(x, self.p["prob.w"], None, relu=False)[0]

@@ -25,6 +25,7 @@ import torch
 
 from . import _lib, _scratch, ops
 from ._lib import check
+from .model import COSTREG_KERNELS, costreg_unet
 
 Tensor = torch.Tensor
 
@@ -340,36 +341,40 @@ def conv_bn_relu3d(unit, x: Tensor, skip: Optional[Tensor] = None, bounds=None) 
     return out if skip is None else skip + out
 
 
-_UNITS = ("conv0", "conv1", "conv2", "conv3", "conv4", "conv5", "conv6", "conv7", "conv9", "conv11")
+class _TrainLayers:
+    """costreg_unet on the autograd ops, batched planar volumes [B,C,D,h,w].  Split-f16 mode keeps one zeroed slot array per call:
+    [0] the cost volume's bound (one absmax launch), then per layer (output bound, output-gradient bound); the BatchNorm passes raise
+    them, the convolutions read them."""
+
+    def __init__(self, cr, x: Tensor):
+        self.cr = cr
+        self.slots = None
+        if get_conv_arithmetic() == "split_f16":
+            self.slots = _scratch.zeros((1 + 2 * len(COSTREG_KERNELS),), torch.float32, x.device)
+            self.in_bound, self.used = self.slots[0:1], 1
+            absmax_bound(x, self.in_bound)
+
+    def _unit(self, name: str, x: Tensor, skip: Optional[Tensor] = None) -> Tensor:
+        unit = getattr(self.cr, name)                              # the holder knows its own stride and direction
+        if self.slots is None:
+            return conv_bn_relu3d(unit, x, skip)
+        out_slot, dy_slot = self.slots[self.used:self.used + 1], self.slots[self.used + 1:self.used + 2]
+        self.used += 2
+        y = conv_bn_relu3d(unit, x, skip, (self.in_bound, out_slot, dy_slot))
+        self.in_bound = out_slot if unit.bn.training else None     # a BatchNorm in eval mode publishes no bound: the next layer measures
+        return y
+
+    def conv(self, name: str, x: Tensor, stride: int) -> Tensor:
+        return self._unit(name, x)
+
+    deconv = _unit
+
+    def tail(self, x: Tensor, skip: Tensor, refresh) -> Tensor:
+        return Conv3dK3.apply(self._unit("conv11", x, skip), self.cr.prob.weight, 1, False)
 
 
 def cost_regularization(cr, x: Tensor) -> Tensor:
     """models/module.py:305-315 on the HIP training ops.  x [B,C,D,h,w] -> [B,1,D,h,w]."""
     if x.shape[2] % 8 or x.shape[3] % 8 or x.shape[4] % 8:
         raise ValueError(f"CostRegNet needs D,h,w divisible by 8, got {tuple(x.shape[2:])}")
-    if get_conv_arithmetic() == "split_f16":
-        # one zeroed slot array per call: [0] the cost volume's bound (one absmax launch), then per layer (output bound, output-gradient
-        # bound); the BatchNorm passes raise them, the convolutions read them
-        slots = _scratch.zeros((1 + 2 * len(_UNITS),), torch.float32, x.device)
-        absmax_bound(x, slots[0:1])
-        bnd = {n: (slots[1 + 2 * i:2 + 2 * i], slots[2 + 2 * i:3 + 2 * i]) for i, n in enumerate(_UNITS)}
-
-        def unit(name, inp, in_bound, skip=None):
-            u = getattr(cr, name)                              # a BatchNorm in eval mode publishes no bound: the next layer measures
-            return conv_bn_relu3d(u, inp, skip, (in_bound,) + bnd[name]), (bnd[name][0] if u.bn.training else None)
-        b = slots[0:1]
-    else:
-        def unit(name, inp, in_bound, skip=None):
-            return conv_bn_relu3d(getattr(cr, name), inp, skip), None
-        b = None
-    c0, b0 = unit("conv0", x, b)
-    c1, b1 = unit("conv1", c0, b0)
-    c2, b2 = unit("conv2", c1, b1)
-    c3, b3 = unit("conv3", c2, b2)
-    c4, b4 = unit("conv4", c3, b3)
-    y, bb = unit("conv5", c4, b4)
-    y, bb = unit("conv6", y, bb)
-    y, bb = unit("conv7", y, bb, skip=c4)
-    y, bb = unit("conv9", y, bb, skip=c2)
-    y, bb = unit("conv11", y, bb, skip=c0)
-    return Conv3dK3.apply(y, cr.prob.weight, 1, False)
+    return costreg_unet(_TrainLayers(cr, x), x)

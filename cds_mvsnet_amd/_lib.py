@@ -155,6 +155,7 @@ SIGNATURES = {
     "cds_colmap_depth_ranges_f64": [P, P, P, P, I, P, P],
     "cds_depth_metrics_f32": [P, P, P, P, F, I, L, I, P, L, P, P],
     "cds_gt_pyramid_f32": [P, P, I, I, I, P, P, I, I, I, P, P, P],
+    "cds_image_batch_u8": [P, I, I, I, P, P, I, I, P, P],
 }
 
 _lib = None

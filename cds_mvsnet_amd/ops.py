@@ -1733,3 +1733,31 @@ def gt_pyramid(depth_src: Tensor, rows, cols, levels: int = 4, mask_src: Optiona
         masks.append(mout[off:off + a * b].view(a, b))
         off += a * b
     return depths, masks
+
+
+def image_batch(src_u8: Tensor, rows, cols) -> Tensor:
+    """Training images from decoded bytes in one launch: src_u8 [n,Hs,Ws,3] uint8 on the device (the images as PIL decodes them);
+    rows [h], cols [w]: source indices in the format of :func:`gt_pyramid` - the two int32 device tensors of :func:`index_tables`
+    (used as they are: an entry outside the source gives 0), or host sequences / arrays / CPU tensors (checked against the source
+    size and uploaded here).  A centre crop is two ``arange`` slices; a loader builds the tables once per dataset.
+    -> [n,3,h,w] float32, ``out[i,c,y,x] = float(src[i,rows[y],cols[x],c]) / 255.0f``: crop, HWC -> CHW and a true division, bit-equal to
+    numpy's ``np.array(img, dtype=np.float32) / 255.`` (include/cds_mvsnet_hip.h: cds_image_batch_u8).  Launches on the current
+    stream; nothing is read back."""
+    if not isinstance(src_u8, torch.Tensor) or src_u8.dim() != 4 or src_u8.shape[3] != 3 or src_u8.numel() == 0:
+        raise ValueError("image_batch: src_u8 must be a non-empty [n,Hs,Ws,3] tensor")
+    ps = _dev_int(src_u8, torch.uint8, "src_u8")
+    n, Hs, Ws = int(src_u8.shape[0]), int(src_u8.shape[1]), int(src_u8.shape[2])
+    dev = src_u8.device
+    on_dev = [isinstance(t, torch.Tensor) and t.is_cuda for t in (rows, cols)]
+    if any(on_dev):
+        if not all(on_dev) or rows.device != dev or cols.device != dev or rows.dim() != 1 or cols.dim() != 1 or \
+                rows.numel() == 0 or cols.numel() == 0:
+            raise ValueError(f"image_batch: device tables must both be non-empty 1-d tensors on {dev} (ops.index_tables)")
+        _dev_int(rows, torch.int32, "rows"), _dev_int(cols, torch.int32, "cols")
+    else:
+        rows, cols = index_tables(rows, cols, Hs, Ws, dev)
+    h, w = int(rows.numel()), int(cols.numel())
+    st = _stream(src_u8)
+    out = torch.empty((n, 3, h, w), dtype=torch.float32, device=dev)
+    check(_lib.load().cds_image_batch_u8(ps, n, Hs, Ws, rows.data_ptr(), cols.data_ptr(), h, w, out.data_ptr(), st), "cds_image_batch_u8")
+    return out

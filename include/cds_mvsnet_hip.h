@@ -830,6 +830,19 @@ int cds_depth_metrics_f32(const float* est, const float* gt, const float* mask, 
 int cds_gt_pyramid_f32(const float* src, const unsigned char* mask_src, int mask_thresh, int Hs, int Ws, const int* rows, const int* cols,
                        int h, int w, int levels, float* depth_out, float* mask_out, void* stream);
 
+/* Training images from decoded bytes (csrc/train_data.hip; reference: datasets/dtu_yao.py:73-77,176, datasets/blended_dataset.py:79-92,165:
+ * np.array(img, float32) / 255., centre crop, stack, transpose(0, 3, 1, 2) on the host).
+ *
+ * cds_image_batch_u8      src [n][Hs][Ws][3] uint8, the decoded images; rows [h], cols [w]: int32 tables on the DEVICE, the format of
+ *                         cds_gt_pyramid_f32 (a centre crop is two ranges).  out [n][3][h][w] fp32:
+ *                           out[i][c][y][x] = (float)src[i][rows[y]][cols[x]][c] / 255.0f
+ *                         - a true fp32 division, bit-equal to numpy's float32 / 255.; a multiplication by 1 / 255.f is not.  A table
+ *                         entry outside the source yields 0.  One launch: a thread owns four consecutive x of one row, reads their
+ *                         12 bytes once and writes the three planes with 16-byte stores when w % 4 == 0 and out is 16-byte aligned,
+ *                         with scalar stores otherwise.  out, rows, cols must be 4-byte aligned. */
+int cds_image_batch_u8(const unsigned char* src, int n, int Hs, int Ws, const int* rows, const int* cols, int h, int w, float* out,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -156,6 +156,8 @@ SIGNATURES = {
     "cds_depth_metrics_f32": [P, P, P, P, F, I, L, I, P, L, P, P],
     "cds_gt_pyramid_f32": [P, P, I, I, I, P, P, I, I, I, P, P, P],
     "cds_image_batch_u8": [P, I, I, I, P, P, I, I, P, P],
+    "cds_eval_views_u8": [P, I, I, I, P, P, P, P, P, P, I, I, P, P],
+    "cds_eval_outputs_f32": [P, I, I, P, I, I, P, I, I, P, I, I, P, I, I, P, P, P],
 }
 
 _lib = None

@@ -2,6 +2,7 @@
 
     python -m cds_mvsnet_amd.infer --testpath <scenes> --testlist <list.txt> --outdir <out> \
         [--resume ckpt.pth] [--refine] [--num_view 5] [--numdepth 192] [--max_h 512 --max_w 640] [--temperature 0.01]
+        [--pipeline gpu [--view_cache_mb 2048]] [--ndepths 48,32,8] [--depth_inter_r 4.0,1.5,0.75]
 
 One process per GPU: with `python -m torch.distributed.run --nproc-per-node N -m cds_mvsnet_amd.infer ...` every rank takes
 the reference views `idx % world == rank` (independent depth maps, no collective).  Outputs follow the reference layout:
@@ -10,6 +11,13 @@ the reference views `idx % world == rank` (independent depth maps, no collective
 with `--filter_method gipuma`, the gipuma-style one (gipuma.py; `--prob_threshold`, `--disp_threshold`, `--num_consistent`).
 `--save_stages` also writes the three stages' own depth maps, `<out>/<scan>/depth_stage{1,2,3}/%08d.pfm`, at their resolutions
 (what evaluations/precision.py scores stage by stage; `python -m cds_mvsnet_amd.depth_eval --folders ...`).
+
+`--pipeline host` (the default) prepares every sample on the host (mvs_io.EvalScenes) and writes its files before the next forward
+starts (mvs_io.save_outputs).  `--pipeline gpu` (eval_data.py) decodes each view once per scan, prepares it on the
+GPU, keeps it in a cache of `--view_cache_mb` MiB, packs the outputs on the GPU and writes them on a thread while the next forward
+runs.  The files are byte-identical for images that need no resize; an image that is not `max_h x max_w` is resized by the
+reference's rule (cv2.resize of the float32 image, INTER_LINEAR, no antialiasing) with `gpu` and by PIL's antialiasing BILINEAR on
+the uint8 image with `host`: the two pipelines then feed the network different pixels.
 """
 from __future__ import annotations
 
@@ -108,22 +116,31 @@ def load_checkpoint(model: torch.nn.Module, path: str, trust_pickle: bool = Fals
                            f"(e.g. {missing[:3]}), {len(unexpected)} unexpected (e.g. {unexpected[:3]})")
 
 
-def run(args) -> float:
-    rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
-    dev = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
-    torch.cuda.set_device(dev)
-    with open(args.testlist) as f:
-        scans = [ln.strip() for ln in f if ln.strip()]
-    data = EvalScenes(args.testpath, scans, nviews=args.num_view, ndepths=args.numdepth,
-                      interval_scale=args.interval_scale, max_h=args.max_h, max_w=args.max_w, refine=args.refine,
-                      dataset=args.dataset)
-    model = CDSMVSNet(refine=args.refine, ndepths=(48, 32, 8), depth_interals_ratio=(4.0, 1.5, 0.75))
+def _triple(kind):
+    """argparse ``type=`` for one value per stage, "a,b,c" -> (a, b, c): a malformed value is a usage error at parse time."""
+    def parse(text: str) -> tuple:
+        try:
+            vals = tuple(kind(x) for x in str(text).split(","))
+        except ValueError:
+            vals = ()
+        if len(vals) != 3:
+            raise argparse.ArgumentTypeError(f"expected three comma-separated {kind.__name__} values (one per stage), got {text!r}")
+        return vals
+    return parse
+
+
+def build_model(args) -> torch.nn.Module:
+    """The model the flags describe, on the host: --refine, --ndepths, --depth_inter_r, then --resume or seeded synthetic weights."""
+    model = CDSMVSNet(refine=args.refine, ndepths=args.ndepths, depth_interals_ratio=args.depth_inter_r)
     if args.resume:
         load_checkpoint(model, args.resume, trust_pickle=args.trust_checkpoint)
     else:
         seeded_init_(model, 0)  # no checkpoint given: deterministic synthetic weights (plumbing runs)
-    model = model.to(dev).eval()
-    last = "stage4" if args.refine else "stage3"
+    return model
+
+
+def _run_host_pipeline(args, model, data, dev, rank, world, last) -> list:
+    """--pipeline host: one sample at a time, prepared on the host, its files written before the next forward starts."""
     times = []
     with torch.no_grad():
         for idx in range(rank, len(data), world):
@@ -148,8 +165,55 @@ def run(args) -> float:
                     os.makedirs(os.path.dirname(p), exist_ok=True)
                     write_pfm(p, out[f"stage{k}"]["depth"][0].float().cpu().numpy())
             print(f"[{rank}] {idx + 1}/{len(data)} {s['filename'].format('depth_est', '.pfm')} {times[-1] * 1e3:.1f} ms", flush=True)
+    return times
+
+
+def _run_gpu_pipeline(args, model, scans, scene_args, dev, rank, world, last) -> list:
+    """--pipeline gpu: EvalViews -> model -> OutputWriter.  Nothing here waits for the device between two forwards; the writer is
+    closed - every byte on disk - before this returns, because the barrier and the fusions that follow read the files back.  The
+    time printed per depth map is host wall time from one sample to the next (the device runs behind it); the average is over the
+    whole loop, after a final synchronisation."""
+    from .eval_data import EvalViews, OutputWriter
+    data = EvalViews(args.testpath, scans, device=dev, cache_mb=args.view_cache_mb, rank=rank, world=world, **scene_args)
+    n = len(data)
+    done = 0
+    torch.cuda.synchronize()
+    t_start = t0 = time.time()
+    with torch.no_grad(), data, OutputWriter(args.outdir) as writer:
+        for s in data:
+            cams = {k: torch.from_numpy(v).unsqueeze(0) for k, v in s["proj_matrices"].items()}
+            dv = torch.from_numpy(s["depth_values"]).unsqueeze(0)
+            out = model(s["imgs"], cams, dv, temperature=args.temperature)
+            writer.submit(s["filename"], out, s["proj_matrices"][last][0], s["imgs"][0, 0], save_stages=args.save_stages)
+            done += 1
+            t1 = time.time()
+            print(f"[{rank}] {data.order[done - 1] + 1}/{len(data.scenes)} {s['filename'].format('depth_est', '.pfm')} "
+                  f"{(t1 - t0) * 1e3:.1f} ms", flush=True)
+            t0 = t1
+        torch.cuda.synchronize()
+    total = time.time() - t_start                             # the writer is closed: the files are on disk
+    print(f"[{rank}] view cache: {data.stats['decodes']} decodes, {data.stats['hits']} hits, {data.stats['evictions']} evictions "
+          f"over {n} depth maps", flush=True)
+    return [total / n] * n if n else []
+
+
+def run(args) -> float:
+    rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
+    dev = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
+    torch.cuda.set_device(dev)
+    with open(args.testlist) as f:
+        scans = [ln.strip() for ln in f if ln.strip()]
+    scene_args = dict(nviews=args.num_view, ndepths=args.numdepth, interval_scale=args.interval_scale, max_h=args.max_h,
+                      max_w=args.max_w, refine=args.refine, dataset=args.dataset)
+    model = build_model(args).to(dev).eval()
+    last = "stage4" if args.refine else "stage3"
+    if args.pipeline == "gpu":
+        times = _run_gpu_pipeline(args, model, scans, scene_args, dev, rank, world, last)
+    else:
+        times = _run_host_pipeline(args, model, EvalScenes(args.testpath, scans, **scene_args), dev, rank, world, last)
     avg = float(np.mean(times)) if times else 0.0
-    print(f"[{rank}] average time: {avg:.4f} s over {len(times)} depth maps")
+    what = "upload + forward" if args.pipeline == "host" else "whole loop, files on disk, per depth map"     # not comparable
+    print(f"[{rank}] average time ({what}): {avg:.4f} s over {len(times)} depth maps")
     if args.fuse:
         # step 2 of the reference's test.py (pcd_filter, test.py:386-396): scans are independent -> shard over ranks
         from .fusion import filter_depth
@@ -191,6 +255,17 @@ def parse_args(argv=None) -> argparse.Namespace:
     ap.add_argument("--max_w", type=int, default=640)
     ap.add_argument("--temperature", type=float, default=0.01)
     ap.add_argument("--dataset", default="dtu", choices=["dtu", "tt", "general"])
+    ap.add_argument("--pipeline", default="host", choices=["host", "gpu"],
+                    help="host: samples prepared and files written on the host, one depth map at a time (PIL antialiasing BILINEAR when "
+                         "an image needs resizing).  gpu: views decoded once per scan, prepared and cached on the GPU, outputs packed on "
+                         "the GPU and written on a thread; an image that needs resizing follows the reference's cv2.resize "
+                         "INTER_LINEAR rule instead, so the two pipelines DIFFER for such images and agree byte for byte otherwise")
+    ap.add_argument("--view_cache_mb", type=float, default=2048.0,
+                    help="--pipeline gpu: device memory for prepared views, in MiB (one view is 12 * max_h * max_w bytes)")
+    ap.add_argument("--ndepths", type=_triple(int), default=(48, 32, 8), metavar="a,b,c",
+                    help="depth hypotheses per stage (the reference's --ndepths; default 48,32,8)")
+    ap.add_argument("--depth_inter_r", type=_triple(float), default=(4.0, 1.5, 0.75), metavar="a,b,c",
+                    help="depth interval ratio per stage (the reference's --depth_inter_r; default 4.0,1.5,0.75)")
     ap.add_argument("--save_stages", action="store_true",
                     help="also write depth_stage{1,2,3}/%%08d.pfm: the depth map of each stage at its own resolution")
     ap.add_argument("--fuse", action="store_true", help="filter + fuse the saved depth maps into <outdir>/<scan>.ply")

@@ -1761,3 +1761,71 @@ def image_batch(src_u8: Tensor, rows, cols) -> Tensor:
     out = torch.empty((n, 3, h, w), dtype=torch.float32, device=dev)
     check(_lib.load().cds_image_batch_u8(ps, n, Hs, Ws, rows.data_ptr(), cols.data_ptr(), h, w, out.data_ptr(), st), "cds_image_batch_u8")
     return out
+
+
+def _eval_table(t, dtype: torch.dtype, n: int, dev, what: str) -> int:
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.device == dev and t.dtype == dtype and t.dim() == 1 and t.is_contiguous()):
+        raise ValueError(f"{what}: expected a contiguous 1-d {dtype} tensor on {dev}")
+    if int(t.numel()) != n:
+        raise ValueError(f"{what}: table has {int(t.numel())} entries, expected {n}")
+    return t.data_ptr()
+
+
+def eval_views(src_u8: Tensor, rows, cols) -> Tensor:
+    """Evaluation views from decoded bytes in one launch: src_u8 [V,Hs,Ws,3] uint8 on the device (the views as PIL decodes them);
+    rows = (row0 [h] int32, row1 [h] int32, fy [h] float32), cols = (col0 [w], col1 [w], fx [w]): the tap tables of OpenCV's float32
+    INTER_LINEAR on the device (``eval_data.view_tables`` builds, uploads and caches them; an edge padding of the rows is a clamp
+    inside the row tables).  -> [V,3,h,w] float32: ``/ 255.0f`` (a true division), horizontal pass ``S[s0] * (1 - fx) + S[s1] * fx``,
+    vertical pass ``R0 * (1 - fy) + R1 * fy``, every operation rounded on its own, HWC -> CHW (include/cds_mvsnet_hip.h:
+    cds_eval_views_u8).  With every weight 0 the result is exactly ``u8 / 255``.  Launches on the current stream; nothing is read back."""
+    if not isinstance(src_u8, torch.Tensor) or src_u8.dim() != 4 or src_u8.shape[3] != 3 or src_u8.numel() == 0:
+        raise ValueError("eval_views: src_u8 must be a non-empty [V,Hs,Ws,3] tensor")
+    ps = _dev_int(src_u8, torch.uint8, "eval_views: src_u8")
+    V, Hs, Ws = int(src_u8.shape[0]), int(src_u8.shape[1]), int(src_u8.shape[2])
+    dev = src_u8.device
+    if len(rows) != 3 or len(cols) != 3 or not all(isinstance(t, torch.Tensor) and t.dim() == 1 for t in tuple(rows) + tuple(cols)):
+        raise ValueError("eval_views: rows and cols must each be three 1-d device tensors (tap 0, tap 1, weight)")
+    h, w = int(rows[0].numel()), int(cols[0].numel())
+    if h == 0 or w == 0:
+        raise ValueError("eval_views: empty tables")
+    p = [_eval_table(t, dt, n, dev, f"eval_views: {nm}") for t, dt, n, nm in
+         ((rows[0], torch.int32, h, "row0"), (rows[1], torch.int32, h, "row1"), (rows[2], torch.float32, h, "fy"),
+          (cols[0], torch.int32, w, "col0"), (cols[1], torch.int32, w, "col1"), (cols[2], torch.float32, w, "fx"))]
+    st = _stream(src_u8)
+    out = torch.empty((V, 3, h, w), dtype=torch.float32, device=dev)
+    check(_lib.load().cds_eval_views_u8(ps, V, Hs, Ws, *p, h, w, out.data_ptr(), st), "cds_eval_views_u8")
+    return out
+
+
+def eval_outputs(confs, img: Tensor, tab: Tensor, h: int, w: int) -> Tuple[Tensor, Tensor]:
+    """The side outputs of one depth map in one launch: confs = the three stage confidence maps [Hk,Wk] float32, img [3,H,W] float32
+    (the reference view), all on one device; tab: int32 [4 h + 4 w] on that device - for c1, c2, c3, img in turn the source row of
+    every output row, then the source column of every output column (``eval_data.output_tables``: ``mvs_io.nearest_resize``'s rule).
+    -> (conf3 [h,w,3] float32, img_u8 [h,w,3] uint8 = ``uint8(clip(img * 255.0f, 0, 255))``), what ``mvs_io.save_outputs`` computes
+    on the host (include/cds_mvsnet_hip.h: cds_eval_outputs_f32).  Launches on the current stream; nothing is read back."""
+    if len(confs) != 3:
+        raise ValueError("eval_outputs: confs must be the three stage confidence maps")
+    if not isinstance(img, torch.Tensor) or img.dim() != 3 or img.shape[0] != 3 or img.numel() == 0:
+        raise ValueError("eval_outputs: img must be a non-empty [3,H,W] tensor")
+    dev = img.device
+    ptrs, dims = [], []
+    for k, c in enumerate(tuple(confs) + (img,)):
+        name = f"conf{k + 1}" if k < 3 else "img"
+        if not (isinstance(c, torch.Tensor) and c.is_cuda and c.device == dev and c.dtype == torch.float32 and c.is_contiguous()):
+            raise ValueError(f"eval_outputs: {name} must be a contiguous float32 tensor on {dev}")
+        if k < 3 and (c.dim() != 2 or c.numel() == 0):
+            raise ValueError(f"eval_outputs: {name} must be a non-empty [H,W] map")
+        ptrs.append(c.data_ptr())
+        dims.append((int(c.shape[-2]), int(c.shape[-1])))
+    h, w = int(h), int(w)
+    if h < 1 or w < 1:
+        raise ValueError("eval_outputs: h and w must be positive")
+    pt = _eval_table(tab, torch.int32, 4 * h + 4 * w, dev, "eval_outputs: tab")
+    st = _stream(img)
+    conf3 = torch.empty((h, w, 3), dtype=torch.float32, device=dev)
+    img_u8 = torch.empty((h, w, 3), dtype=torch.uint8, device=dev)
+    args = []
+    for p, (a, b) in zip(ptrs, dims):
+        args += [p, a, b]
+    check(_lib.load().cds_eval_outputs_f32(*args, pt, h, w, conf3.data_ptr(), img_u8.data_ptr(), st), "cds_eval_outputs_f32")
+    return conf3, img_u8

@@ -361,7 +361,85 @@ def _align(n: int, a: int = 256) -> int:
     return (n + a - 1) // a * a
 
 
-class TrainBatches:
+class DecodeAhead:
+    """What :class:`TrainBatches` and ``eval_data.EvalViews`` share: the decode pool, the ring of staging-buffer events and the
+    iterator's life cycle - ONE copy of the rules that keep a staging buffer from being refilled while a copy still reads it.
+
+    ``_start(fn, *args)`` runs one decode, on the pool (created on first use: ``threads`` workers, at most 16, never sized from the
+    machine's CPU count) or, with ``ahead=0``, at once on the caller's thread; either way the result or the exception is in the
+    returned future.  ``_record(s)`` marks, on the caller's current stream, the end of the copy that reads staging buffer ``s``;
+    ``_wait(s)`` makes the host wait for it, and must precede every refill of that buffer.  ``close()``, exhaustion, an exception and
+    ``__del__`` shut the pool down; a worker never waits on a queue, so none can be left blocked.  A subclass keeps its scheduled
+    work in ``self._pending`` and says in ``_futures`` which futures that holds."""
+
+    def __init__(self, threads: int, ahead: int, name: str):
+        self.ahead, self.threads = int(ahead), int(threads)
+        if self.ahead < 0 or not 1 <= self.threads <= MAX_THREADS:
+            raise ValueError(f"{type(self).__name__}: ahead must be >= 0 and threads 1..{MAX_THREADS}, got {ahead}, {threads}")
+        self._pool_name = name
+        self._pool: Optional[ThreadPoolExecutor] = None
+        self._events: List[Optional["torch.cuda.Event"]] = [None] * (self.ahead + 1)
+        self._pending: Dict[int, object] = {}
+        self._scheduled = 0
+        self._k = 0
+        self._closed = False
+        self._lock = threading.Lock()
+
+    def __iter__(self):
+        return self
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc) -> bool:
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:                                     # interpreter shutdown
+            pass
+
+    def _futures(self, pending) -> List[Future]:
+        raise NotImplementedError
+
+    def close(self) -> None:
+        """Drop what has not started, wait for the (finite) decodes that have, join the workers.  Idempotent."""
+        with self._lock:
+            self._closed = True
+            pool, self._pool = self._pool, None
+            pending, self._pending = self._pending, {}
+        for f in self._futures(pending):
+            f.cancel()
+        if pool is not None:
+            pool.shutdown(wait=True, cancel_futures=True)
+
+    def _start(self, fn, *args) -> Future:
+        if self.ahead > 0:
+            if self._pool is None:
+                self._pool = ThreadPoolExecutor(max_workers=self.threads, thread_name_prefix=self._pool_name)
+            return self._pool.submit(fn, *args)
+        f: Future = Future()
+        try:
+            f.set_result(fn(*args))
+        except Exception as e:
+            f.set_exception(e)
+        return f
+
+    def _wait(self, s: int) -> None:
+        ev = self._events[s]
+        if ev is not None:                                    # the copy that last read this buffer must have finished
+            ev.synchronize()
+            self._events[s] = None
+
+    def _record(self, s: int) -> None:
+        ev = torch.cuda.Event()
+        ev.record()
+        self._events[s] = ev
+
+
+class TrainBatches(DecodeAhead):
     """One epoch of ``train.train_step`` samples from a :class:`DTUTrainScenes` / :class:`BlendedTrainScenes`, an iterator.
 
     Order: :func:`epoch_batches` (``shuffle`` and ``drop_last`` default to the dataset's train mode, as in the reference's loaders).
@@ -393,49 +471,14 @@ class TrainBatches:
         train = dataset.mode == "train"
         self.batches = epoch_batches(len(dataset), self.batch_size, dataset.seed, self.epoch, train if shuffle is None else bool(shuffle),
                                      train if drop_last is None else bool(drop_last), rank, world)
-        self.ahead = int(ahead)
-        self.threads = int(threads)
-        if self.ahead < 0 or not 1 <= self.threads <= MAX_THREADS:
-            raise ValueError(f"TrainBatches: ahead must be >= 0 and threads 1..{MAX_THREADS}, got {ahead}, {threads}")
-        self._pool: Optional[ThreadPoolExecutor] = None
+        super().__init__(threads, ahead, "cds-decode")
         self._ring: List[Optional[dict]] = [None] * (self.ahead + 1)
-        self._events: List[Optional["torch.cuda.Event"]] = [None] * (self.ahead + 1)
-        self._pending: Dict[int, List[Future]] = {}
-        self._scheduled = 0
-        self._k = 0
-        self._closed = False
-        self._lock = threading.Lock()
 
     def __len__(self) -> int:
         return len(self.batches)
 
-    def __iter__(self) -> "TrainBatches":
-        return self
-
-    def __enter__(self) -> "TrainBatches":
-        return self
-
-    def __exit__(self, *exc) -> bool:
-        self.close()
-        return False
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:                                     # interpreter shutdown
-            pass
-
-    def close(self) -> None:
-        """Drop what has not started, wait for the (finite) decodes that have, join the workers.  Idempotent."""
-        with self._lock:
-            self._closed = True
-            pool, self._pool = self._pool, None
-            pending, self._pending = self._pending, {}
-        for futs in pending.values():
-            for f in futs:
-                f.cancel()
-        if pool is not None:
-            pool.shutdown(wait=True, cancel_futures=True)
+    def _futures(self, pending) -> List[Future]:
+        return [f for futs in pending.values() for f in futs]
 
     # -- staging ---------------------------------------------------------------------------------------------------
     def _slot(self, s: int) -> dict:
@@ -468,25 +511,12 @@ class TrainBatches:
                     if not os.path.isfile(path):
                         raise FileNotFoundError(f"{path}: not found (sample {i} of {self.dataset.listfile})")
             s = j % (self.ahead + 1)
-            ev = self._events[s]
-            if ev is not None:                                # the copy that last read this buffer must have finished
-                ev.synchronize()
-                self._events[s] = None
+            self._wait(s)
             slot = self._slot(s)
             futs = []
             for b, i in enumerate(idx):
                 out = (slot["imgs"][b], slot["depth"][b], slot["mask"][b] if slot["mask"] is not None else None)
-                if self.ahead > 0:
-                    if self._pool is None:
-                        self._pool = ThreadPoolExecutor(max_workers=self.threads, thread_name_prefix="cds-decode")
-                    futs.append(self._pool.submit(self.dataset.load, i, self.epoch, out))
-                else:
-                    f: Future = Future()
-                    try:
-                        f.set_result(self.dataset.load(i, self.epoch, out))
-                    except Exception as e:
-                        f.set_exception(e)
-                    futs.append(f)
+                futs.append(self._start(self.dataset.load, i, self.epoch, out))
             self._pending[j] = futs
             self._scheduled += 1
 
@@ -517,9 +547,7 @@ class TrainBatches:
                 img_tab = self._tables("img", Hs, Ws)
                 gt_tab = self._tables("gt", Hg, Wg)
                 staged = slot["buf"].to(dev, non_blocking=True)             # the one copy, on the current stream
-                ev = torch.cuda.Event()
-                ev.record()
-                self._events[k % (self.ahead + 1)] = ev
+                self._record(k % (self.ahead + 1))
                 n_img, n_gt = self.batch_size * N * Hs * Ws * 3, self.batch_size * Hg * Wg
                 u8 = staged[:n_img].view(self.batch_size * N, Hs, Ws, 3)[:B * N]
                 imgs = ops.image_batch(u8, img_tab[0], img_tab[1])

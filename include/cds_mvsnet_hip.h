@@ -843,6 +843,30 @@ int cds_gt_pyramid_f32(const float* src, const unsigned char* mask_src, int mask
 int cds_image_batch_u8(const unsigned char* src, int n, int Hs, int Ws, const int* rows, const int* cols, int h, int w, float* out,
                        void* stream);
 
+/* Evaluation views from decoded bytes and the side outputs of a depth map (csrc/eval_data.hip; reference: datasets/general_eval.py:88-118
+ * - float32 / 255., the Tanks & Temples edge padding, cv2.resize(INTER_LINEAR) of the float32 image - and test.py:216-248).
+ *
+ * cds_eval_views_u8       src [V][Hs][Ws][3] uint8, the decoded views; row0, row1 [h] and col0, col1 [w]: int32 tap tables, fy [h] and
+ *                         fx [w]: fp32 weights of the second tap, all on the DEVICE (the host builds them by OpenCV's rule; the edge
+ *                         padding is a clamp inside the row tables).  out [V][3][h][w] fp32, with S = (float)src / 255.0f (a true
+ *                         division):
+ *                           R_k = S[row_k][col0] * (1.f - fx) + S[row_k][col1] * fx        k = 0, 1
+ *                           out = R_0 * (1.f - fy) + R_1 * fy
+ *                         every operation rounded to fp32 on its own (no FMA): numpy float32 arithmetic reproduces it bit for bit,
+ *                         and fx = fy = 0 gives u8 / 255 exactly.  Tap indices are clamped to the source.  One launch; a thread owns
+ *                         four consecutive x of one row and writes 16-byte stores when w % 4 == 0 and out is 16-byte aligned.
+ *                         Tables and out must be 4-byte aligned.
+ * cds_eval_outputs_f32    c1 [H1][W1], c2 [H2][W2], c3 [H3][W3]: the stage confidences; img [3][Hi][Wi]: the reference image.
+ *                         tab: int32 on the DEVICE, source rows of c1, c2, c3, img for each output row ([h] each), then source columns
+ *                         ([w] each) - nearest-neighbour tables built on the host, clamped to the sources here.
+ *                         conf3 [h][w][3] = the three confidences; img_u8 [h][w][3] = (uint8)clip(img * 255.0f, 0, 255): one rounded
+ *                         fp32 multiply, then truncation.  One launch. */
+int cds_eval_views_u8(const unsigned char* src, int V, int Hs, int Ws, const int* row0, const int* row1, const float* fy, const int* col0,
+                      const int* col1, const float* fx, int h, int w, float* out, void* stream);
+int cds_eval_outputs_f32(const float* c1, int H1, int W1, const float* c2, int H2, int W2, const float* c3, int H3, int W3,
+                         const float* img, int Hi, int Wi, const int* tab, int h, int w, float* conf3, unsigned char* img_u8,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,6 +18,9 @@
 int cds_conv3d_zmg_dispatch(const float* x, const void* wsp, const float* bias, float* out, int Cin, int Cout, int D, int H, int W,
                             int stride, int pair, int act, hipStream_t st, const float* in_bound = nullptr, float w_inv = 1.f,
                             float* out_bound = nullptr);
+// deconv3d_zm.hip: the z-marching split-f16 kernel of conv7 (64 -> 32 transposed) behind cds_deconv3d_sf16_f32, same convention
+int cds_deconv3d_zm64_dispatch(const float* x, const void* wsp, const float* bias, const float* skip, float* out, int Cin, int Cout,
+                               int D, int H, int W, int act, hipStream_t st, const float* in_bound, float w_inv, float* out_bound);
 
 // native 4-float vector (volatile-loadable, unlike HIP's float4 struct): pins a 16-byte LDS read
 using cds_f4 = float __attribute__((ext_vector_type(4)));

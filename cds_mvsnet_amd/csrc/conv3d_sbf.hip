@@ -998,11 +998,18 @@ extern "C" int cds_conv3d_sf16_f32(const float* x, const void* weight_split, con
 
 // The transposed convolution to Cout = 32 (conv7 of CostRegNet) in SPLIT-F16 arithmetic: weight_split from
 // ops.split_pack_deconv3d(..., f16=True), w_inv_scale = 1 / its weight scale, in_bound / out_bound as in cds_conv3d_sf16_f32.
+// Large volumes run on the z-marching kernel of deconv3d_zm.hip, small ones on the tiled kernel here: the same operand and the
+// same results bit for bit.
 extern "C" int cds_deconv3d_sf16_f32(const float* x, const void* weight_split, const float* bias, const float* skip, float* out, int Cin,
                                      int Cout, int D, int H, int W, int act, const float* in_bound, float w_inv_scale, float* out_bound,
                                      void* stream) {
   if (!x || !weight_split || !out || !in_bound || Cin < 8 || (Cin % 8) || Cout != 32 || D < 1 || H < 1 || W < 1 || !(w_inv_scale > 0.f))
     return CDS_EINVAL;
+  {   // the z-marching class-per-wave kernel (deconv3d_zm.hip) where the volume fills the chip (CDS_DZM_DEEP)
+    const int r = cds_deconv3d_zm64_dispatch(x, weight_split, bias, skip, out, Cin, Cout, D, H, W, act, (hipStream_t)stream, in_bound,
+                                             w_inv_scale, out_bound);
+    if (r != CDS_ZMG_UNSUPPORTED) return r;
+  }
   // few tiles (the cascade stages): one 16-cout block per workgroup, two workgroups per tile
   const long tiles = (long)cds_ceil_div(W, 32) * cds_ceil_div(H, 4) * D;
   if (tiles <= cds_env_int("CDS_SBF_YSPLIT_TILES", 256) && !cds_env_is("CDS_SBF_YSPLIT", '0'))

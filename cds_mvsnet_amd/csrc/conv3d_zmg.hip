@@ -458,8 +458,10 @@ int cds_conv3d_zmg_dispatch(const float* x, const void* wsp, const float* bias, 
       return launch_zmg<ZG<1, 2, 1, false, 32, 8, 1, 1, 8, true>>(x, wsp, bias, out, Cout, D, H, W, act, st, in_bound, w_inv, out_bound);
     if (stride == 2 && Cin == 8 && Cout == 16)
       return launch_zmg<ZG<2, 1, 1, false, 16, 8, 1, 1, 8, true>>(x, wsp, bias, out, Cout, D, H, W, act, st, in_bound, w_inv, out_bound);
+    // conv3: both rounds of weights in one wave (RPW = 2: 112 registers of two fp16 terms, 162 VGPRs) instead of the K split over wave
+    // pairs that three bf16 terms need: no exchange through LDS and no finalising step (profiles/zmarch_conv7.md: 180-183 -> 157-162 us)
     if (stride == 2 && Cin == 16 && Cout == 32)
-      return launch_zmg<ZG<2, 2, 2, false, 16, 4, 1, 1, 8, true>>(x, wsp, bias, out, Cout, D, H, W, act, st, in_bound, w_inv, out_bound);
+      return launch_zmg<ZG<2, 2, 2, false, 16, 4, 1, 1, 8, true, 2>>(x, wsp, bias, out, Cout, D, H, W, act, st, in_bound, w_inv, out_bound);
     // The deep stride-1 layers (conv4 32 -> 32, conv6 64 -> 64).  CDS_ZMG_DEEP (A/B knob): 0 = tiled kernels, 1 = z-march where
     // columns x segments fill the 256 CUs (the few tiles of the cascade stages' deep layers stay on the tiled kernels and their
     // cout split), 2 = z-march whatever the size.

@@ -16,10 +16,10 @@
 
 namespace {
 
-template <int ROUNDS_>
+template <int ROUNDS_, int TY_ = 8>
 struct DZC {
   static constexpr int ROUNDS = ROUNDS_;
-  static constexpr int TX = 16, TY = 8;                 // cells per plane: one N-tile per cell row
+  static constexpr int TX = 16, TY = TY_;               // cells per plane: one N-tile per cell row
   static constexpr int IX = TX + 1, IY = TY + 1, IXP = 18;
   static constexpr int ROUNDB = IY * IXP * POSB;
   static constexpr int SLOTB = ROUNDS * ROUNDB;         // one input cell plane: [round][row][col][term][8] bf16
@@ -29,6 +29,59 @@ struct DZC {
   static constexpr int NITEM = IY * IX * ROUNDS;
   static constexpr int IPT = (NITEM + PW * 64 - 1) / (PW * 64);
 };
+
+// The producer waves of a column (X0, Y0) marching over the cell planes [a0, a1): load, split and deposit plane a + 2 while the
+// consumers work on planes a and a + 1; out-of-volume cells are zeros.  One barrier per cell plane, matched by the consumers.
+template <class C, bool F16>
+__device__ __forceinline__ void dzm_produce(const float* __restrict__ x, unsigned char* lds, int ptid, int X0, int Y0, int D, int H, int W,
+                                            int a0, int a1, float xs) {
+  constexpr int ROUNDS = C::ROUNDS, Cin = 8 * ROUNDS;
+  __builtin_amdgcn_s_setprio(3);               // A/B at M1: producers at 0 / 1 / 3: 355 / 351 / 345 us
+  int s_src[C::IPT], s_dst[C::IPT];
+#pragma unroll
+  for (int h = 0; h < C::IPT; ++h) {
+    const int it = h * C::PW * 64 + ptid;
+    const int rd = it % ROUNDS, p = it / ROUNDS;
+    const int row = p / C::IX, c = p - row * C::IX;
+    const int gy = Y0 + row, gx = X0 + c;
+    const bool ok = it < C::NITEM && gy < H && gx < W;
+    s_src[h] = ok ? ((gy * W + gx) * Cin + rd * 8) : -1;
+    s_dst[h] = it < C::NITEM ? rd * C::ROUNDB + (row * C::IXP + c) * POSB : -1;
+  }
+  float4 va[C::IPT], vb[C::IPT];
+  auto issue = [&](int plane) {
+    const bool pok = plane < D;
+    const float* __restrict__ xp = x + (size_t)min(plane, D - 1) * H * W * Cin;
+#pragma unroll
+    for (int h = 0; h < C::IPT; ++h) {
+      const bool ok = pok && s_src[h] >= 0;
+      const float* src = xp + (ok ? s_src[h] : 0);
+      const float4 a = *reinterpret_cast<const float4*>(src), b = *reinterpret_cast<const float4*>(src + 4);
+      va[h] = ok ? a : make_float4(0.f, 0.f, 0.f, 0.f);
+      vb[h] = ok ? b : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+  };
+  auto deposit = [&](int plane) {
+    unsigned char* base = lds + (plane % C::NSLOT) * C::SLOTB;
+#pragma unroll
+    for (int h = 0; h < C::IPT; ++h)
+      if (s_dst[h] >= 0) {
+        if (F16) split_store8_f16(base + s_dst[h], va[h], vb[h], xs);
+        else split_store8(base + s_dst[h], va[h], vb[h]);
+      }
+  };
+  issue(a0);
+  deposit(a0);
+  issue(a0 + 1);
+  deposit(a0 + 1);
+  issue(a0 + 2);
+  __syncthreads();                                  // #0: planes a0, a0 + 1 staged
+  for (int a = a0; a < a1; ++a) {
+    deposit(a + 2);                                 // slot of plane a - 1, which nobody reads any more
+    issue(a + 3);
+    __syncthreads();
+  }
+}
 
 // F16: split-f16 arithmetic (sbf_common.hpp): two fp16 terms, three products per K-step, tensor scales from device bounds.
 template <int ROUNDS, bool F16>
@@ -40,7 +93,7 @@ __global__ __launch_bounds__((DZC<ROUNDS>::THREADS), 3) void deconv3d_zm_kernel(
   constexpr int NT = F16 ? 2 : 3;
   const float xs = F16 ? sf16_scale(in_bound[0]) : 1.0f;
   const float out_mul = F16 ? w_inv / xs : 1.0f;
-  constexpr int Cin = 8 * ROUNDS, Cout = 16;
+  constexpr int Cout = 16;
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -54,53 +107,7 @@ __global__ __launch_bounds__((DZC<ROUNDS>::THREADS), 3) void deconv3d_zm_kernel(
   const int Ho = 2 * H, Wo = 2 * W;
 
   if (wave >= C::CW) {
-    // ============================== producers ==============================
-    __builtin_amdgcn_s_setprio(3);               // A/B at M1: producers at 0 / 1 / 3: 355 / 351 / 345 us
-    const int ptid = tid - C::CW * 64;
-    int s_src[C::IPT], s_dst[C::IPT];
-#pragma unroll
-    for (int h = 0; h < C::IPT; ++h) {
-      const int it = h * C::PW * 64 + ptid;
-      const int rd = it % ROUNDS, p = it / ROUNDS;
-      const int row = p / C::IX, c = p - row * C::IX;
-      const int gy = Y0 + row, gx = X0 + c;
-      const bool ok = it < C::NITEM && gy < H && gx < W;
-      s_src[h] = ok ? ((gy * W + gx) * Cin + rd * 8) : -1;
-      s_dst[h] = it < C::NITEM ? rd * C::ROUNDB + (row * C::IXP + c) * POSB : -1;
-    }
-    float4 va[C::IPT], vb[C::IPT];
-    auto issue = [&](int plane) {
-      const bool pok = plane < D;
-      const float* __restrict__ xp = x + (size_t)min(plane, D - 1) * H * W * Cin;
-#pragma unroll
-      for (int h = 0; h < C::IPT; ++h) {
-        const bool ok = pok && s_src[h] >= 0;
-        const float* src = xp + (ok ? s_src[h] : 0);
-        const float4 a = *reinterpret_cast<const float4*>(src), b = *reinterpret_cast<const float4*>(src + 4);
-        va[h] = ok ? a : make_float4(0.f, 0.f, 0.f, 0.f);
-        vb[h] = ok ? b : make_float4(0.f, 0.f, 0.f, 0.f);
-      }
-    };
-    auto deposit = [&](int plane) {
-      unsigned char* base = lds + (plane % C::NSLOT) * C::SLOTB;
-#pragma unroll
-      for (int h = 0; h < C::IPT; ++h)
-        if (s_dst[h] >= 0) {
-          if (F16) split_store8_f16(base + s_dst[h], va[h], vb[h], xs);
-          else split_store8(base + s_dst[h], va[h], vb[h]);
-        }
-    };
-    issue(a0);
-    deposit(a0);
-    issue(a0 + 1);
-    deposit(a0 + 1);
-    issue(a0 + 2);
-    __syncthreads();                                  // #0: planes a0, a0 + 1 staged
-    for (int a = a0; a < a1; ++a) {
-      deposit(a + 2);                                 // slot of plane a - 1, which nobody reads any more
-      issue(a + 3);
-      __syncthreads();
-    }
+    dzm_produce<C, F16>(x, lds, tid - C::CW * 64, X0, Y0, D, H, W, a0, a1, xs);
     return;
   }
 
@@ -182,7 +189,161 @@ __global__ __launch_bounds__((DZC<ROUNDS>::THREADS), 3) void deconv3d_zm_kernel(
   if (F16) sf16_publish_bound(amax, out_bound);
 }
 
+
+// conv7 of CostRegNet: the same transposed convolution at 64 -> 32 (+ BN shift, ReLU, residual), split-f16 only, as a sibling of the
+// kernel above.  What differs: (1) the matrix operand is the tiled kernel's (ops.split_pack_deconv3d(w, f16=True), DTab<false> in
+// conv3d_sbf.hip: 9 K-steps per round, K-slot g of class c = its g-th tap in (dz, dy, dx) order, so the lane groups of one K-step read
+// different cell offsets INCLUDING dz; class 7 alone has a second K-step, its four dz = 1 taps), so the model keeps one packing of the
+// layer for both kernels; (2) a column is 16 x 4 cells with all eight rounds resident (3 x 34 560 B of LDS); (3) the two 16-cout blocks
+// are two workgroups of a column (gridDim.y): a wave's weights are 8 rounds x 2 terms x 4 = 64 VGPRs, 128 for class 7 - both blocks in
+// one workgroup would be 256 for that wave.  The column's input is then staged twice, the second time from L2 / the memory-side cache.
+constexpr int DZM64_W1L = 2;                          // rounds of class 7's second operand kept in LDS (1 KB per round and term)
+__global__ __launch_bounds__((DZC<8, 4>::THREADS), 3) void deconv3d_zm64_kernel(
+    const float* __restrict__ x, const uint4* __restrict__ wsp, const float* __restrict__ bias, const float* __restrict__ skip,
+    float* __restrict__ out, int D, int H, int W, int tiles_x, int ncols, int seg_len, int act, const float* __restrict__ in_bound,
+    float w_inv, float* __restrict__ out_bound) {
+  using C = DZC<8, 4>;
+  constexpr int ROUNDS = 8, Cout = 32, NKS = 9, W1L = DZM64_W1L;
+  const float xs = sf16_scale(in_bound[0]);
+  const float out_mul = w_inv / xs;
+  extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wg = cds_xcd_remap(blockIdx.x, gridDim.x);
+  const int mbtot = gridDim.y, mb0 = blockIdx.y;      // this workgroup's 16-cout block
+  const int col = wg % ncols, seg = wg / ncols;
+  const int tx_i = col % tiles_x, ty_i = col / tiles_x;
+  const int a0 = seg * seg_len, a1 = min(D, a0 + seg_len);
+  if (a0 >= a1) return;
+  const int X0 = tx_i * C::TX, Y0 = ty_i * C::TY;
+  const int Ho = 2 * H, Wo = 2 * W;
+
+  if (wave >= C::CW) {
+    dzm_produce<C, true>(x, lds, tid - C::CW * 64, X0, Y0, D, H, W, a0, a1, xs);
+    return;
+  }
+
+  // ============================== consumers: wave = parity class ==============================
+  const int pz = wave >> 2, py = (wave >> 1) & 1, px = wave & 1;
+  const bool two = wave == 7;                         // the class with eight taps: a second K-step per round
+  if (two) __builtin_amdgcn_s_setprio(1);
+  const int j = lane & 15, g = lane >> 4;
+  // K-step `wave` of every round; class 7: and K-step 8, whose last W1L rounds wait in LDS behind the ring (written and read by this
+  // wave alone): with all 128 weight registers the wave spilled 10 VGPRs at the 168 that three waves per SIMD leave it
+  BV w0[ROUNDS][2], w1[ROUNDS - W1L][2];
+  unsigned char* w1l = lds + C::LDS + lane * 16;
+  {
+    const uint4* __restrict__ wp = wsp + lane;
+#pragma unroll
+    for (int rd = 0; rd < ROUNDS; ++rd)
+#pragma unroll
+      for (int k = 0; k < 2; ++k) {
+        w0[rd][k].u = wp[(size_t)(((rd * NKS + wave) * mbtot + mb0) * 3 + k) * 64];
+        const uint4 v = wp[(size_t)(((rd * NKS + (two ? 8 : wave)) * mbtot + mb0) * 3 + k) * 64];
+        if (rd < ROUNDS - W1L) w1[rd][k].u = v;
+        else if (two) *reinterpret_cast<uint4*>(w1l + ((rd - (ROUNDS - W1L)) * 2 + k) * 1024) = v;
+      }
+  }
+  const float4 bv = bias ? *reinterpret_cast<const float4*>(bias + mb0 * 16 + 4 * g) : make_float4(0.f, 0.f, 0.f, 0.f);
+  // tap slot g of this class -> cell offset (DTab<false>::tap_d); a slot past the class's taps has zero weights and reads offset 0.
+  // Class 7's second K-step is its first one a cell plane up.
+  const int ny = 1 + py, nx = 1 + px;
+  const bool live = g < (1 + pz) * ny * nx;
+  const int dz = live ? g / (ny * nx) : 0, dy = live ? (g / nx) % ny : 0, dx = live ? g % nx : 0;
+  const int b_off = ((dy * C::IXP) + j + dx) * POSB;
+  const int xv = 2 * (X0 + j) + px;
+  const bool x_ok = X0 + j < W;
+  const size_t zstride = (size_t)Ho * Wo * Cout;
+  const int nrows = min(C::TY, H - Y0);
+  float amax = 0.f;                                   // running maximum of the magnitudes this lane stores
+  __syncthreads();                                    // #0
+  for (int a = a0; a < a1; ++a) {
+    const unsigned char* p0 = lds + (a % C::NSLOT) * C::SLOTB + b_off;
+    const unsigned char* hi = lds + ((a + 1) % C::NSLOT) * C::SLOTB + b_off;
+    const unsigned char* lo = dz ? hi : p0;
+    const size_t zbase = (size_t)(2 * a + pz) * zstride;
+    float4 skn = make_float4(0.f, 0.f, 0.f, 0.f);
+    auto row_off = [&](int n) { return ((size_t)(2 * (Y0 + n) + py) * Wo + xv) * Cout + mb0 * 16 + 4 * g; };
+    if (skip && x_ok) skn = *reinterpret_cast<const float4*>(skip + zbase + row_off(0));
+    asm volatile("" ::"v"(skn.x), "v"(skn.y), "v"(skn.z), "v"(skn.w));   // (see the row loop of the kernel above)
+    for (int n = 0; n < nrows; ++n) {
+      const float4 sk = skn;
+      if (skip && x_ok && n + 1 < nrows) skn = *reinterpret_cast<const float4*>(skip + zbase + row_off(n + 1));
+      f32x4 acc[1] = {(f32x4){0.f, 0.f, 0.f, 0.f}};
+      const unsigned char* lo_n = lo + n * C::IXP * POSB;
+      const unsigned char* hi_n = hi + n * C::IXP * POSB;
+#pragma unroll
+      for (int rd = 0; rd < ROUNDS; ++rd) {
+        BV b[1][2];
+        b[0][0].u = *reinterpret_cast<const uint4*>(lo_n + rd * C::ROUNDB);
+        b[0][1].u = *reinterpret_cast<const uint4*>(lo_n + rd * C::ROUNDB + 16);
+        SF16_TERMS(acc, 0, 1, w0[rd], b);
+        if (two) {
+          BV c[1][2];
+          c[0][0].u = *reinterpret_cast<const uint4*>(hi_n + rd * C::ROUNDB);
+          c[0][1].u = *reinterpret_cast<const uint4*>(hi_n + rd * C::ROUNDB + 16);
+          if (rd < ROUNDS - W1L) {
+            SF16_TERMS(acc, 0, 1, w1[rd < ROUNDS - W1L ? rd : 0], c);
+          } else {
+            BV wl[2];
+            wl[0].u = *reinterpret_cast<const uint4*>(w1l + ((rd - (ROUNDS - W1L)) * 2 + 0) * 1024);
+            wl[1].u = *reinterpret_cast<const uint4*>(w1l + ((rd - (ROUNDS - W1L)) * 2 + 1) * 1024);
+            SF16_TERMS(acc, 0, 1, wl, c);
+          }
+        }
+      }
+      asm volatile("" ::"v"(skn.x), "v"(skn.y), "v"(skn.z), "v"(skn.w));   // the next row's residual arrives before this row's store
+      if (x_ok) {
+        const f32x4 r = acc[0];
+        float4 o = make_float4(r.x * out_mul + bv.x, r.y * out_mul + bv.y, r.z * out_mul + bv.z, r.w * out_mul + bv.w);
+        if (act == CDS_ACT_RELU) o = make_float4(fmaxf(o.x, 0.f), fmaxf(o.y, 0.f), fmaxf(o.z, 0.f), fmaxf(o.w, 0.f));
+        if (skip) o = make_float4(sk.x + o.x, sk.y + o.y, sk.z + o.z, sk.w + o.w);
+        amax = fmaxf(fmaxf(amax, fmaxf(fabsf(o.x), fabsf(o.y))), fmaxf(fabsf(o.z), fabsf(o.w)));
+        sbf_store4(out + zbase + row_off(n), o);
+      }
+    }
+    __syncthreads();
+  }
+  sf16_publish_bound(amax, out_bound);
+}
+
+// z segments per column: whole rounds of 256 single-resident workgroups against the planes a segment spends priming its ring
+int dzm_pick_nseg(int wgs_per_seg, int D) {
+  int best = 1;
+  double best_cost = 1e30;
+  for (int n = 1; n <= min(D, 24); ++n) {
+    const int len = cds_ceil_div(D, n);
+    const int n_eff = cds_ceil_div(D, len);
+    const double cost = (double)cds_ceil_div(wgs_per_seg * n_eff, 256) * (len + 1.5);
+    if (cost < best_cost - 1e-9) { best_cost = cost; best = n; }
+  }
+  const int nseg_e = cds_env_int("CDS_DZM_NSEG", 0);   // A/B and test knob, read per launch
+  return nseg_e > 0 ? min(nseg_e, D) : best;
+}
+
 }  // namespace
+
+// conv7 (ConvTranspose3d 64 -> 32, channels-last, split-f16) for cds_deconv3d_sf16_f32 (conv3d_sbf.hip): CDS_ZMG_UNSUPPORTED when the
+// volume stays on the tiled kernel.  CDS_DZM_DEEP (A/B knob, like CDS_ZMG_DEEP): 0 = tiled kernel, 1 = z-march where columns x
+// segments x cout blocks fill the 256 CUs, 2 = z-march whatever the size.
+int cds_deconv3d_zm64_dispatch(const float* x, const void* wsp, const float* bias, const float* skip, float* out, int Cin, int Cout,
+                               int D, int H, int W, int act, hipStream_t st, const float* in_bound, float w_inv, float* out_bound) {
+  const int deep = cds_env_int("CDS_DZM_DEEP", 1);
+  if (deep <= 0 || Cin != 64 || Cout != 32 || !in_bound) return CDS_ZMG_UNSUPPORTED;
+  if ((long)2 * H * 2 * W * Cout >= (1l << 31) || (long)H * W * Cin >= (1l << 31)) return CDS_ZMG_UNSUPPORTED;   // 32-bit in-plane offsets
+  using C = DZC<8, 4>;
+  const int tiles_x = cds_ceil_div(W, C::TX), tiles_y = cds_ceil_div(H, C::TY);
+  const int ncols = tiles_x * tiles_y;
+  const int seg_len = cds_ceil_div(D, dzm_pick_nseg(ncols * 2, D));
+  const int nseg = cds_ceil_div(D, seg_len);
+  if (deep == 1 && ncols * nseg * 2 < 256) return CDS_ZMG_UNSUPPORTED;
+  static std::atomic<unsigned long long> lds_ok{0};
+  if (int e_lds = cds_allow_lds(reinterpret_cast<const void*>(deconv3d_zm64_kernel), 160 * 1024, lds_ok)) return e_lds;
+  hipLaunchKernelGGL(deconv3d_zm64_kernel, dim3(ncols * nseg, 2), dim3(C::THREADS), C::LDS + DZM64_W1L * 2 * 1024, st, x, reinterpret_cast<const uint4*>(wsp),
+                     bias, skip, out, D, H, W, tiles_x, ncols, seg_len, act, in_bound, w_inv, out_bound);
+  return cds_launch_status();
+}
 
 // ConvTranspose3d k3 s2 p1 op1 (+bias +ReLU +residual) 32 -> 16 in split-bf16 arithmetic, channels-last: x [D][H][W][32] ->
 // out [2D][2H][2W][16]; weight_cls from ops.split_pack_deconv_cls (int16 [8 classes][4 rounds][2][3][64][8]).
@@ -194,17 +355,7 @@ static int dzm_entry(const float* x, const void* weight_cls, const float* bias, 
   hipStream_t st = (hipStream_t)stream;
   const int tiles_x = cds_ceil_div(W, C::TX), tiles_y = cds_ceil_div(H, C::TY);
   const int ncols = tiles_x * tiles_y;
-  const char* nseg_e = getenv("CDS_DZM_NSEG");   // A/B and test knob, read per launch
-  int best = 1;
-  double best_cost = 1e30;
-  for (int n = 1; n <= min(D, 24); ++n) {        // whole rounds of 256 single-resident workgroups; 2 planes of priming per segment
-    const int len = cds_ceil_div(D, n);
-    const int n_eff = cds_ceil_div(D, len);
-    const double cost = (double)cds_ceil_div(ncols * n_eff, 256) * (len + 1.5);
-    if (cost < best_cost - 1e-9) { best_cost = cost; best = n; }
-  }
-  if (nseg_e && atoi(nseg_e) > 0) best = min(atoi(nseg_e), D);
-  const int seg_len = cds_ceil_div(D, best);
+  const int seg_len = cds_ceil_div(D, dzm_pick_nseg(ncols, D));
   const int nseg = cds_ceil_div(D, seg_len);
   if (in_bound) {
     static std::atomic<unsigned long long> lds_ok_h{0};

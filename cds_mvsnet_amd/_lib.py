@@ -24,6 +24,9 @@ MAX_IMAGES = 16
 STAGE_STATE_WORDS = 2080
 DEPTH_METRICS_MAX_T = 8
 DEPTH_METRICS_MAX_GROUPS = 1024
+ICP_SUMS = 18
+ICP_MAX_GROUPS = 1024
+CROP_MAX_VERTICES = 256
 EINVAL = -1000
 
 P = c_void_p
@@ -143,6 +146,11 @@ SIGNATURES = {
     "cds_grid_hash_build": [P, L, L, P, P, I, P],
     "cds_nn_query_f32": [P, P, L, P, P, P, P, P, P, I, P, F, P, P],
     "cds_thin_round_f32": [P, P, L, P, P, I, P, F, P, P, P],
+    "cds_transform_points_f32": [P, L, P, P, P],
+    "cds_nn_index_f32": [P, P, L, P, P, P, P, P, P, I, P, F, P, P, P],
+    "cds_icp_sums_f64": [P, P, L, P, P, P, P, P, P, P, I, P, F, P, L, P, P, P, P],
+    "cds_voxel_mean_f32": [P, L, P, P, L, P, P],
+    "cds_polygon_crop_f32": [P, L, P, I, I, DB, DB, P, P],
     "cds_gipuma_tiles": [L],
     "cds_gipuma_prob_filter_f32": [P, P, P, I, I, I, P, P, P, P],
     "cds_gipuma_fuse_view_f32": [P, P, P, P, I, I, I, I, F, F, F, I, P, P, P, P],

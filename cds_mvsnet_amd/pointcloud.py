@@ -1,9 +1,9 @@
-"""Point-cloud primitives of the DTU evaluation on the GPU: capped nearest-neighbour distances, greedy thinning to a minimum
-spacing, and a PLY vertex reader.
+"""Point-cloud primitives of the DTU and Tanks and Temples evaluations on the GPU: capped nearest-neighbour distances (with
+or without the index of the neighbour), greedy thinning to a minimum spacing, and a PLY vertex reader.
 
-The hot paths are the HIP kernels of ``csrc/pointcloud.hip`` (``include/cds_mvsnet_hip.h``): a sparse uniform grid with 64-bit
-cell keys and a hash table, queried one point per lane.  torch is used for device memory and for the sort / unique / cumsum
-that lay the grid out.  Inputs must be float32 ROCm tensors; there is no CPU path.
+The hot paths are the HIP kernels of ``csrc/pointcloud.hip`` and ``csrc/registration.hip`` (``include/cds_mvsnet_hip.h``): a
+sparse uniform grid with 64-bit cell keys and a hash table, queried one point per lane.  torch is used for device memory
+and for the sort / unique / cumsum that lay the grid out.  Inputs must be float32 ROCm tensors; there is no CPU path.
 """
 from __future__ import annotations
 
@@ -85,6 +85,7 @@ class PointGrid:
         if rank is not None:             # integer copy: rank bits must not pass through float arithmetic
             self.pts.view(torch.int32)[:, 3] = rank.to(self.device, torch.int32)[self.perm]
         self.n = n
+        self.indexed = False            # True when the w lane holds each point's input index (index_grid)
 
     def keys(self, points: Tensor) -> Tensor:
         """Fine cell keys of arbitrary points in this grid's frame (coordinates clamped to the grid)."""
@@ -132,6 +133,46 @@ def nearest_distance(query: Tensor, target: Tensor, max_dist: float, grid: Optio
                                        grid.table_vals.data_ptr(), grid.log2_slots, grid.frame.data_ptr(), float(max_dist),
                                        out.data_ptr(), _stream(query)), "cds_nn_query_f32")
     return out
+
+
+def index_grid(target: Tensor, cell: Optional[float] = None) -> PointGrid:
+    """A PointGrid of ``target`` whose w lane carries each point's input index (rank = arange(N)): what
+    :func:`nearest_index` and the registration kernels search."""
+    target = _points(target, "target")
+    grid = PointGrid(target, cell if cell is not None else default_cell(target),
+                     rank=torch.arange(target.shape[0], dtype=torch.int32, device=target.device))
+    grid.indexed = True
+    return grid
+
+
+def _grid_args(grid: PointGrid):
+    return (grid.pts.data_ptr(), grid.cell_start.data_ptr(), grid.cell_keys.data_ptr(), grid.coarse_start.data_ptr(),
+            grid.table_keys.data_ptr(), grid.table_vals.data_ptr(), grid.log2_slots, grid.frame.data_ptr())
+
+
+def nearest_index(query: Tensor, target: Tensor, max_dist: float, grid: Optional[PointGrid] = None,
+                  cell: Optional[float] = None):
+    """:func:`nearest_distance` that also says which target point was nearest -> (dist float32 [M], index int32 [M]).
+    The smallest fp32 d2 = dx*dx + dy*dy + dz*dz wins and among equal d2 the lowest target index; it is accepted only if
+    d2 < max_dist^2, otherwise dist = max_dist and index = -1 (also for an empty target).  ``grid``: an
+    :func:`index_grid` of ``target`` to reuse."""
+    query = _points(query, "query")
+    if not (max_dist >= 0):
+        raise ValueError(f"nearest_index: max_dist must be >= 0, got {max_dist}")
+    m = query.shape[0]
+    dist = torch.full((m,), float(max_dist), dtype=torch.float32, device=query.device)
+    index = torch.full((m,), -1, dtype=torch.int32, device=query.device)
+    if target.shape[0] == 0 or m == 0:
+        _points(target, "target")
+        return dist, index
+    if grid is None:
+        grid = index_grid(target, cell)
+    elif not grid.indexed:
+        raise ValueError("nearest_index: the grid must come from index_grid (its w lane holds the input indices)")
+    order = torch.sort(grid.keys(query), stable=True)[1]
+    check(_lib.load().cds_nn_index_f32(query.data_ptr(), order.data_ptr(), m, *_grid_args(grid), float(max_dist),
+                                       dist.data_ptr(), index.data_ptr(), _stream(query)), "cds_nn_index_f32")
+    return dist, index
 
 
 def thinning_order(n: int, seed: int = 0) -> Tensor:

@@ -196,6 +196,80 @@ def make_dtu_scene(half_x: float, half_y: float, spacing: float, res: float, mar
     return out
 
 
+def tt_surface(x, y, half: float, centre=(1.5, -0.8, 0.6)):
+    """The height field of :func:`make_tt_scene` over |x - cx|, |y - cy| <= half (float64 numpy)."""
+    u = (np.asarray(x, np.float64) - centre[0]) / half
+    v = (np.asarray(y, np.float64) - centre[1]) / half
+    return centre[2] + half * (0.25 * np.sin(3.0 * u) * np.cos(2.0 * v) + 0.08 * np.sin(7.0 * u + 1.0) * np.sin(5.0 * v))
+
+
+def similarity(deg: float, axis, shift, scale: float = 1.0, about=(0.0, 0.0, 0.0)) -> np.ndarray:
+    """4x4 float64: scale times a rotation of ``deg`` degrees about ``axis`` through the point ``about``, then ``shift``."""
+    k = np.asarray(axis, np.float64)
+    k = k / np.linalg.norm(k)
+    K = np.array([[0, -k[2], k[1]], [k[2], 0, -k[0]], [-k[1], k[0], 0]])
+    a = math.radians(deg)
+    R = np.eye(3) + math.sin(a) * K + (1 - math.cos(a)) * (K @ K)
+    c = np.asarray(about, np.float64)
+    out = np.eye(4)
+    out[:3, :3] = scale * R
+    out[:3, 3] = c - scale * (R @ c) + np.asarray(shift, np.float64)
+    return out
+
+
+def make_tt_scene(n_gt: int = 30_000, n_pred: int = 30_000, tau: float = 0.01, density: float = 2.0, noise: float = 0.4,
+                  outlier_frac: float = 0.04, outlier_range: float = 8.0, holes: int = 4, hole_radius: float = 10.0,
+                  misalign=(0.15, 1.2, 1.002), seed: int = 0) -> Dict[str, object]:
+    """A scene in the layout of a Tanks and Temples training scene, sized by ``tau`` (noise, outlier_range, hole_radius and
+    the misalignment's shift are in units of tau):
+      gt      float32 [~n_gt,3]: the surface :func:`tt_surface` on a jittered grid with ``density`` points per tau;
+      crop    a concave (notched L) polygon volume orthogonal to Z that cuts both clouds (the keys of tt_eval.read_crop);
+      trans   float64 [4,4]: the scene's nominal alignment, prediction frame -> ground-truth frame (a rigid motion);
+      true_trans  ``D @ trans`` with D the small similarity ``misalign`` = (degrees, shift in tau, scale) about the centre;
+      pred    float32 [<= n_pred,3]: uniform random surface samples (another sampling than gt) with N(0, noise tau) height
+              noise, ``holes`` empty discs and ``outlier_frac`` points moved up to ``outlier_range`` tau away, mapped into
+              the prediction frame by the inverse of true_trans: ``trans`` alone leaves it misaligned by D;
+      tau."""
+    rs = np.random.RandomState(seed)
+    centre = np.array([1.5, -0.8, 0.6])
+    side = max(int(round(math.sqrt(n_gt))), 2)
+    spacing = tau / density
+    half = 0.5 * (side - 1) * spacing
+    g = (np.arange(side) - 0.5 * (side - 1)) * spacing
+    gx, gy = np.meshgrid(g, g, indexing="ij")
+    gx = centre[0] + gx.reshape(-1) + rs.uniform(-0.3, 0.3, gx.size) * spacing
+    gy = centre[1] + gy.reshape(-1) + rs.uniform(-0.3, 0.3, gy.size) * spacing
+    gt = np.stack([gx, gy, tt_surface(gx, gy, half, centre)], 1).astype(np.float32)
+
+    px = centre[0] + rs.uniform(-1.0, 1.0, n_pred) * half
+    py = centre[1] + rs.uniform(-1.0, 1.0, n_pred) * half
+    pred = np.stack([px, py, tt_surface(px, py, half, centre) + rs.randn(n_pred) * noise * tau], 1)
+    if holes:
+        hc = centre[:2] + rs.uniform(-0.7, 0.7, (holes, 2)) * half
+        gone = np.zeros(n_pred, bool)
+        for c in hc:
+            gone |= ((pred[:, 0] - c[0]) ** 2 + (pred[:, 1] - c[1]) ** 2) <= (hole_radius * tau) ** 2
+        pred = pred[~gone]
+    n_out = int(outlier_frac * len(pred))
+    if n_out:
+        idx = rs.choice(len(pred), n_out, replace=False)
+        pred[idx] += rs.uniform(-outlier_range, outlier_range, (n_out, 3)) * tau
+
+    # a notched L in units of half around the centre: concave, and it leaves a band of both clouds outside
+    shape = np.array([[-0.9, -0.85], [0.88, -0.9], [0.9, -0.1], [0.35, -0.05], [0.2, 0.3], [0.3, 0.92], [-0.5, 0.88],
+                      [-0.45, 0.35], [-0.92, 0.3]])
+    poly = np.concatenate([centre[:2] + shape * half, np.zeros((len(shape), 1))], 1)
+    crop = {"orthogonal_axis": "Z", "axis_min": float(centre[2] - 0.24 * half), "axis_max": float(centre[2] + 0.3 * half),
+            "bounding_polygon": poly}
+
+    trans = similarity(25.0, (0.2, -0.1, 1.0), (0.3, -0.2, 0.1))
+    D = similarity(misalign[0], (1.0, 0.6, 0.8), np.array([0.5, -0.3, 0.8]) / math.sqrt(0.98) * misalign[1] * tau, misalign[2], centre)
+    true_trans = D @ trans
+    inv = np.linalg.inv(true_trans)
+    pred = (pred @ inv[:3, :3].T + inv[:3, 3]).astype(np.float32)
+    return {"gt": gt, "pred": pred, "crop": crop, "trans": trans, "true_trans": true_trans, "tau": float(tau)}
+
+
 def _min_track_angle(centres: np.ndarray, xyz: np.ndarray, pt: np.ndarray, img: np.ndarray) -> float:
     """Smallest angle (degrees) at a point between two camera centres that both observe it, over all tracks."""
     N, P = len(centres), len(xyz)

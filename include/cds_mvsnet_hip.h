@@ -743,6 +743,53 @@ int cds_thin_round_f32(const float* pts, const int* cell_start, long long n, con
                        void* stream);
 
 /*
+ * Registration and preparation of point clouds for the Tanks and Temples F-score (csrc/registration.hip; cds_mvsnet_amd/tt_eval.py,
+ * DESIGN.md 1.6).  The grid arguments (pts .. frame_host) are those of cds_nn_query_f32, of a grid whose w lane holds each
+ * point's input index as int bits (PointGrid with rank = arange(N)).
+ * cds_transform_points_f32  out[i] = fp32(T points[i]): T 12 doubles on the DEVICE (row-major 3x4), row r computed in float64 as
+ *                           ((T[r][0] x + T[r][1] y) + T[r][2] z) + T[r][3], every product and sum rounded separately, then
+ *                           rounded once to fp32.  out may not alias points.
+ * cds_nn_index_f32          the walk of cds_nn_query_f32 with the nearest point's input index: the smallest d2 = dx*dx + dy*dy +
+ *                           dz*dz (fp32) wins, among equal d2 the lowest input index; accepted only if d2 < max_dist^2.
+ *                           dist[i] as cds_nn_query_f32 (max_dist when nothing is accepted), index[i] int32, -1 in that case.
+ * cds_icp_sums_f64          one point-to-point registration step.  Per source point s (source [m][3] fp32, m >= 1):
+ *                           p = fp32(T s) as cds_transform_points_f32, q = the nearest target of p as cds_nn_index_f32.  Over
+ *                           the accepted pairs, out [CDS_ICP_SUMS] doubles on the DEVICE:
+ *                             [0] count   [1..3] sum p   [4..6] sum q   [7 + 3r + c] sum q[r] p[c]   [16] sum |p - q|^2
+ *                             [17] sum |p|^2 (the scale of the similarity update divides by the variance of p)
+ *                           in fp64 from the fp32 values, |p - q|^2 = (dx dx + dy dy) + dz dz, |p|^2 likewise.  Summed in a fixed order
+ *                           (per-workgroup records in ws, ws_doubles >= CDS_ICP_WS_DOUBLES; a second pass whose shape depends
+ *                           on m only; no atomics): bit-reproducible for the same inputs.  order: a permutation of the m source
+ *                           points that the lanes follow (it fixes the order of the sums as well) or NULL.  index [m] int32 /
+ *                           dist [m] fp32: the per-point results as cds_nn_index_f32, or NULL.
+ * cds_voxel_mean_f32        voxel v of n_voxels holds the points perm[start[v] .. start[v + 1]) (perm [n] int64 input indices,
+ *                           start [n_voxels + 1] int32); out[v] = their mean, accumulated in fp64 in that order, divided by the
+ *                           count and rounded once to fp32.  The keys, the stable sort and the offsets are the caller's
+ *                           (cds_grid_keys_f32 + torch), so the output order is the caller's voxel order.
+ * cds_polygon_crop_f32      keep[i] (uint8 0 / 1) for points [n][3] fp32, all arithmetic in fp64.  axis w = 0 / 1 / 2 (X / Y / Z) with
+ *                           (u, v) = (Y, Z) / (X, Z) / (X, Y); polygon [P][3] doubles on the DEVICE, 3 <= P <= CDS_CROP_MAX_VERTICES.
+ *                           Kept iff axis_min <= p[w] <= axis_max and an odd number of edges (a = polygon[i], b = polygon[(i+1) % P])
+ *                           have (p[v] < a[v]) != (p[v] < b[v]) and a[u] + (p[v] - a[v]) / (b[v] - a[v]) * (b[u] - a[u]) < p[u],
+ *                           evaluated in that order with IEEE divide.
+ */
+#define CDS_ICP_SUMS 18
+#define CDS_ICP_MAX_GROUPS 1024 /* workgroups of the first pass of cds_icp_sums_f64 */
+#define CDS_ICP_WS_DOUBLES (CDS_ICP_MAX_GROUPS * CDS_ICP_SUMS)
+#define CDS_CROP_MAX_VERTICES 256
+int cds_transform_points_f32(const float* points, long long n, const double* T, float* out, void* stream);
+int cds_nn_index_f32(const float* query, const long long* order, long long m, const float* pts, const int* cell_start,
+                     const long long* cell_keys, const int* coarse_start, const long long* table_keys, const int* table_vals,
+                     int log2_slots, const float* frame_host, float max_dist, float* dist, int* index, void* stream);
+int cds_icp_sums_f64(const float* source, const long long* order, long long m, const double* T, const float* pts,
+                     const int* cell_start, const long long* cell_keys, const int* coarse_start, const long long* table_keys,
+                     const int* table_vals, int log2_slots, const float* frame_host, float max_dist, double* ws,
+                     long long ws_doubles, double* out, int* index, float* dist, void* stream);
+int cds_voxel_mean_f32(const float* points, long long n, const long long* perm, const int* start, long long n_voxels, float* out,
+                       void* stream);
+int cds_polygon_crop_f32(const float* points, long long n, const double* polygon, int P, int axis, double axis_min,
+                         double axis_max, unsigned char* keep, void* stream);
+
+/*
  * Gipuma-style depth-map fusion (the reference's --filter_method gipuma, gipuma.py:153-195, which runs the external fusibile;
  * cds_mvsnet_amd/gipuma.py).  The rule, its fp32 operation order and the points where it fixes behaviour fusibile leaves open
  * are in the header comment of csrc/gipuma.hip.  Views share one h x w; V h w < 2^31.

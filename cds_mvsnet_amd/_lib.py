@@ -27,6 +27,8 @@ DEPTH_METRICS_MAX_GROUPS = 1024
 ICP_SUMS = 18
 ICP_MAX_GROUPS = 1024
 CROP_MAX_VERTICES = 256
+RANSAC_RECORD = 15
+RANSAC_MIN_SAMPLE, RANSAC_MAX_SAMPLE = 3, 8
 EINVAL = -1000
 
 P = c_void_p
@@ -151,6 +153,7 @@ SIGNATURES = {
     "cds_icp_sums_f64": [P, P, L, P, P, P, P, P, P, P, I, P, F, P, L, P, P, P, P],
     "cds_voxel_mean_f32": [P, L, P, P, L, P, P],
     "cds_polygon_crop_f32": [P, L, P, I, I, DB, DB, P, P],
+    "cds_ransac_similarity_f64": [P, P, L, L, I, DB, ctypes.c_ulonglong, P, L, P, P, P, P],
     "cds_gipuma_tiles": [L],
     "cds_gipuma_prob_filter_f32": [P, P, P, I, I, I, P, P, P, P],
     "cds_gipuma_fuse_view_f32": [P, P, P, P, I, I, I, I, F, F, F, I, P, P, P, P],

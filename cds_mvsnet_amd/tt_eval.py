@@ -13,10 +13,16 @@ toolbox run is unpinned, neither the toolbox nor Open3D was available to compare
    F = 2 P R / (P + R), and the two cumulative curves up to 5 tau.
 
 ``python -m cds_mvsnet_amd.tt_eval --datapath <T&T training data> --plydir <outdir> --scenes Barn,Truck`` scores a directory of
-fused clouds (``infer --dataset tt --fuse``).  A reconstruction made in another frame than the ground truth's cameras needs the
-toolbox's trajectory alignment first; that step is out of scope here and ``--init`` is the hook for its result.  The hot paths
-are the HIP kernels of ``csrc/registration.hip`` and ``csrc/pointcloud.hip``; inputs must be float32 ROCm tensors, there is no
-CPU path.
+fused clouds (``infer --dataset tt --fuse``).  ``<Scene>_trans.txt`` maps the benchmark's own COLMAP reconstruction
+(``<Scene>_COLMAP_SfM.log``) onto the scan; a reconstruction made from other cameras, with their own origin, orientation and
+scale, is first aligned to that reconstruction from its camera centres, the toolbox's trajectory alignment
+(:func:`trajectory_alignment`: a RANSAC over camera-centre correspondences, 100 000 hypotheses of 6, one launch of
+cds_ransac_similarity_f64).  ``--cams "<testpath>/{scene}/cams"`` takes the cameras ``infer`` ran with, ``--traj
+"<dir>/{scene}.log"`` a trajectory file, ``--export-log DIR`` writes the ``<Scene>.log`` the benchmark website asks for next to
+the ``.ply``; the resulting transform replaces ``<Scene>_trans.txt @ init`` as the start of the registration.  The toolbox's
+mapping file for video-rate logs is out of scope: both trajectories must list the same cameras in the same order.  The hot
+paths are the HIP kernels of ``csrc/registration.hip``, ``csrc/ransac.hip`` and ``csrc/pointcloud.hip``; clouds must be
+float32 ROCm tensors (correspondences float64), there is no CPU path.
 """
 from __future__ import annotations
 
@@ -24,6 +30,7 @@ import argparse
 import json
 import math
 import os
+import re
 import sys
 import time
 from typing import Dict, List, Optional, Sequence, Tuple
@@ -31,7 +38,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, mvs_io
 from ._lib import check
 from .dtu_eval import _Phases, _mean
 from .ops import _stream
@@ -365,6 +372,131 @@ def evaluate(pred: Tensor, gt: Tensor, crop: Dict[str, object], trans, tau: floa
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+def read_log_trajectory(path: str) -> np.ndarray:
+    """The toolbox's ``.log`` trajectory -> camera-to-world poses float64 [M,4,4].  Per camera one metadata line of three
+    integers, then the four rows of the matrix; blank lines between cameras are skipped."""
+    with open(path) as f:
+        lines = [(no, ln.split()) for no, ln in enumerate(f, 1) if ln.strip()]
+    poses = []
+    for i in range(0, len(lines), 5):
+        no, meta = lines[i]
+        try:
+            if len(meta) != 3:
+                raise ValueError
+            [int(v) for v in meta]
+        except ValueError:
+            raise ValueError(f"{path}:{no}: expected a metadata line of three integers, got {' '.join(meta)!r}") from None
+        rows = lines[i + 1:i + 5]
+        if len(rows) < 4:
+            raise ValueError(f"{path}:{no}: camera {len(poses)} has {len(rows)} matrix rows, expected 4")
+        m = np.empty((4, 4), np.float64)
+        for r, (rno, fields) in enumerate(rows):
+            try:
+                if len(fields) != 4:
+                    raise ValueError
+                m[r] = [float(v) for v in fields]
+            except ValueError:
+                raise ValueError(f"{path}:{rno}: expected a matrix row of four numbers, got {' '.join(fields)!r}") from None
+        poses.append(m)
+    return np.stack(poses) if poses else np.zeros((0, 4, 4), np.float64)
+
+
+def write_log_trajectory(path: str, poses) -> None:
+    """The inverse of :func:`read_log_trajectory`: camera i as the metadata line ``i i 0`` and four rows, every number
+    written so that it reads back to the same float64."""
+    poses = np.asarray(poses, np.float64)
+    if poses.ndim != 3 or poses.shape[1:] != (4, 4):
+        raise ValueError(f"write_log_trajectory: expected poses [M,4,4], got {poses.shape}")
+    with open(path, "w") as f:
+        for i, m in enumerate(poses):
+            f.write(f"{i} {i} 0\n")
+            for row in m:
+                f.write(" ".join(repr(float(v)) for v in row) + "\n")
+
+
+def camera_poses_from_cams(folder: str) -> np.ndarray:
+    """Camera-to-world poses float64 [M,4,4] of an MVSNet ``cams`` folder: ``%08d_cam.txt`` in ascending id, the
+    world-to-camera extrinsic of :func:`mvs_io.read_cam_file` inverted in float64."""
+    if not os.path.isdir(folder):
+        raise FileNotFoundError(f"{folder} not found")
+    names = sorted(n for n in os.listdir(folder) if re.fullmatch(r"\d{8}_cam\.txt", n))
+    if not names:
+        raise FileNotFoundError(f"{folder}: no %08d_cam.txt files")
+    return np.stack([np.linalg.inv(mvs_io.read_cam_file(os.path.join(folder, n))[1].astype(np.float64)) for n in names])
+
+
+def _correspondences(t: Tensor, name: str) -> Tensor:
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise RuntimeError(f"{name} must be a ROCm (cuda) tensor; there is no CPU fallback")
+    if t.dtype != torch.float64 or t.dim() != 2 or t.shape[1] != 3:
+        raise ValueError(f"{name}: expected a float64 tensor [N,3], got {t.dtype} {tuple(t.shape)}")
+    return t.contiguous()
+
+
+def ransac_similarity(src: Tensor, dst: Tensor, threshold: float, k: int = 6, iterations: int = 100_000, seed: int = 0,
+                      return_all: bool = False):
+    """RANSAC for the similarity that maps src onto dst (float64 [N,3] device tensors, correspondence i <-> i), one launch
+    of cds_ransac_similarity_f64 and one host read: ``iterations`` hypotheses of ``k`` distinct correspondences drawn from
+    (seed, hypothesis) alone, Umeyama with scaling on each, scored over all N with ``|T src_i - dst_i| < threshold``; the
+    winner has the most inliers, then the smallest sum of squared inlier distances, then the smallest index; no refit.
+    -> (T float64 4x4, {"index", "count", "fitness" = count / N, "rmse" = sqrt(err2 / count)}); with no accepted hypothesis
+    index -1, count 0 and the identity.  ``return_all`` adds (count int32 [iterations], err2 float64 [iterations]) of every
+    hypothesis as device tensors (a rejected one: 0, +inf)."""
+    src, dst = _correspondences(src, "src"), _correspondences(dst, "dst")
+    if src.shape != dst.shape or src.device != dst.device:
+        raise ValueError(f"ransac_similarity: src {tuple(src.shape)} and dst {tuple(dst.shape)} must match, on one device")
+    if not _lib.RANSAC_MIN_SAMPLE <= k <= _lib.RANSAC_MAX_SAMPLE:
+        raise ValueError(f"ransac_similarity: k must be {_lib.RANSAC_MIN_SAMPLE}..{_lib.RANSAC_MAX_SAMPLE}, got {k}")
+    if not (threshold >= 0 and math.isfinite(threshold)) or iterations < 0 or not 0 <= seed < 2 ** 64:
+        raise ValueError(f"ransac_similarity: threshold {threshold}, iterations {iterations}, seed {seed}")
+    dev, n, H = src.device, src.shape[0], int(iterations)
+    ws = torch.empty(max((H + 255) // 256, 1) * _lib.RANSAC_RECORD, dtype=torch.float64, device=dev)
+    out = torch.empty(_lib.RANSAC_RECORD, dtype=torch.float64, device=dev)
+    count = torch.empty(H, dtype=torch.int32, device=dev) if return_all else None
+    err2 = torch.empty(H, dtype=torch.float64, device=dev) if return_all else None
+    check(_lib.load().cds_ransac_similarity_f64(src.data_ptr(), dst.data_ptr(), n, H, int(k), float(threshold), int(seed),
+                                                ws.data_ptr(), ws.numel(), out.data_ptr(),
+                                                count.data_ptr() if return_all else None,
+                                                err2.data_ptr() if return_all else None, _stream(src)),
+          "cds_ransac_similarity_f64")
+    rec = out.cpu().numpy()
+    T = np.eye(4)
+    T[:3] = rec[3:].reshape(3, 4)
+    c = int(rec[1])
+    info = {"index": int(rec[0]), "count": c, "fitness": c / n if n else 0.0, "rmse": math.sqrt(rec[2] / c) if c else 0.0}
+    return (T, info, count, err2) if return_all else (T, info)
+
+
+def trajectory_alignment(est_poses, ref_poses, trans, threshold: float = 0.2, k: int = 6, iterations: int = 100_000,
+                         seed: int = 0, device="cuda", info: Optional[Dict[str, object]] = None) -> np.ndarray:
+    """The toolbox's ``trajectory_alignment`` with its constants -> float64 4x4 from the estimate's frame to the
+    ground-truth frame.  Source: the camera centres of ``est_poses`` (camera-to-world [M,4,4]); target: ``trans`` (the
+    scene's ``_trans.txt``) applied to the centres of ``ref_poses`` (the scene's ``_COLMAP_SfM.log``), camera i <-> camera
+    i; :func:`ransac_similarity` between them.  Both must hold the same cameras (the toolbox's mapping file for video-rate
+    logs is out of scope): unequal counts raise, as does a result with no inlier or fewer than ``k``.  ``info`` receives
+    index, count, fitness, rmse and the transform."""
+    est, ref = np.asarray(est_poses, np.float64), np.asarray(ref_poses, np.float64)
+    for name, a in (("est_poses", est), ("ref_poses", ref)):
+        if a.ndim != 3 or a.shape[1:] != (4, 4):
+            raise ValueError(f"trajectory_alignment: {name} must be [M,4,4], got {a.shape}")
+    if len(est) != len(ref):
+        raise ValueError(f"trajectory_alignment: {len(est)} estimated cameras against {len(ref)} reference cameras; "
+                         "both trajectories must list the same cameras")
+    trans = np.asarray(trans, np.float64)
+    if trans.shape != (4, 4):
+        raise ValueError(f"trajectory_alignment: trans must be 4x4, got {trans.shape}")
+    src = np.ascontiguousarray(est[:, :3, 3])
+    dst = np.ascontiguousarray(ref[:, :3, 3] @ trans[:3, :3].T + trans[:3, 3])
+    T, r = ransac_similarity(torch.from_numpy(src).to(device), torch.from_numpy(dst).to(device), threshold, k, iterations, seed)
+    if r["count"] == 0 or r["count"] < k:
+        raise ValueError(f"trajectory_alignment: no similarity fits the {len(est)} camera centres within {threshold} "
+                         f"({r['count']} inliers, {k} needed)")
+    if info is not None:
+        info.update(r, transform=T.tolist())
+    return T
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 def scene_names(testlist: Optional[str], scenes: Optional[str]) -> List[str]:
     if testlist:
         with open(testlist) as f:
@@ -381,14 +513,22 @@ def scene_paths(datapath: str, scene: str) -> Dict[str, str]:
 def main(argv: Optional[Sequence[str]] = None) -> Dict[str, object]:
     ap = argparse.ArgumentParser(prog="python -m cds_mvsnet_amd.tt_eval",
                                  description="Tanks and Temples precision / recall / F-score of fused point clouds, on the GPU")
-    ap.add_argument("--datapath", required=True, help="the T&T training data: <Scene>/<Scene>.ply, <Scene>.json, <Scene>_trans.txt")
+    ap.add_argument("--datapath", required=True, help="the T&T training data: <Scene>/<Scene>.ply, <Scene>.json, <Scene>_trans.txt "
+                                                     "(with --traj / --cams also <Scene>_COLMAP_SfM.log)")
     ap.add_argument("--plydir", required=True, help="folder of the fused clouds (infer --dataset tt --fuse --outdir)")
     grp = ap.add_mutually_exclusive_group(required=True)
     grp.add_argument("--testlist", help="file with one scene per line")
     grp.add_argument("--scenes", help="comma-separated scene names, e.g. Barn,Truck")
     ap.add_argument("--ply", default="{scene}.ply", help="file name of a scene's cloud; {scene} = Barn")
     ap.add_argument("--tau", type=float, help="distance threshold; required for a scene outside the training set")
-    ap.add_argument("--init", help="4x4 text matrix right-multiplied onto <Scene>_trans.txt (e.g. a trajectory alignment)")
+    start = ap.add_mutually_exclusive_group()
+    start.add_argument("--init", help="4x4 text matrix right-multiplied onto <Scene>_trans.txt")
+    start.add_argument("--traj", help="the reconstruction's camera trajectory (.log, camera-to-world); {scene} = Barn.  Aligned to "
+                                      "<Scene>_COLMAP_SfM.log from the camera centres; the result replaces <Scene>_trans.txt")
+    start.add_argument("--cams", help="the same from the cameras infer ran with: the folder of %%08d_cam.txt, e.g. "
+                                      "\"<testpath>/{scene}/cams\"")
+    ap.add_argument("--export-log", metavar="DIR", help="with --cams: write <Scene>.log, the trajectory file the benchmark asks for")
+    ap.add_argument("--seed", type=int, default=0, help="seed of the trajectory alignment's RANSAC")
     ap.add_argument("--no-register", action="store_true", help="score at the initial transform, without the ICP rounds")
     ap.add_argument("--json", help="write the per-scene and mean results here")
     ap.add_argument("--device", default="cuda")
@@ -397,7 +537,10 @@ def main(argv: Optional[Sequence[str]] = None) -> Dict[str, object]:
     dev = torch.device(args.device)
     if dev.type != "cuda":
         raise SystemExit("tt_eval runs on the GPU only (--device cuda[:N])")
+    if args.export_log and not args.cams:
+        ap.error("--export-log needs --cams")
     init = read_trans(args.init) if args.init else np.eye(4)
+    aligned = bool(args.traj or args.cams)
     jobs = []
     for scene in scene_names(args.testlist, args.scenes):        # resolve every file and tau before the first scene is scored
         try:
@@ -406,18 +549,37 @@ def main(argv: Optional[Sequence[str]] = None) -> Dict[str, object]:
             ap.error(str(e))
         ply = os.path.join(args.plydir, args.ply.format(scene=scene))
         paths = scene_paths(args.datapath, scene)
+        if aligned:
+            paths["sfm_log"] = os.path.join(args.datapath, scene, f"{scene}_COLMAP_SfM.log")
+        if args.traj:
+            paths["traj"] = args.traj.format(scene=scene)
         for p in [ply] + list(paths.values()):
             if not os.path.isfile(p):
                 raise FileNotFoundError(f"{scene}: {p} not found")
+        if args.cams:
+            paths["cams"] = args.cams.format(scene=scene)
+            if not os.path.isdir(paths["cams"]):
+                raise FileNotFoundError(f"{scene}: {paths['cams']} not found")
         jobs.append((scene, tau, ply, paths))
+    if args.export_log:
+        os.makedirs(args.export_log, exist_ok=True)
     per_scene: Dict[str, Dict[str, object]] = {}
     with torch.cuda.device(dev):
         for scene, tau, ply, paths in jobs:
             t0 = time.time()
             gt = torch.from_numpy(read_ply_points(paths["ply"])).to(dev)
             pred = torch.from_numpy(read_ply_points(ply)).to(dev)
-            r = evaluate(pred, gt, read_crop(paths["crop"]), read_trans(paths["trans"]) @ init, tau,
-                         register=not args.no_register)
+            start, traj = read_trans(paths["trans"]) @ init, None
+            if aligned:
+                est = camera_poses_from_cams(paths["cams"]) if args.cams else read_log_trajectory(paths["traj"])
+                if args.export_log:
+                    write_log_trajectory(os.path.join(args.export_log, f"{scene}.log"), est)
+                traj = {}
+                start = trajectory_alignment(est, read_log_trajectory(paths["sfm_log"]), read_trans(paths["trans"]),
+                                             seed=args.seed, device=dev, info=traj)
+            r = evaluate(pred, gt, read_crop(paths["crop"]), start, tau, register=not args.no_register)
+            if traj is not None:
+                r["trajectory"] = traj
             per_scene[scene] = r
             print(f"{scene}: precision {r['precision']:.4f}  recall {r['recall']:.4f}  f-score {r['fscore']:.4f}  "
                   f"(tau {tau:g}, {r['n_pred_sampled']} / {r['n_gt_sampled']} points, {time.time() - t0:.1f} s)", flush=True)
@@ -425,6 +587,8 @@ def main(argv: Optional[Sequence[str]] = None) -> Dict[str, object]:
     print(f"mean over {len(per_scene)} scenes: precision {mean['precision']:.4f}  recall {mean['recall']:.4f}  "
           f"f-score {mean['fscore']:.4f}")
     out = {"scenes": per_scene, "mean": mean, "settings": {"tau": args.tau, "register": not args.no_register}}
+    if aligned:                                                      # without the alignment the output stays as it was
+        out["settings"]["seed"] = args.seed
     if args.json:
         with open(args.json, "w") as f:
             json.dump(out, f, indent=1)

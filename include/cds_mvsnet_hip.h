@@ -790,6 +790,30 @@ int cds_polygon_crop_f32(const float* points, long long n, const double* polygon
                          double axis_max, unsigned char* keep, void* stream);
 
 /*
+ * Trajectory alignment of the Tanks and Temples protocol (csrc/ransac.hip, csrc/ransac_common.hpp): RANSAC for
+ * the similarity that maps src onto dst, correspondence i <-> i (src, dst [n][3] doubles on the DEVICE), all in float64.
+ * cds_ransac_similarity_f64  hypothesis h of `hypotheses` (one per lane) draws k distinct indices (CDS_RANSAC_MIN_SAMPLE <= k <=
+ *                            CDS_RANSAC_MAX_SAMPLE) from (seed, h) alone: draw j takes z = splitmix64(seed, 8 h + j),
+ *                            r = floor(z (n - j) / 2^64), then r += 1 for every earlier pick <= r, walking them in ascending
+ *                            order.  T = Umeyama with scaling on the k pairs (sums in draw order, covariance
+ *                            sum q p^T / k - mean_q mean_p^T, 3x3 SVD in the lane, E = diag(1, 1, +-1) from det(U) det(V)).
+ *                            Rejected (count 0, err2 +inf): variance of p zero, second singular value <= 1e-9 of the first,
+ *                            an entry of T not finite, n < k.  Score: d2_i = |T src_i - dst_i|^2, inlier iff d2_i < threshold^2;
+ *                            count = inliers, err2 = sum of their d2 in index order.  The winner is the first in the total
+ *                            order (larger count, smaller err2, smaller h): identical bytes run to run.
+ *                            out [CDS_RANSAC_RECORD] doubles on the DEVICE: [0] h  [1] count  [2] err2  [3..14] T (rows of
+ *                            the 3x4); with no hypothesis, or every one rejected: h = -1, count 0, err2 +inf, the identity.
+ *                            count [hypotheses] int32 / err2 [hypotheses] doubles: every hypothesis's score, or NULL.
+ *                            ws: ws_doubles >= CDS_RANSAC_RECORD * ceil(hypotheses / 256).  n, hypotheses < 2^31.
+ */
+#define CDS_RANSAC_RECORD 15
+#define CDS_RANSAC_MIN_SAMPLE 3
+#define CDS_RANSAC_MAX_SAMPLE 8
+int cds_ransac_similarity_f64(const double* src, const double* dst, long long n, long long hypotheses, int k, double threshold,
+                              unsigned long long seed, double* ws, long long ws_doubles, double* out, int* count, double* err2,
+                              void* stream);
+
+/*
  * Gipuma-style depth-map fusion (the reference's --filter_method gipuma, gipuma.py:153-195, which runs the external fusibile;
  * cds_mvsnet_amd/gipuma.py).  The rule, its fp32 operation order and the points where it fixes behaviour fusibile leaves open
  * are in the header comment of csrc/gipuma.hip.  Views share one h x w; V h w < 2^31.

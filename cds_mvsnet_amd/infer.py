@@ -8,7 +8,9 @@ One process per GPU: with `python -m torch.distributed.run --nproc-per-node N -m
 the reference views `idx % world == rank` (independent depth maps, no collective).  Outputs follow the reference layout:
 `<out>/<scan>/depth_est/%08d.pfm`, `confidence/%08d.pfm` (3 channels = stage 1-3 confidences), `cams/%08d_cam.txt`,
 `images/%08d.jpg`, ready for the fusion step.  `--fuse` then writes `<out>/<scan>.ply` with the normal fusion (fusion.py) or,
-with `--filter_method gipuma`, the gipuma-style one (gipuma.py; `--prob_threshold`, `--disp_threshold`, `--num_consistent`).
+with `--filter_method gipuma`, the gipuma-style one (gipuma.py; `--prob_threshold`, `--disp_threshold`, `--num_consistent`),
+or, with `--filter_method dynamic`, the dynamic consistency check (fusion.py; `--conf`, `--dyn_dist_base`, `--dyn_rel_base`,
+`--dyn_views`).
 `--save_stages` also writes the three stages' own depth maps, `<out>/<scan>/depth_stage{1,2,3}/%08d.pfm`, at their resolutions
 (what evaluations/precision.py scores stage by stage; `python -m cds_mvsnet_amd.depth_eval --folders ...`).
 
@@ -216,7 +218,7 @@ def run(args) -> float:
     print(f"[{rank}] average time ({what}): {avg:.4f} s over {len(times)} depth maps")
     if args.fuse:
         # step 2 of the reference's test.py (pcd_filter, test.py:386-396): scans are independent -> shard over ranks
-        from .fusion import filter_depth
+        from .fusion import filter_depth, format_admitted
         from .gipuma import filter_scan
         if world > 1:  # every rank's depth maps must be on disk before any scan is fused
             if not torch.distributed.is_initialized():
@@ -231,6 +233,15 @@ def run(args) -> float:
                                    prob_threshold=[float(p) for p in args.prob_threshold.split(",")],
                                    disp_threshold=args.disp_threshold, num_consistent=args.num_consistent, device=str(dev))
                 print(f"[{rank}] {scan}.ply: {info['points']} points from {info['views']} views (gipuma)", flush=True)
+                continue
+            if args.filter_method == "dynamic":
+                # the dynamic consistency check: one setting for every scene, thresholds graded by view count
+                info = filter_depth(os.path.join(args.testpath, scan), os.path.join(args.outdir, scan),
+                                    os.path.join(args.outdir, f"{scan}.ply"), conf=[float(c) for c in args.conf.split(",")],
+                                    device=str(dev), method="dynamic", dist_base=args.dyn_dist_base,
+                                    rel_base=args.dyn_rel_base, n_views=[int(v) for v in args.dyn_views.split(",")])
+                print(f"[{rank}] {scan}.ply: {info['points']} points, final mask {info['mean_final_mask']:.3f}, admitted at "
+                      f"{format_admitted(info['admitted_at'])} (dynamic)", flush=True)
                 continue
             info = filter_depth(os.path.join(args.testpath, scan), os.path.join(args.outdir, scan),
                                 os.path.join(args.outdir, f"{scan}.ply"), conf=[float(c) for c in args.conf.split(",")],
@@ -272,11 +283,16 @@ def parse_args(argv=None) -> argparse.Namespace:
     ap.add_argument("--conf", default="0.0,0.0,0.0", help="per-stage confidence thresholds (test.py:61)")
     ap.add_argument("--thres_view", type=int, default=3)
     ap.add_argument("--thres_disp", type=float, default=1.0)
-    ap.add_argument("--filter_method", default="normal", choices=["normal", "gipuma"],
-                    help="--fuse with the normal fusion (fusion.py) or the gipuma-style one (gipuma.py)")
+    ap.add_argument("--filter_method", default="normal", choices=["normal", "gipuma", "dynamic"],
+                    help="--fuse with the normal fusion (fusion.py), the gipuma-style one (gipuma.py) or the dynamic "
+                         "consistency check (fusion.py, DESIGN §1.7; uses --conf)")
     ap.add_argument("--prob_threshold", default="0.0,0.0,0.0", help="gipuma: per-stage confidence thresholds (test.py:68)")
     ap.add_argument("--disp_threshold", type=float, default=0.2, help="gipuma: disparity threshold (test.py:69)")
     ap.add_argument("--num_consistent", type=int, default=3, help="gipuma: consistent views a point needs (test.py:70)")
+    ap.add_argument("--dyn_dist_base", type=float, default=0.25, help="dynamic: re-projection distance per level, in pixels")
+    ap.add_argument("--dyn_rel_base", type=float, default=1.0 / 1300.0, help="dynamic: relative depth difference per level")
+    ap.add_argument("--dyn_views", default="2,10", metavar="n_min,n_max",
+                    help="dynamic: a pixel is kept when n views agree at level n for some n in this range")
     return ap.parse_args(argv)
 
 

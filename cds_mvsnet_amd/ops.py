@@ -1334,6 +1334,45 @@ def depth_fusion(ref_depth: Tensor, ref_conf: Tensor, src_depths: Tensor, src_co
     return fused, mask, points, vm
 
 
+DYNAMIC_MAX_LEVELS = 16     # cap of n_max in cds_depth_fusion_dynamic_f32 (kMaxLevels of csrc/fusion_dynamic.hip)
+
+
+def depth_fusion_dynamic(ref_depth: Tensor, ref_conf: Tensor, src_depths: Tensor, src_confs: Tensor, cams: Tensor,
+                         prob_thresh, dist_base: float = 0.25, rel_base: float = 1.0 / 1300.0, n_views=(2, 10),
+                         want_admit: bool = False, want_levels: bool = False):
+    """Depth-map fusion with the dynamic consistency check for one reference view (rule: include/cds_mvsnet_hip.h).
+    Inputs as :func:`depth_fusion`; n_views = (n_min, n_max) -> (fused [h,w], mask [h,w] in {0,1}, points [3,h,w],
+    admit [h,w] uint8 | None, levels [V,h,w] uint8 | None; a level of n_max + 1 means inconsistent)."""
+    V, h, w = src_depths.shape
+    if tuple(ref_depth.shape) != (h, w) or tuple(ref_conf.shape) != (3, h, w) or tuple(src_confs.shape) != (V, 3, h, w) \
+            or tuple(cams.shape) != (V, 100):
+        raise ValueError("depth_fusion_dynamic: inconsistent shapes")
+    if len(n_views) != 2:
+        raise ValueError(f"depth_fusion_dynamic: n_views must be (n_min, n_max), got {n_views!r}")
+    n_min, n_max = int(n_views[0]), int(n_views[1])
+    if n_min < 1 or n_max < n_min or n_max > DYNAMIC_MAX_LEVELS:
+        raise ValueError(f"depth_fusion_dynamic: need 1 <= n_min <= n_max <= {DYNAMIC_MAX_LEVELS}, got {(n_min, n_max)}")
+    if not (float(dist_base) > 0.0 and float(rel_base) > 0.0):
+        raise ValueError(f"depth_fusion_dynamic: dist_base and rel_base must be positive, got {dist_base}, {rel_base}")
+    th = torch.tensor([float(p) for p in prob_thresh], dtype=torch.float32)
+    if th.numel() != 3:
+        raise ValueError("depth_fusion_dynamic: three confidence thresholds expected")
+    dev = ref_depth.device
+    fused = torch.empty((h, w), dtype=torch.float32, device=dev)
+    mask = torch.empty((h, w), dtype=torch.float32, device=dev)
+    points = torch.empty((3, h, w), dtype=torch.float32, device=dev)
+    admit = torch.empty((h, w), dtype=torch.uint8, device=dev) if want_admit else None
+    levels = torch.empty((V, h, w), dtype=torch.uint8, device=dev) if want_levels else None
+    check(_lib.load().cds_depth_fusion_dynamic_f32(_dev(ref_depth, "ref_depth"), _dev(ref_conf, "ref_conf"),
+                                                   _dev(src_depths, "src_depths"), _dev(src_confs, "src_confs"),
+                                                   _dev(cams, "cams"), fused.data_ptr(), mask.data_ptr(), points.data_ptr(),
+                                                   admit.data_ptr() if admit is not None else None,
+                                                   levels.data_ptr() if levels is not None else None, V, h, w,
+                                                   _host(th, "prob_thresh"), float(dist_base), float(rel_base), n_min, n_max,
+                                                   _stream(fused)), "cds_depth_fusion_dynamic_f32")
+    return fused, mask, points, admit, levels
+
+
 def _refine_range(lo, hi, device) -> Tensor:
     """(depth_min, depth_max, interval) of the Refinement kernels: a 3-element device tensor (geometry block) with hi None, or two
     Python floats = limits that are already in interval units (interval 1: module.py's network on its own)."""

@@ -516,6 +516,33 @@ int cds_depth_fusion_f32(const float* ref_depth, const float* ref_conf, const fl
                          float dist_thresh, float depth_thresh, float view_thresh, void* stream);
 
 /*
+ * Depth-map fusion with a dynamic consistency check: the thresholds grow with the number of agreeing views, so
+ * tight agreement needs few views and loose agreement needs many.  Inputs, cams layout and probability filter as
+ * cds_depth_fusion_f32.  The rule, per reference pixel (px, py) = (x + 0.5, y + 0.5) with reference depth rd:
+ *   1. Re-projection, exactly that of cds_depth_fusion_f32, arithmetic included: source depths zeroed where any of the three
+ *      confidences is not above its threshold; chain image -> camera -> world -> other camera -> image with +1e-9
+ *      normalisations; grid coordinates clamped to +-1.1; in_range_v taken before the sample; the source -> reference
+ *      (x, y, depth) map sampled bilinearly (zero padding, align_corners=True), evaluated at the four taps.  Per view v:
+ *      (rx, ry, rz)_v and in_range_v.
+ *   2. e_v = sqrt((rx - px)^2 + (ry - py)^2);  r_v = |rd - rz_v| / rd  (denominator rd, not max(rd, rz); rd = 0 gives NaN or
+ *      inf and every comparison is false).
+ *   3. Level l_v = the smallest integer n in [1, n_max] with in_range_v, e_v < (float)n * dist_base and
+ *      r_v < (float)n * rel_base (products and comparisons in fp32); n_max + 1 if there is none (inconsistent).
+ *   4. c_n = #{v : l_v <= n}.  admit = the smallest n with n_min <= n <= min(n_max, V) and c_n >= n, or 0.  V < n_min admits
+ *      nothing; that is not an error.
+ *   5. fused = (rd + sum_v rz_v [l_v <= n_max]) / (1 + sum_v [l_v <= n_max]), in view order.
+ *   6. mask = (admit > 0) and the reference pixel's three confidences are above their thresholds.
+ *   7. points = the world point of the fused depth, as in cds_depth_fusion_f32.
+ *   fused [h][w], mask [h][w] (0/1), points [3][h][w] (world); admit [h][w] uint8 or NULL; levels [V][h][w] uint8 or NULL
+ *   CDS_EINVAL: a null required pointer; V, h or w < 1; n_min < 1, n_max < n_min or n_max > 16; dist_base or rel_base not > 0.
+ */
+int cds_depth_fusion_dynamic_f32(const float* ref_depth, const float* ref_conf, const float* src_depths,
+                                 const float* src_confs, const float* cams, float* fused, float* mask, float* points,
+                                 unsigned char* admit, unsigned char* levels, int V, int h, int w,
+                                 const float* prob_thresh_host, float dist_base, float rel_base, int n_min, int n_max,
+                                 void* stream);
+
+/*
  * Norm-curvature bookkeeping of one FeatureNet level (module.py:250-251,257-258,264-265) in one launch:
  *   nc_sum[i] = (a[i]^2 + b[i]^2 + c[i]^2) / 3,  nc_abs[i] = |c[i]|   for the three DynamicConv curvature maps of the level
  */

@@ -268,6 +268,44 @@ def costreg_unet(layers, vol, refresh=None):
     return layers.tail(x, c0, refresh)
 
 
+def feature_pyramid(layers, imgs, emit=None):
+    """The wiring of FeatureNet (module.py:234-267), stated once for every way of running it: two DynamicConv units per level on the way
+    down, a DynamicConv head per stage, 1x1 laterals over cat(nearest2x(coarse), skip) on the way up.  An activation is opaque here:
+    (raw, affine) for the inference layers (InstanceNorm applied on load, see _InferenceLayers), a tensor in training.
+    layers: ``dyn(name, x, level) -> (act, nc)`` (level 0 / 1 / 2 selects the epipoles at full / half / quarter resolution; conv00's
+    shared reference copies are the layers' business), ``down(name, x) -> act``, ``lateral(name, coarse, skip) -> act``,
+    ``head(name, x, level, stage) -> (features, act, nc)``: out1 / out2 / out3 + InstanceNorm + tanh, features the tuple that opens the
+    stage's result, act what inner2 reads (stage 2 only, else None), and ``curv(a, b, c)``: the tuple that closes the result.
+    emit(stage_name, stage_tuple): called with stage 1 before inner1 is launched and with stage 2 before inner2 (stage 3 is returned):
+    the coarse stages can start on another stream next to the finer FPN levels.
+    An intermediate goes as soon as its last reader ran: c00 after conv01, d0 and c10 after conv11, d1 and c20 after conv21, c21 and c11
+    after inner1, the stage-2 activation and c01 after inner2; a lateral's output when the next one replaces it."""
+    emit = emit or (lambda name, stage: None)
+    c00, n00 = layers.dyn("conv00", imgs, 0)
+    c01, n01 = layers.dyn("conv01", c00, 0)
+    del c00
+    d0 = layers.down("downsample1", c01)
+    c10, n10 = layers.dyn("conv10", d0, 1)
+    c11, n11 = layers.dyn("conv11", c10, 1)
+    del d0, c10
+    d1 = layers.down("downsample2", c11)
+    c20, n20 = layers.dyn("conv20", d1, 2)
+    c21, n21 = layers.dyn("conv21", c20, 2)
+    del d1, c20
+    fea, _, n22 = layers.head("out1", c21, 2, 1)
+    stage1 = fea + layers.curv(n20, n21, n22)
+    emit("stage1", stage1)
+    x = layers.lateral("inner1", c21, c11)
+    del c21, c11
+    fea, o2, n12 = layers.head("out2", x, 1, 2)
+    stage2 = fea + layers.curv(n10, n11, n12)
+    emit("stage2", stage2)
+    x = layers.lateral("inner2", o2, c01)
+    del o2, c01
+    fea, _, n02 = layers.head("out3", x, 0, 3)
+    return {"stage1": stage1, "stage2": stage2, "stage3": fea + layers.curv(n00, n01, n02)}
+
+
 class _ExactLayers:
     """costreg_unet on the exact-fp32 kernels (one fmaf chain per output), planar volumes [C,D,h,w]."""
 
@@ -528,33 +566,27 @@ class _FeatureRunner:
         net = self.net
 
         def dyn(name: str, dc: DynamicConv):
-            dev = dc.att_convs[0].weight.device
-            for i, k in enumerate(dc.size_kernels):
-                w = torch.cat((dc.convs[i].weight.detach(), dc.att_convs[i].weight.detach()), dim=0)
+            on_gpu, nk = dc.att_convs[0].weight.is_cuda, len(dc.size_kernels)
+            ws = [torch.cat((dc.convs[i].weight.detach(), dc.att_convs[i].weight.detach()), dim=0) for i in range(nk)]
+            for i, w in enumerate(ws):
                 out[f"{name}.w{i}"] = _pack2d(w)
                 if dc.convs[i].bias is not None:
-                    out[f"{name}.b{i}"] = torch.cat((dc.convs[i].bias.detach(), torch.zeros(3, device=dev))).contiguous()
-            if ops.dynconv_sbf_supported(dc.in_c, dc.out_c + 3, dc.size_kernels, 4, fused=USE_FUSED_BLEND) and dc.att_convs[0].weight.is_cuda:
-                out[f"{name}.ws"] = ops.split_pack_dynconv([torch.cat((dc.convs[i].weight.detach(), dc.att_convs[i].weight.detach()), dim=0)
-                                                            for i in range(len(dc.size_kernels))])
+                    out[f"{name}.b{i}"] = torch.cat((dc.convs[i].bias.detach(), torch.zeros(3, device=w.device))).contiguous()
+            sbf = ops.dynconv_sbf_supported(dc.in_c, dc.out_c + 3, dc.size_kernels, 4, fused=USE_FUSED_BLEND) and on_gpu
+            if sbf:
+                out[f"{name}.ws"] = ops.split_pack_dynconv(ws)
                 if ops.USE_SPLIT_F16 and (dc.in_c, tuple(dc.size_kernels)) in ops.DYNCONV_CL_SHAPES:
                     # split-f16 operands of the channels-last kernel (two fp16 terms of w x a power-of-two scale, + 1 / scale)
-                    out[f"{name}.wh"], out[f"{name}.whs"] = ops.split_pack_dynconv(
-                        [torch.cat((dc.convs[i].weight.detach(), dc.att_convs[i].weight.detach()), dim=0) for i in range(len(dc.size_kernels))],
-                        f16=True)
-                if dc.convs[0].bias is not None:
-                    out[f"{name}.bs"] = torch.stack([out[f"{name}.b{i}"] for i in range(len(dc.size_kernels))]).contiguous()
-            if name == "conv00" and USE_SPLIT_BF16 and ops.USE_CONV2D_SBF and dc.size_kernels == (3, 7, 11) and dc.att_convs[0].weight.is_cuda:
+                    out[f"{name}.wh"], out[f"{name}.whs"] = ops.split_pack_dynconv(ws, f16=True)
+            conv00 = name == "conv00" and USE_SPLIT_BF16 and ops.USE_CONV2D_SBF and dc.size_kernels == (3, 7, 11) and on_gpu
+            if conv00:
                 # conv00 on the matrix cores (csrc/feat_cl.hip: tap-pair K-steps for the 3-channel input)
-                out[f"{name}.ws00"] = ops.split_pack_conv00([torch.cat((dc.convs[i].weight.detach(), dc.att_convs[i].weight.detach()), dim=0)
-                                                             for i in range(3)])
+                out[f"{name}.ws00"] = ops.split_pack_conv00(ws)
                 if ops.USE_SPLIT_F16:
-                    out[f"{name}.wh00"], out[f"{name}.whs00"] = ops.split_pack_conv00(
-                        [torch.cat((dc.convs[i].weight.detach(), dc.att_convs[i].weight.detach()), dim=0) for i in range(3)], f16=True)
-                if dc.convs[0].bias is not None:
-                    out[f"{name}.bs"] = torch.stack([out[f"{name}.b{i}"] for i in range(3)]).contiguous()
+                    out[f"{name}.wh00"], out[f"{name}.whs00"] = ops.split_pack_conv00(ws, f16=True)
+            if (sbf or conv00) and dc.convs[0].bias is not None:
+                out[f"{name}.bs"] = torch.stack([out[f"{name}.b{i}"] for i in range(nk)]).contiguous()
             scale, shift = _bn_fold(dc.att_weights[1])
-            nk = len(dc.size_kernels)
             out[f"{name}.m1"] = (dc.att_weights[0].weight.detach().reshape(4, nk) * scale.view(4, 1)).contiguous()
             out[f"{name}.mb"] = shift.contiguous()
             out[f"{name}.m2"] = dc.att_weights[3].weight.detach().reshape(nk, 4).contiguous()
@@ -564,28 +596,24 @@ class _FeatureRunner:
         for name in ("out1", "out2", "out3"):
             dyn(name, getattr(net, name))
         for name in ("downsample1", "downsample2", "inner1", "inner2"):
-            out[f"{name}.w"] = _pack2d(getattr(net, name).conv.weight.detach())
-        # channels-last kernels (feat_cl.hip): [tap][cin][cout] for the stride-2 units, [cin][cout] for the FPN laterals
-        for name in ("downsample1", "downsample2"):
             w = getattr(net, name).conv.weight.detach()
+            out[f"{name}.w"] = _pack2d(w)
+            # channels-last kernels (feat_cl.hip): [cin][cout] for the FPN laterals, [tap][cin][cout] for the stride-2 units
+            if w.shape[2] == 1:
+                out[f"{name}.wt"] = w.reshape(w.shape[0], w.shape[1]).t().contiguous()
+                continue
             out[f"{name}.w9"] = w.permute(2, 3, 1, 0).reshape(9, w.shape[1], w.shape[0]).contiguous()
             if ops.USE_SPLIT_F16 and w.is_cuda and (w.shape[1], w.shape[0]) in ((8, 16), (16, 32)):
                 out[f"{name}.wh"], out[f"{name}.whs"] = ops.split_pack_dynconv([w], f16=True)      # the matrix-core form (split-f16)
-        for name in ("inner1", "inner2"):
-            w = getattr(net, name).conv.weight.detach()
-            out[f"{name}.wt"] = w.reshape(w.shape[0], w.shape[1]).t().contiguous()
         return out
 
-    # A layer output travels as (raw, affine): the un-normalised convolution result plus the [N,C,3] table
-    # (1/std, -mean/std, leaky slope) of its InstanceNorm + LeakyReLU, which the consuming convolutions apply on load
-    # (`cds_conv2d_affine_f32`) - the normalised tensor is never written.  affine = None marks a materialised tensor.
-    def _dynamic(self, p, name: str, dc: DynamicConv, x: Tensor, epi: Tensor, T: float, n_shared: int = 1,
+    @staticmethod
+    def _dynamic(p, name: str, dc: DynamicConv, x: Tensor, epi: Tensor, T: float, n_shared: int = 1,
                  aff: Optional[Tensor] = None, stats_slope: Optional[float] = 0.1):
-        """x [N,Cin,H,W] (with its pending affine), epi CPU [N,2] (pixels at this resolution) ->
+        """One DynamicConv on the planar kernels.  x [N,Cin,H,W] (with its pending affine), epi CPU [N,2] (pixels at this resolution) ->
         (out [N,Cout,H,W], norm_curv [N,H,W]).  n_shared > 1: the first n_shared images are copies of one image (SURVEY
         §8(f)-4): their epipole-independent branch responses are convolved once (image n_shared - 1 stands for all)."""
-        N, Cin, H, W = x.shape
-        nk = len(dc.size_kernels)
+        (N, Cin, H, W), nk = x.shape, len(dc.size_kernels)
         xs = x[n_shared - 1:] if n_shared > 1 else x
         affs = aff[n_shared - 1:].contiguous() if (aff is not None and n_shared > 1) else aff
         fusable = USE_FUSED_BLEND and n_shared == 1 and stats_slope is not None and nk >= 2 and N <= ops.MAX_IMAGES
@@ -603,167 +631,133 @@ class _FeatureRunner:
             for i, k in enumerate(dc.size_kernels):
                 ops.conv2d(xs, p[f"{name}.w{i}"], p.get(f"{name}.b{i}"), dc.out_c + 3, k, 1, (k - 1) // 2, ACT_NONE,
                            out=branches[i], in_affine=affs)
-        return ops.dynconv_blend(branches, p[f"{name}.m1"], p[f"{name}.mb"], p[f"{name}.m2"], epi, T, n_shared,
-                                 stats_slope=stats_slope)
-
-    def _dyn_unit(self, p, name, x, epi, T, n_shared: int = 1, aff: Optional[Tensor] = None):
-        # the blend kernel leaves the InstanceNorm statistics of its output: (raw, affine) without another pass
-        y, nc, _, a = self._dynamic(p, name, getattr(self.net, name).conv, x, epi, T, n_shared, aff)
-        return y, a, nc
-
-    def _plain_unit(self, p, name, x, aff: Optional[Tensor] = None):
-        unit: ConvUnit = getattr(self.net, name)
-        k = unit.conv.kernel_size[0]
-        y = ops.conv2d(x, p[f"{name}.w"], None, unit.conv.out_channels, k, unit.stride, unit.padding, in_affine=aff)
-        return y, ops.instnorm_affine(y, 0.1)
-
-    def _lateral_unit(self, p, name, coarse, a_coarse, skip, a_skip):
-        """FPN lateral: ConvUnit 1x1 over cat(nearest2x(coarse), skip), neither of which is materialised."""
-        unit: ConvUnit = getattr(self.net, name)
-        return ops.conv2d_fpn(coarse, skip, p[f"{name}.w"], unit.conv.out_channels, a_coarse, a_skip, stats_slope=0.1)
-
-    @staticmethod
-    def _final(o: Tensor, st: Tensor, n_chw: int) -> Tuple[Tensor, Optional[Tensor]]:
-        """InstanceNorm + tanh of the stage output (st = its statistics from the blend kernel); the first n_chw images
-        stay [C,h,w] (reference features), the rest are emitted channels-last [h,w,C] (source features, gathered by K1/K3)."""
-        N = o.shape[0]
-        chw = ops.instnorm_apply(o[:n_chw], st[:n_chw], ACT_TANH) if n_chw > 0 else None
-        hwc = ops.instnorm_apply(o[n_chw:], st[n_chw:], ACT_TANH, out_hwc=True) if n_chw < N else None
-        return chw, hwc
+        return ops.dynconv_blend(branches, p[f"{name}.m1"], p[f"{name}.mb"], p[f"{name}.m2"], epi, T, n_shared, stats_slope=stats_slope)
 
     def __call__(self, imgs: Tensor, epipoles: Tensor, T: float, n_chw: Optional[int] = None, n_shared: int = 1, on_stage1=None):
         """imgs [N,3,H,W]; epipoles: one per image in pixels - a CPU tensor [N,2] at full resolution, or the three device tensors [N,2]
-        of the geometry block at full / half / quarter resolution.
+        of the geometry block at full / half / quarter resolution.  on_stage1(stage_name, stage_tuple): feature_pyramid's emit.
         Returns {'stageK': (fea_chw [n_chw,C,h,w] | None, fea_hwc [N-n_chw,h,w,C] | None, nc_sum [N,h,w], |nc| [N,h,w])}."""
         net = self.net
         if net.training:
             raise NotImplementedError("_FeatureRunner is the inference runner (InstanceNorm applied on load, packed weights); "
                                       "in training mode CDSMVSNet.forward uses training.feature_net (autograd ops)")
-        N = imgs.shape[0]
-        if n_chw is None:
-            n_chw = N
-        if N > ops.MAX_IMAGES:
+        if imgs.shape[0] > ops.MAX_IMAGES:
             raise ValueError(f"at most {ops.MAX_IMAGES} images per FeatureNet batch")
         p = net._packed.get(net, self._pack)
         if isinstance(epipoles, (tuple, list)):
-            e0, e1, e2 = epipoles                 # device slices of the call's geometry block (CDSMVSNet.geometry_block)
+            epi = tuple(epipoles)                 # device slices of the call's geometry block (CDSMVSNet.geometry_block)
         else:                                     # direct callers: CPU [N,2] at full resolution, uploaded here
             e0 = epipoles.detach().float().cpu().contiguous()
-            e0, e1, e2 = (ops.geo(e, imgs.device, "epipoles") for e in (e0, e0 / 2, e0 / 4))
-        if USE_FEAT_CL and net.conv00.conv.out_c == 8 and all(f"{nm}.ws" in p for nm in self._CL_LAYERS):
-            return self._call_cl(p, imgs, e0, e1, e2, T, n_chw, n_shared, on_stage1)
-        # conv00 sees the raw images: with n_shared copies of the reference image its branch convolutions (3x3, 7x7,
-        # 11x11) run once for all of them; from conv01 on the inputs differ (the blend depends on the epipole)
-        c00, a00, n00 = self._dyn_unit(p, "conv00", imgs, e0, T, n_shared)
-        c01, a01, n01 = self._dyn_unit(p, "conv01", c00, e0, T, aff=a00)
-        d0, ad0 = self._plain_unit(p, "downsample1", c01, a01)
-        c10, a10, n10 = self._dyn_unit(p, "conv10", d0, e1, T, aff=ad0)
-        c11, a11, n11 = self._dyn_unit(p, "conv11", c10, e1, T, aff=a10)
-        d1, ad1 = self._plain_unit(p, "downsample2", c11, a11)
-        c20, a20, n20 = self._dyn_unit(p, "conv20", d1, e2, T, aff=ad1)
-        c21, a21, n21 = self._dyn_unit(p, "conv21", c20, e2, T, aff=a20)
-
-        out = {}
-        o1, n22, s1, _ = self._dynamic(p, "out1", net.out1, c21, e2, T, aff=a21)
-        out["stage1"] = self._final(o1, s1, n_chw) + ops.curvature_stats(n20, n21, n22)
-        if on_stage1 is not None:          # the coarse stage can start (on another stream) while the finer FPN levels are computed
-            on_stage1("stage1", out["stage1"])
-
-        # FPN: nearest-neighbour up-sampling and concatenation move raw values; the affine tables concatenate alike
-        x, ax = self._lateral_unit(p, "inner1", c21, a21, c11, a11)
-        o2, n12, s2, _ = self._dynamic(p, "out2", net.out2, x, e1, T, aff=ax)
-        o2n = ops.instnorm_apply(o2, s2, ACT_TANH)
-        hwc2 = torch.stack([ops.chw_to_hwc(o2n[i]) for i in range(n_chw, N)]) if n_chw < N else None
-        out["stage2"] = (o2n[:n_chw] if n_chw > 0 else None, hwc2) + ops.curvature_stats(n10, n11, n12)
-        if on_stage1 is not None:
-            on_stage1("stage2", out["stage2"])
-
-        x, ax = self._lateral_unit(p, "inner2", o2n, None, c01, a01)      # o2n is materialised (tanh features)
-        o3, n02, s3, _ = self._dynamic(p, "out3", net.out3, x, e0, T, aff=ax)
-        out["stage3"] = self._final(o3, s3, n_chw) + ops.curvature_stats(n00, n01, n02)
-        return out
+            epi = tuple(ops.geo(e, imgs.device, "epipoles") for e in (e0, e0 / 2, e0 / 4))
+        channels_last = USE_FEAT_CL and net.conv00.conv.out_c == 8 and all(f"{nm}.ws" in p for nm in _ChannelsLastLayers.MATRIX_CORE)
+        n_chw = imgs.shape[0] if n_chw is None else n_chw
+        layers = (_ChannelsLastLayers if channels_last else _PlanarLayers)(net, p, epi, T, n_chw, n_shared)
+        return feature_pyramid(layers, (imgs, None), on_stage1)
 
 
-    _CL_LAYERS = ("conv01", "conv10", "conv11", "conv20", "conv21", "out1", "out2", "out3")
+class _InferenceLayers:
+    """What the two layouts of the inference feature_pyramid share.  A layer output travels as (raw, affine): the un-normalised result
+    plus the [N,C,3] table (1/std, -mean/std, leaky slope) of its InstanceNorm + LeakyReLU, which the consuming convolutions apply on
+    load (`cds_conv2d_affine_f32`) - the normalised tensor is never written; the DynamicConv kernels leave the table next to their output,
+    without another pass.  affine = None marks a materialised tensor (the images, the tanh features).  The first n_chw images' features
+    leave planar [C,h,w] (reference features), the rest channels-last [h,w,C] (source features, gathered by K1 / K3)."""
 
-    def _call_cl(self, p, imgs: Tensor, e0: Tensor, e1: Tensor, e2: Tensor, T: float, n_chw: int, n_shared: int, on_stage1):
-        """The same network on CHANNELS-LAST activations [N,h,w,C] (csrc/feat_cl.hip): staged tile rows are contiguous runs, the
-        DynamicConv kernel stores 16-byte channel quads, the stage outputs leave channels-last for the source views (what K1 / K3
-        gather) and planar for the reference views in the same pass - no transposition kernels."""
-        net = self.net
-        N, _, H, W = imgs.shape
-        # conv00 (3 input channels, kernel sizes 3 / 7 / 11) sees the raw planar images; the n_shared reference copies are convolved
-        # once and blended per copy (its own epipole).  Default: one matrix-core kernel (tap-pair K-steps); CDS_CONV00_MFMA=0: the
-        # VALU branch kernels + a blend kernel that writes channels-last
-        dc = net.conv00.conv
+    def __init__(self, net: FeatureNet, p: Dict[str, Tensor], epi, T: float, n_chw: int, n_shared: int):
+        self.net, self.p, self.epi, self.T, self.n_chw, self.n_shared = net, p, epi, T, n_chw, n_shared
+
+    def dyn(self, name: str, x, level: int):
+        y, nc, _, a = self._dynconv(name, getattr(self.net, name).conv, x, level)
+        return (y, a), nc
+
+    def curv(self, a: Tensor, b: Tensor, c: Tensor):
+        return ops.curvature_stats(a, b, c)
+
+
+class _PlanarLayers(_InferenceLayers):
+    """feature_pyramid on the planar kernels: activations (raw [N,C,h,w], affine)."""
+
+    def _dynconv(self, name: str, dc: DynamicConv, x, level: int):
+        # conv00 sees the raw images: with n_shared copies of the reference image its branch convolutions (3x3, 7x7, 11x11) run once
+        # for all of them; from conv01 on the inputs differ (the blend depends on the epipole)
+        return _FeatureRunner._dynamic(self.p, name, dc, x[0], self.epi[level], self.T, self.n_shared if name == "conv00" else 1, x[1])
+
+    def down(self, name: str, x):
+        unit: ConvUnit = getattr(self.net, name)
+        y = ops.conv2d(x[0], self.p[f"{name}.w"], None, unit.conv.out_channels, unit.conv.kernel_size[0], unit.stride, unit.padding, in_affine=x[1])
+        return y, ops.instnorm_affine(y, 0.1)
+
+    def lateral(self, name: str, coarse, skip):
+        # nearest-neighbour up-sampling and concatenation move raw values (the affine tables concatenate alike): neither is materialised
+        return ops.conv2d_fpn(coarse[0], skip[0], self.p[f"{name}.w"], getattr(self.net, name).conv.out_channels, coarse[1], skip[1], stats_slope=0.1)
+
+    def head(self, name: str, x, level: int, stage: int):
+        o, nc, st, _ = self._dynconv(name, getattr(self.net, name), x, level)
+        n, N = self.n_chw, o.shape[0]
+        if stage == 2:                    # inner2 reads the tanh features of all images, planar and materialised
+            on = ops.instnorm_apply(o, st, ACT_TANH)
+            hwc = torch.stack([ops.chw_to_hwc(on[i]) for i in range(n, N)]) if n < N else None
+            return (on[:n] if n > 0 else None, hwc), (on, None), nc
+        chw = ops.instnorm_apply(o[:n], st[:n], ACT_TANH) if n > 0 else None
+        hwc = ops.instnorm_apply(o[n:], st[n:], ACT_TANH, out_hwc=True) if n < N else None
+        return (chw, hwc), None, nc
+
+
+class _ChannelsLastLayers(_InferenceLayers):
+    """feature_pyramid on CHANNELS-LAST activations (raw [N,h,w,C], affine) (csrc/feat_cl.hip): staged tile rows are contiguous runs, the
+    DynamicConv kernel stores 16-byte channel quads, the stage outputs leave channels-last for the source views (what K1 / K3
+    gather) and planar for the reference views in the same pass - no transposition kernels."""
+
+    MATRIX_CORE = ("conv01", "conv10", "conv11", "conv20", "conv21", "out1", "out2", "out3")       # need their ".ws" operand
+
+    def _operand(self, name: str, x: Tensor, aff: Optional[Tensor], plain: str = ".ws", tag: str = ""):
+        """(operand of the layer's kernel, the split-f16 keywords of its wrapper): the split-f16 operand where it was packed and the input
+        has a known bound, else the `plain` one and no keywords.  A pending affine: InstanceNorm-ed on load, so sqrt(h w) bounds it
+        (Samuelson's inequality; LeakyReLU shrinks); conv00 (tag "00"): the images' largest magnitude (one small reduction)."""
+        p = self.p
+        if not (ops.USE_SPLIT_F16 and f"{name}.wh{tag}" in p and (aff is not None or tag == "00")):
+            return p[name + plain + tag], {}
+        bound = {"in_bound": x.abs().amax().reshape(1)} if aff is None else {"x_bound": float(x.shape[1] * x.shape[2]) ** 0.5}
+        return p[f"{name}.wh{tag}"], {**bound, "w_inv_scale": p[f"{name}.whs{tag}"]}
+
+    def _conv00(self, imgs: Tensor):
+        """conv00 (3 input channels, kernel sizes 3 / 7 / 11) sees the raw planar images; the n_shared reference copies are convolved once and
+        blended per copy (its own epipole).  One matrix-core kernel (tap-pair K-steps); CDS_CONV00_MFMA=0: VALU branches + a blend kernel."""
+        p, dc, n_shared = self.p, self.net.conv00.conv, self.n_shared
+        att = (p["conv00.m1"], p["conv00.mb"], p["conv00.m2"], self.epi[0], self.T, n_shared, 0.1)
         xs = imgs[n_shared - 1:] if n_shared > 1 else imgs
         if "conv00.ws00" in p and USE_CONV00_MFMA:
-            if ops.USE_SPLIT_F16 and "conv00.wh00" in p:      # split-f16: the images' scale from their largest magnitude (one small reduction)
-                xs = xs.contiguous()
-                c00, n00, _, a00 = ops.conv00_cl(xs, p["conv00.wh00"], p.get("conv00.bs"), p["conv00.m1"], p["conv00.mb"], p["conv00.m2"],
-                                                 e0, T, n_shared, 0.1, in_bound=xs.abs().amax().reshape(1), w_inv_scale=p["conv00.whs00"])
-                return self._after_conv00(p, c00, n00, a00, e0, e1, e2, T, n_chw, on_stage1)
-            c00, n00, _, a00 = ops.conv00_cl(xs.contiguous(), p["conv00.ws00"], p.get("conv00.bs"), p["conv00.m1"], p["conv00.mb"],
-                                             p["conv00.m2"], e0, T, n_shared, 0.1)
-            return self._after_conv00(p, c00, n00, a00, e0, e1, e2, T, n_chw, on_stage1)
-        branches = torch.empty((len(dc.size_kernels), xs.shape[0], dc.out_c + 3, H, W), dtype=torch.float32, device=imgs.device)
+            xs = xs.contiguous()
+            w, kw = self._operand("conv00", xs, None, tag="00")
+            return ops.conv00_cl(xs, w, p.get("conv00.bs"), *att, **kw)
+        branches = torch.empty((len(dc.size_kernels), xs.shape[0], dc.out_c + 3) + imgs.shape[2:], dtype=torch.float32, device=imgs.device)
         for i, k in enumerate(dc.size_kernels):
             ops.conv2d(xs, p[f"conv00.w{i}"], p.get(f"conv00.b{i}"), dc.out_c + 3, k, 1, (k - 1) // 2, ACT_NONE, out=branches[i])
-        c00, n00, _, a00 = ops.dynconv_blend_cl(branches, p["conv00.m1"], p["conv00.mb"], p["conv00.m2"], e0, T, n_shared, 0.1)
-        del branches
-        return self._after_conv00(p, c00, n00, a00, e0, e1, e2, T, n_chw, on_stage1)
+        return ops.dynconv_blend_cl(branches, *att)
 
-    def _after_conv00(self, p, c00: Tensor, n00: Tensor, a00: Tensor, e0: Tensor, e1: Tensor, e2: Tensor, T: float, n_chw: int, on_stage1):
-        net = self.net
-        N = c00.shape[0]
+    def _dynconv(self, name: str, dc: DynamicConv, x, level: int):
+        if name == "conv00":
+            return self._conv00(x[0])
+        p = self.p
+        w, kw = self._operand(name, *x)
+        return ops.dynconv_cl(x[0], w, p.get(f"{name}.bs"), dc.size_kernels, p[f"{name}.m1"], p[f"{name}.mb"], p[f"{name}.m2"],
+                              self.epi[level], self.T, 0.1, in_affine=x[1], **kw)
 
-        def dyn(name: str, dc: DynamicConv, x: Tensor, epi: Tensor, aff: Optional[Tensor]):
-            if ops.USE_SPLIT_F16 and f"{name}.wh" in p and aff is not None:
-                # split-f16: the input is InstanceNorm-ed on load, so sqrt(h w) bounds it (Samuelson's inequality; LeakyReLU shrinks)
-                return ops.dynconv_cl(x, p[f"{name}.wh"], p.get(f"{name}.bs"), dc.size_kernels, p[f"{name}.m1"], p[f"{name}.mb"],
-                                      p[f"{name}.m2"], epi, T, 0.1, in_affine=aff, x_bound=float(x.shape[1] * x.shape[2]) ** 0.5,
-                                      w_inv_scale=p[f"{name}.whs"])
-            return ops.dynconv_cl(x, p[f"{name}.ws"], p.get(f"{name}.bs"), dc.size_kernels, p[f"{name}.m1"], p[f"{name}.mb"],
-                                  p[f"{name}.m2"], epi, T, 0.1, in_affine=aff)
+    def down(self, name: str, x):
+        w, kw = self._operand(name, *x, plain=".w9")
+        y = ops.conv2d_k3s2_cl(x[0], None if kw else w, getattr(self.net, name).conv.out_channels, x[1], wsplit=w if kw else None, **kw)
+        return y, ops.instnorm_stats_cl(y, 0.1)[1]
 
-        def down(name: str, x: Tensor, aff: Tensor):
-            if ops.USE_SPLIT_F16 and f"{name}.wh" in p and aff is not None:
-                y = ops.conv2d_k3s2_cl(x, None, getattr(net, name).conv.out_channels, aff, wsplit=p[f"{name}.wh"],
-                                       w_inv_scale=p[f"{name}.whs"], x_bound=float(x.shape[1] * x.shape[2]) ** 0.5)
-                return y, ops.instnorm_stats_cl(y, 0.1)[1]
-            y = ops.conv2d_k3s2_cl(x, p[f"{name}.w9"], getattr(net, name).conv.out_channels, aff)
-            return y, ops.instnorm_stats_cl(y, 0.1)[1]
+    def lateral(self, name: str, coarse, skip):
+        return ops.conv2d_fpn_cl(coarse[0], skip[0], self.p[f"{name}.wt"], getattr(self.net, name).conv.out_channels, coarse[1], skip[1], 0.1)
 
-        c01, n01, _, a01 = dyn("conv01", net.conv01.conv, c00, e0, a00)
-        del c00
-        d0, ad0 = down("downsample1", c01, a01)
-        c10, n10, _, a10 = dyn("conv10", net.conv10.conv, d0, e1, ad0)
-        c11, n11, _, a11 = dyn("conv11", net.conv11.conv, c10, e1, a10)
-        del d0, c10
-        d1, ad1 = down("downsample2", c11, a11)
-        c20, n20, _, a20 = dyn("conv20", net.conv20.conv, d1, e2, ad1)
-        c21, n21, _, a21 = dyn("conv21", net.conv21.conv, c20, e2, a20)
-        del d1, c20
-
-        out = {}
-        o1, n22, s1, _ = dyn("out1", net.out1, c21, e2, a21)
-        hwc, chw = ops.instnorm_apply_cl(o1, s1, ACT_TANH, n_chw, cl_from=n_chw)
-        out["stage1"] = (chw, hwc) + ops.curvature_stats(n20, n21, n22)
-        if on_stage1 is not None:
-            on_stage1("stage1", out["stage1"])
-
-        x, ax = ops.conv2d_fpn_cl(c21, c11, p["inner1.wt"], net.inner1.conv.out_channels, a21, a11, 0.1)
-        o2, n12, s2, _ = dyn("out2", net.out2, x, e1, ax)
-        o2n, chw = ops.instnorm_apply_cl(o2, s2, ACT_TANH, n_chw, cl_from=0)       # all images channels-last: inner2 reads them
-        out["stage2"] = (chw, o2n[n_chw:] if n_chw < N else None) + ops.curvature_stats(n10, n11, n12)
-        if on_stage1 is not None:
-            on_stage1("stage2", out["stage2"])
-
-        x, ax = ops.conv2d_fpn_cl(o2n, c01, p["inner2.wt"], net.inner2.conv.out_channels, None, a01, 0.1)
-        o3, n02, s3, _ = dyn("out3", net.out3, x, e0, ax)
-        hwc, chw = ops.instnorm_apply_cl(o3, s3, ACT_TANH, n_chw, cl_from=n_chw)
-        out["stage3"] = (chw, hwc) + ops.curvature_stats(n00, n01, n02)
-        return out
+    def head(self, name: str, x, level: int, stage: int):
+        o, nc, st, _ = self._dynconv(name, getattr(self.net, name), x, level)
+        n = self.n_chw
+        if stage == 2:                    # all images channels-last: inner2 reads them
+            on, chw = ops.instnorm_apply_cl(o, st, ACT_TANH, n, cl_from=0)
+            return (chw, on[n:] if n < o.shape[0] else None), (on, None), nc
+        hwc, chw = ops.instnorm_apply_cl(o, st, ACT_TANH, n, cl_from=n)
+        return (chw, hwc), None, nc
 
 
 # ------------------------------------------------------------------------------------------------

@@ -18,6 +18,7 @@ import torch
 import torch.nn.functional as F
 
 from . import _scratch, geometry, ops
+from .model import _to_host, feature_pyramid
 
 Tensor = torch.Tensor
 
@@ -78,30 +79,35 @@ def _curv(a: Tensor, b: Tensor, c: Tensor) -> Tuple[Tensor, Tensor]:
     return train2d_ops.CurvatureStats.apply(a, b, c)
 
 
+class _TrainFeatureLayers:
+    """model.feature_pyramid on the autograd ops: activations are tensors [N,C,h,w], a stage's features one tensor."""
+
+    def __init__(self, net, epi: Tensor, T: float, groups: int):
+        self.net, self.epi, self.T, self.groups = net, (epi, epi / 2, epi / 4), T, groups
+
+    def dyn(self, name: str, x: Tensor, level: int):
+        return _unit(getattr(self.net, name), x, self.epi[level], self.T, self.groups)
+
+    def down(self, name: str, x: Tensor) -> Tensor:
+        return _unit(getattr(self.net, name), x, None, self.T)
+
+    def lateral(self, name: str, coarse: Tensor, skip: Tensor) -> Tensor:
+        return _unit(getattr(self.net, name), _cat_up(coarse, skip), None, self.T)
+
+    def head(self, name: str, x: Tensor, level: int, stage: int):
+        o, nc = _dyn(getattr(self.net, name), x, self.epi[level], self.T, self.groups)
+        fea = _in_act(o, tanh=True)
+        return (fea,), fea if stage == 2 else None, nc
+
+    def curv(self, a: Tensor, b: Tensor, c: Tensor):
+        return _curv(a, b, c)
+
+
 def feature_net(net, x: Tensor, epi: Tensor, T: float, groups: int = 1) -> Dict[str, Tuple[Tensor, Tensor, Tensor]]:
     """models/module.py:234-267.  x [N,3,H,W], epi [N,2] -> {'stageK': (fea, nc_sum, |nc|)} batched over N.  groups > 1: x stacks
     that many separate calls of the reference (the only cross-sample operation in FeatureNet is the BatchNorm2d inside each
     DynamicConv's attention MLP: its statistics are then taken per group)."""
-    e0, e1, e2 = epi, epi / 2, epi / 4
-    c00, n00 = _unit(net.conv00, x, e0, T, groups)
-    c01, n01 = _unit(net.conv01, c00, e0, T, groups)
-    d0 = _unit(net.downsample1, c01, None, T)
-    c10, n10 = _unit(net.conv10, d0, e1, T, groups)
-    c11, n11 = _unit(net.conv11, c10, e1, T, groups)
-    d1 = _unit(net.downsample2, c11, None, T)
-    c20, n20 = _unit(net.conv20, d1, e2, T, groups)
-    c21, n21 = _unit(net.conv21, c20, e2, T, groups)
-    out = {}
-    o1, n22 = _dyn(net.out1, c21, e2, T, groups)
-    out["stage1"] = (_in_act(o1, tanh=True), *_curv(n20, n21, n22))
-    t = _unit(net.inner1, _cat_up(c21, c11), None, T)
-    o2, n12 = _dyn(net.out2, t, e1, T, groups)
-    o2 = _in_act(o2, tanh=True)
-    out["stage2"] = (o2, *_curv(n10, n11, n12))
-    t = _unit(net.inner2, _cat_up(o2, c01), None, T)
-    o3, n02 = _dyn(net.out3, t, e0, T, groups)
-    out["stage3"] = (_in_act(o3, tanh=True), *_curv(n00, n01, n02))
-    return out
+    return feature_pyramid(_TrainFeatureLayers(net, epi, T, groups), x)
 
 
 BATCH_FEATURES = os.environ.get("CDS_TRAIN_BATCH_FEATURES", "1") != "0"   # 0 = one FeatureNet call per image of every pair, as the reference
@@ -305,7 +311,6 @@ def train_geometry(model, proj_matrices: Dict[str, Tensor], depth_values: Tensor
     geometry block, uploaded with one asynchronous copy; `forward_train(..., geo=)` then only launches kernels, which is what the
     captured training step (train.CapturedTrainStep) records.  Device inputs are read back here (a synchronisation: keep the cameras
     and depth values on the host, as the data loader delivers them, to let the host run ahead of the GPU)."""
-    from .model import _to_host
     keys = list(proj_matrices.keys())
     host = _to_host([depth_values] + [proj_matrices[k] for k in keys])
     dv, cams = host[0], dict(zip(keys, host[1:]))

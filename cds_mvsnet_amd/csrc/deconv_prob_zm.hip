@@ -22,6 +22,17 @@
 //   half 1 (pz = 0): B1 = cells (dy, dx) in {0,1}^2 of plane a      -> A[0] (py = 0: dy = 1 slots are zero), A[1] (py = 1)
 //   half 2 (pz = 1): B2 = cells (dz, dx) at dy = 0, B3 = at dy = 1  -> A[2] (py = 0) on B2; A[3] on B2 and A[4] on B3 (py = 1)
 // with K-slot g = lane >> 4 of a 32-deep K-step = the cell offset, its 8 values = the 8 channels of the round.
+//
+// prob on the matrix cores (MF, split-f16 only; profiles/tail_prob_mfma.md): the consumers store y x s_y as two fp16 terms (32 B per
+// voxel, the size of the fp32 plane), and the four prob waves run a GEMM over TAPS: one v_mfma_f32_16x16x32_f16 per (output row o,
+// input row o + ky - 1, 16-wide x tile) with N = 16 x positions, K = [y_hi w_hi | y_lo w_hi | y_hi w_lo | spare] over the 8 channels
+// and M row 4 kz' + kx = tap ((kz' + R) mod 3, ky, kx).  The three ky instructions chain in the accumulator; in the result lane group
+// G holds kx = 0, 1, 2 of tap kz = (G + R) mod 3 at its x, so the kx sum is two DPP adds (row_shr:1, row_shl:1; lanes 2..13 of a tile
+// are whole, tiles step by 12) and with R = (q + 1) mod 3 for y plane q group G always adds into the output plane p = q + 1 - kz with
+// p = -G (mod 3): one accumulator register per (row, tile).  The group whose plane is complete stores it and clears.  Summation
+// order: ky in the MFMA chain, kx centre / left / right, then the three planes in arrival order - independent of timing.
+// y layout (MF): [row][term][x parity][slot = (x >> 1) ^ 8 (x & 1)][8 fp16]: the 16-byte operand reads of 16 consecutive x (even
+// origin) touch 16 different 16-byte bank groups, the consumers' 8-byte stores (x = 2 j + px) are 2-way.
 #include "sbf_common.hpp"
 
 namespace {
@@ -45,7 +56,11 @@ struct DPZ {
   static constexpr int NITEM = IY * IX * ROUNDS;     // (cell, round) staging items of one plane
   static constexpr int IPT = (NITEM + PW * 64 - 1) / (PW * 64);      // per producer thread (prologue of a segment)
   static constexpr int IPC = (NITEM + CW * 64 - 1) / (CW * 64);      // per consumer thread (inside the march)
+  // prob on the matrix cores: x tiles of 16 read positions at origin MSTEP * t, whole outputs in lanes 2 .. 13
+  static constexpr int MT = 5, MSTEP = 12;
+  static constexpr int YTERMB = YROWB / 2, YPARB = YTERMB / 2;       // y plane: [row][term][x parity][slot][8] fp16
 };
+static_assert(DPZ::MT * DPZ::MSTEP == 2 * DPZ::CXR && (DPZ::MT - 1) * DPZ::MSTEP + 16 <= DPZ::YX, "prob x tiles");
 static_assert(DPZ::PW * DPZ::PR == 2 * DPZ::CYR, "prob rows");
 static_assert(DPZ::LDS <= 160 * 1024, "LDS budget");
 
@@ -57,21 +72,38 @@ __device__ __forceinline__ float dpz_fma(float d, float w, float acc) {
   return acc;
 }
 
+// The value of the lane one to the left / right inside its row of 16 lanes (DPP row_shr:1 / row_shl:1); 0 where the row ends.
+__device__ __forceinline__ float dpz_row_shr1(float v) {
+  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x111, 0xF, 0xF, true));
+}
+__device__ __forceinline__ float dpz_row_shl1(float v) {
+  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x101, 0xF, 0xF, true));
+}
+
 // F16: the transposed convolution in split-f16 arithmetic (sbf_common.hpp): two fp16 terms of x x (scale from the device bound in_bound),
-// three products per K-step, exact rescaling before the BN shift; prob (VALU, fp32) is unchanged.
+// three products per K-step, exact rescaling before the BN shift; prob stays on the VALU in fp32 unless MF.
 #define DPZ_TERMS(ACC, W, X)                                  \
   do {                                                        \
     if constexpr (F16) { SF16_TERMS(ACC, 0, C::NT, W, X); }   \
     else { SBF_TERMS(ACC, 0, C::NT, W, X); }                  \
   } while (0)
-template <bool F16>
+// MF: prob on the matrix cores (header comment).  pw is then the operand table of ops.split_pack_prob ([3 R][3 ky][64 lanes] x 16 B),
+// p_inv 1 / its scale, and y is scaled by s_y from the bound skip_bound + y_gain * in_bound + max |bias| >= max |y|.
+template <bool F16, bool MF>
 __global__ __launch_bounds__(DPZ::THREADS, 3) void deconv_prob_zm_kernel(
     const float* __restrict__ x, const uint4* __restrict__ wsp, const float* __restrict__ bias, const float* __restrict__ skip,
     const float* __restrict__ pw, float* __restrict__ out, int D, int H, int W, int tiles_x, int ncols, int seg_len,
-    const float* __restrict__ in_bound, float w_inv) {
+    const float* __restrict__ in_bound, float w_inv, const float* __restrict__ skip_bound, float y_gain, float p_inv) {
+  static_assert(F16 || !MF, "the matrix-core prob form exists in split-f16 only");
   using C = DPZ;
   const float xs = F16 ? sf16_scale(in_bound[0]) : 1.0f;
   const float out_mul = F16 ? w_inv / xs : 1.0f;
+  float ys = 1.0f;
+  if constexpr (MF) {
+    float bmax = 0.f;
+    for (int i = 0; i < 8; ++i) bmax = fmaxf(bmax, fabsf(bias[i]));
+    ys = sf16_scale(skip_bound[0] + y_gain * in_bound[0] + bmax);
+  }
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   unsigned char* const inring = lds + C::WB;
   unsigned char* const ybuf = inring + 2 * C::SLOTB;
@@ -131,6 +163,97 @@ __global__ __launch_bounds__(DPZ::THREADS, 3) void deconv_prob_zm_kernel(
           else split_store8(base + s_dst[h], va[h], vb[h]);
         }
     };
+    if constexpr (MF) {
+      // ---- prob on the matrix cores: wave = 3 output rows x MT x tiles; lane = (group g, read position n) ----
+      const int n = lane & 15, g = lane >> 4, rg = wave - C::CW;
+      const uint4* __restrict__ pwm = reinterpret_cast<const uint4*>(pw);
+      BV wa[3][3];                                     // [rotation R][ky]
+#pragma unroll
+      for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int ky = 0; ky < 3; ++ky) wa[r][ky].u = pwm[(r * 3 + ky) * 64 + lane];
+      const int oy0 = ty_i * 2 * C::CYR + C::PR * rg;
+      int b_off[C::MT];                                // operand byte offset inside a y row
+#pragma unroll
+      for (int t = 0; t < C::MT; ++t) {
+        const int xl = C::MSTEP * t + n;               // y-plane x of this lane's read; its output is owned column xl - 2
+        b_off[t] = (g & 1) * C::YTERMB + (xl & 1) * C::YPARB + (((xl >> 1) ^ ((xl & 1) << 3)) << 4);
+      }
+      // outputs: tile t of row oy0 + r is element st_lane of the (wave-uniform) row pointer + MSTEP t, where x < Wo: MSTEP t < st_lim
+      const int ox0 = tx_i * 2 * C::CXR + n - 2;
+      const bool st_ok = g < 3 && n >= 2 && n <= 13;
+      const unsigned st_lane = st_ok ? oy0 * Wo + ox0 : 0;
+      const int st_lim = st_ok ? Wo - ox0 : 0;
+      const float inv = p_inv / ys;
+      float A[C::MT][C::PR];
+#pragma unroll
+      for (int t = 0; t < C::MT; ++t)
+#pragma unroll
+        for (int r = 0; r < C::PR; ++r) A[t][r] = 0.f;
+      const int yrow0 = (C::PR * rg + 1) * C::YROWB;   // first of the PR + 2 input rows
+      auto load_b = [&](BV (&b)[C::PR + 2], const unsigned char* yb, int t) {
+#pragma unroll
+        for (int rho = 0; rho < C::PR + 2; ++rho) b[rho].u = *reinterpret_cast<const uint4*>(yb + rho * C::YROWB + b_off[t]);
+      };
+      auto process = [&](int q, auto rc) {
+        constexpr int R = decltype(rc)::value;
+        const unsigned char* yb = ybuf + (q & 1) * C::YB + yrow0;
+        BV b[2][C::PR + 2];
+        load_b(b[0], yb, 0);
+#pragma unroll
+        for (int t = 0; t < C::MT; ++t) {
+          if (t + 1 < C::MT) load_b(b[(t + 1) & 1], yb, t + 1);
+          f32x4 d[C::PR];
+#pragma unroll
+          for (int r = 0; r < C::PR; ++r) {
+            d[r] = (f32x4){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int ky = 0; ky < 3; ++ky) SF16_MFMA(d[r], wa[R][ky], b[t & 1][r + ky]);
+          }
+#pragma unroll
+          for (int r = 0; r < C::PR; ++r) {
+            float s = d[r][1] + dpz_row_shr1(d[r][0]);       // kx = 1 at x, kx = 0 from x - 1
+            s = s + dpz_row_shl1(d[r][2]);                   // kx = 2 from x + 1
+            A[t][r] = A[t][r] + s;
+          }
+        }
+      };
+      const int ap = qs >> 1;
+      issue(ap);
+      deposit(ap);
+      if (qs & 1) {
+        issue(ap + 1);
+        deposit(ap + 1);
+      }
+      __syncthreads();                            // #0
+      for (int t = qs; t <= te; ++t) {
+        const int q = t - 1;
+        if (q >= qs && q <= qe) {
+          const int R = (q + 1) % 3;
+          if (R == 0) process(q, std::integral_constant<int, 0>());
+          else if (R == 1) process(q, std::integral_constant<int, 1>());
+          else process(q, std::integral_constant<int, 2>());
+        }
+        const int o = t - 2;                        // complete now; its owner is the lane group -o (mod 3)
+        const bool own = g == (3 - (o + 3) % 3) % 3;
+        if (o >= 2 * a0 && o < 2 * a1) {
+          float* po = out + (size_t)o * Ho * Wo;
+#pragma unroll
+          for (int r = 0; r < C::PR; ++r)
+            if (oy0 + r < Ho) {
+#pragma unroll
+              for (int tt = 0; tt < C::MT; ++tt)
+                if (own && C::MSTEP * tt < st_lim) (po + r * Wo + C::MSTEP * tt)[st_lane] = A[tt][r] * inv;
+            }
+        }
+#pragma unroll
+        for (int tt = 0; tt < C::MT; ++tt)
+#pragma unroll
+          for (int r = 0; r < C::PR; ++r) A[tt][r] = own ? 0.f : A[tt][r];
+        __syncthreads();
+      }
+      return;
+    }
     // ---- prob: lane = x column c of the owned 60, wave = 3 output rows ----
     const int c = ptid & 63, rg = ptid >> 6;
     const int ox = tx_i * 2 * C::CXR + c;
@@ -249,7 +372,9 @@ __global__ __launch_bounds__(DPZ::THREADS, 3) void deconv_prob_zm_kernel(
       sk_off[py][q] = (xv >= 0 && xv < Wo && yv >= 0 && yv < Ho) ? (yv * Wo + xv) * 8 + co : -1;
     }
   const bool border = X0 < 0 || X0 + C::CXC > W || Y0 < 0 || Y0 + C::CYC > H;   // workgroup-uniform: only then is y masked
-  const int y_off = (2 * wave) * C::YROWB + (g & 1) * C::YHALFB + (2 * j + px) * 16;   // + py * YROWB + q * 32 * 16
+  // fp32 y: + py * YROWB + q * 32 * 16; MF (fp16 terms, x = 32 q + 2 j + px): hi at + py * YROWB + q * 16 * 16, lo one YTERMB further
+  const int y_off = MF ? (2 * wave) * C::YROWB + px * C::YPARB + ((j ^ (px << 3)) << 4) + (g & 1) * 8
+                       : (2 * wave) * C::YROWB + (g & 1) * C::YHALFB + (2 * j + px) * 16;
   const size_t zstride = (size_t)Ho * Wo * 8;
   float4 sk0[2][C::NT], sk1[2][C::NT];    // [py][q] of the even / odd half-steps
   auto load_skip = [&](float4 (&sk)[2][C::NT], int t) {
@@ -290,7 +415,16 @@ __global__ __launch_bounds__(DPZ::THREADS, 3) void deconv_prob_zm_kernel(
         const float4 s4 = sk[py][q];
         float4 o = make_float4(s4.x + fmaxf(a.x, 0.f), s4.y + fmaxf(a.y, 0.f), s4.z + fmaxf(a.z, 0.f), s4.w + fmaxf(a.w, 0.f));
         if (border && sk_off[py][q] < 0) o = make_float4(0.f, 0.f, 0.f, 0.f);
-        *reinterpret_cast<float4*>(yb + py * C::YROWB + q * 32 * 16) = o;
+        if constexpr (MF) {
+          uint32_t h0, l0, h1, l1;
+          split2_f16(o.x, o.y, ys, h0, l0);
+          split2_f16(o.z, o.w, ys, h1, l1);
+          unsigned char* yp = yb + py * C::YROWB + q * 16 * 16;
+          *reinterpret_cast<uint2*>(yp) = make_uint2(h0, h1);
+          *reinterpret_cast<uint2*>(yp + C::YTERMB) = make_uint2(l0, l1);
+        } else {
+          *reinterpret_cast<float4*>(yb + py * C::YROWB + q * 32 * 16) = o;
+        }
       }
   };
   // ---- input staging inside the march: plane t / 2 + 1 is loaded at the start of every EVEN half-step t (its slot held plane
@@ -391,8 +525,10 @@ __global__ __launch_bounds__(DPZ::THREADS, 3) void deconv_prob_zm_kernel(
 // conv11 + residual + prob in one launch.  x [D][H][W][16] channels-last input cells, skip [2D][2H][2W][8] channels-last (conv0's
 // output), weight_split from ops.split_pack_deconv_prob (int16 [2][5][3][64][8]), bias [8] (BN shift), prob_table from
 // ops.pack_prob_table (float [3 kx][2 halves][3 ky][3 kz][4]); out [2D][2H][2W] fp32.
+// skip_bound given: prob_table is the operand table of ops.split_pack_prob and prob runs on the matrix cores (split-f16 only).
 static int dpz_entry(const float* x, const void* weight_split, const float* bias, const float* skip, const float* prob_table, float* out,
-                     int D, int H, int W, const float* in_bound, float w_inv, void* stream) {
+                     int D, int H, int W, const float* in_bound, float w_inv, void* stream, const float* skip_bound = nullptr,
+                     float y_gain = 0.f, float p_inv = 1.f) {
   if (!x || !weight_split || !bias || !skip || !prob_table || !out || D < 1 || H < 1 || W < 1) return CDS_EINVAL;
   if ((long)2 * H * 2 * W * 8 >= (1l << 31) || (long)H * W * 16 >= (1l << 31)) return CDS_EINVAL;   // in-plane offsets are 32-bit
   using C = DPZ;
@@ -413,18 +549,27 @@ static int dpz_entry(const float* x, const void* weight_split, const float* bias
   if (nseg_env > 0) best = min(nseg_env, D);
   const int seg_len = cds_ceil_div(D, best);
   const int nseg = cds_ceil_div(D, seg_len);
+  if (skip_bound) {
+    static std::atomic<unsigned long long> lds_ok_m{0};
+    if (int e_lds = cds_allow_lds(reinterpret_cast<const void*>(deconv_prob_zm_kernel<true, true>), 160 * 1024, lds_ok_m)) return e_lds;
+    hipLaunchKernelGGL((deconv_prob_zm_kernel<true, true>), dim3(ncols * nseg), dim3(C::THREADS), C::LDS, st, x,
+                       reinterpret_cast<const uint4*>(weight_split), bias, skip, prob_table, out, D, H, W, tiles_x, ncols, seg_len, in_bound,
+                       w_inv, skip_bound, y_gain, p_inv);
+    return cds_launch_status();
+  }
   if (in_bound) {
     static std::atomic<unsigned long long> lds_ok_h{0};
-    if (int e_lds = cds_allow_lds(reinterpret_cast<const void*>(deconv_prob_zm_kernel<true>), 160 * 1024, lds_ok_h)) return e_lds;
-    hipLaunchKernelGGL(deconv_prob_zm_kernel<true>, dim3(ncols * nseg), dim3(C::THREADS), C::LDS, st, x,
+    if (int e_lds = cds_allow_lds(reinterpret_cast<const void*>(deconv_prob_zm_kernel<true, false>), 160 * 1024, lds_ok_h)) return e_lds;
+    hipLaunchKernelGGL((deconv_prob_zm_kernel<true, false>), dim3(ncols * nseg), dim3(C::THREADS), C::LDS, st, x,
                        reinterpret_cast<const uint4*>(weight_split), bias, skip, prob_table, out, D, H, W, tiles_x, ncols, seg_len, in_bound,
-                       w_inv);
+                       w_inv, nullptr, 0.f, 1.f);
     return cds_launch_status();
   }
   static std::atomic<unsigned long long> lds_ok{0};
-  if (int e_lds = cds_allow_lds(reinterpret_cast<const void*>(deconv_prob_zm_kernel<false>), 160 * 1024, lds_ok)) return e_lds;
-  hipLaunchKernelGGL(deconv_prob_zm_kernel<false>, dim3(ncols * nseg), dim3(C::THREADS), C::LDS, st, x,
-                     reinterpret_cast<const uint4*>(weight_split), bias, skip, prob_table, out, D, H, W, tiles_x, ncols, seg_len, nullptr, 1.0f);
+  if (int e_lds = cds_allow_lds(reinterpret_cast<const void*>(deconv_prob_zm_kernel<false, false>), 160 * 1024, lds_ok)) return e_lds;
+  hipLaunchKernelGGL((deconv_prob_zm_kernel<false, false>), dim3(ncols * nseg), dim3(C::THREADS), C::LDS, st, x,
+                     reinterpret_cast<const uint4*>(weight_split), bias, skip, prob_table, out, D, H, W, tiles_x, ncols, seg_len, nullptr, 1.0f,
+                     nullptr, 0.f, 1.f);
   return cds_launch_status();
 }
 
@@ -440,4 +585,20 @@ extern "C" int cds_deconv_prob_zm_sf16_f32(const float* x, const void* weight_sp
                                            float w_inv_scale, void* stream) {
   if (!in_bound || !(w_inv_scale > 0.f)) return CDS_EINVAL;
   return dpz_entry(x, weight_split, bias, skip, prob_table, out, D, H, W, in_bound, w_inv_scale, stream);
+}
+
+// The split-f16 tail with prob on the matrix cores as well.  prob_table from ops.pack_prob_table and prob_mfma / p_inv_scale from
+// ops.split_pack_prob (fp16 (hi, lo) operands [3][3][64][8] and 1 / their scale); skip_bound a DEVICE scalar >= max |skip| (conv0's
+// out_bound), y_gain >= max over cout of the sum of |folded conv11 weight|: skip_bound + y_gain * in_bound + max |bias| bounds the
+// volume between the two layers, which is what its fp16 terms are scaled by.  CDS_DPZ_PROB_MFMA=0 (A/B knob, read per launch) runs
+// prob on the VALU from prob_table instead: the kernel of cds_deconv_prob_zm_sf16_f32.
+extern "C" int cds_deconv_prob_zm_sf16_mfma_f32(const float* x, const void* weight_split, const float* bias, const float* skip,
+                                                const float* prob_table, const void* prob_mfma, float* out, int D, int H, int W,
+                                                const float* in_bound, float w_inv_scale, const float* skip_bound, float y_gain,
+                                                float p_inv_scale, void* stream) {
+  if (!in_bound || !(w_inv_scale > 0.f) || !prob_mfma || !skip_bound || !(y_gain >= 0.f) || !(p_inv_scale > 0.f)) return CDS_EINVAL;
+  const char* e = getenv("CDS_DPZ_PROB_MFMA");
+  if (e && atoi(e) == 0) return dpz_entry(x, weight_split, bias, skip, prob_table, out, D, H, W, in_bound, w_inv_scale, stream);
+  return dpz_entry(x, weight_split, bias, skip, static_cast<const float*>(prob_mfma), out, D, H, W, in_bound, w_inv_scale, stream,
+                   skip_bound, y_gain, p_inv_scale);
 }

@@ -331,6 +331,7 @@ class SplitLayers:
         self.p, self.kernels, self.in_bound = p, kernels, None
         if bound is not None and ops.USE_SPLIT_F16 and all(name + ".wh" in p for name in kernels):
             self.in_bound, self.slots, self.used = bound, torch.zeros((16,), dtype=torch.float32, device=bound.device), 0
+            self.bounds: Dict[str, Tensor] = {}      # layer -> the slot it published max |output| in
 
     def _layer(self, name: str, publish: bool = True):
         """(packer of the layer's kernel, operand, bias, the split-f16 keywords of its wrapper)."""
@@ -339,7 +340,7 @@ class SplitLayers:
             return packer, self.p[name + key], self.p[name + ".b"], {}
         kw = {"in_bound": self.in_bound, "w_inv_scale": self.p[name + ".whs"]}
         if publish:
-            self.in_bound = kw["out_bound"] = self.slots[self.used:self.used + 1]
+            self.in_bound = kw["out_bound"] = self.bounds[name] = self.slots[self.used:self.used + 1]
             self.used += 1
         return packer, self.p[name + ".wh"], self.p[name + ".b"], kw
 
@@ -356,6 +357,10 @@ class SplitLayers:
     def tail(self, x: Tensor, skip: Tensor, refresh) -> Tensor:
         # conv11 + the conv0 residual + prob: one z-marching kernel, the 8-channel volume between them never reaches HBM
         _, w, b, kw = self._layer("conv11", publish=False)
+        if kw and "prob.wm" in self.p:
+            # split-f16: prob on the matrix cores too; skip is conv0's output, whose bound is in its slot
+            kw.update(prob_mfma=self.p["prob.wm"], prob_inv_scale=self.p["prob.wms"], skip_bound=self.bounds["conv0"],
+                      y_gain=self.p["conv11.gain"])
         return ops.deconv_prob_zm(x, w, b, skip, self.p["prob.tab"], **kw)
 
 
@@ -419,6 +424,10 @@ class CostRegNet(_PackedHolder):
         out["prob.w"] = w.reshape(w.shape[0], 27, 1).contiguous()
         if sbf:
             out["prob.tab"] = ops.pack_prob_table(self.prob.weight)
+            if "conv11.wh" in out:
+                # prob on the matrix cores of the fused tail: its operands and the gain that bounds conv11's output
+                out["prob.wm"], out["prob.wms"] = ops.split_pack_prob(self.prob.weight, f16=True)
+                out["conv11.gain"] = ops.deconv_prob_gain(out["conv11.wh"], out["conv11.whs"])
         return out
 
     def split_bf16_supported(self) -> bool:

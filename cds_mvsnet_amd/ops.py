@@ -694,10 +694,55 @@ def pack_prob_table(w: Tensor) -> Tensor:
     return w.detach().float()[0].reshape(2, 4, 3, 3, 3).permute(4, 0, 3, 2, 1).contiguous()   # [h][i][kz][ky][kx] -> [kx][h][ky][kz][i]
 
 
+def split_pack_prob(w: Tensor, f16: bool = True) -> Tuple[Tensor, float]:
+    """prob weight [1,8,3,3,3] -> the matrix operands of prob as a GEMM over taps (csrc/deconv_prob_zm.hip): per rotation r and ky one
+    16 x 32 operand in MFMA lane order (lane = 16 k-group + row, 8 fp16 each): row 4 kz + kx holds tap ((kz + r) mod 3, ky, kx), rows
+    3, 7, 11 and 12 - 15 are zero; the k-groups are w_hi | w_hi | w_lo | 0 over the 8 channels, multiplying y_hi | y_lo | y_hi | spare.
+    w s = hi + lo (+ <= 2^-22 relative) for the power of two s that puts max |w| into (2^14, 2^15].  -> (int16 [3][3][64][8], 1 / s)."""
+    if tuple(w.shape) != (1, 8, 3, 3, 3):
+        raise ValueError("split_pack_prob: Conv3d weight [1,8,3,3,3]")
+    if not f16:
+        raise ValueError("split_pack_prob: the matrix-core form of prob exists in split-f16 arithmetic only")
+    wf = w.detach().float()[0]                                                      # [c][kz][ky][kx]
+    rows = torch.zeros((3, 3, 16, 8), dtype=torch.float32, device=w.device)         # [r][ky][row][c]
+    for r in range(3):
+        for kz in range(3):
+            rows[r, :, 4 * kz:4 * kz + 3] = wf[:, (kz + r) % 3].permute(1, 2, 0)    # [ky][kx][c]
+    split, inv = _split2_f16(rows)                                                  # [r][ky][(hi, lo, unused)][16][8]
+    terms = split.view(torch.float16)
+    hi, lo = terms[:, :, 0], terms[:, :, 1]
+    return torch.stack((hi, hi, lo, torch.zeros_like(hi)), dim=2).reshape(3, 3, 64, 8).contiguous().view(torch.int16), inv
+
+
+def deconv_prob_gain(wsplit: Tensor, w_inv_scale: float) -> float:
+    """A gain of conv11 from its split-f16 operand (split_pack_deconv_prob(..., f16=True)): max over the matrix rows (x parity, cout) of
+    the sum of |w| over every operand, K slot and input channel, so that |conv11(x)| <= gain * max |x| + max |shift|.  Every output
+    voxel sees a subset of these taps: the bound is up to ~4x loose, which costs nothing (csrc/deconv_prob_zm.hip)."""
+    t = wsplit.view(torch.float16).float()                                          # [rd][operand][term][16 g + row][ci]
+    a = (t[:, :, 0] + t[:, :, 1]).reshape(2, 5, 4, 16, 8).abs()
+    return float(a.sum(dim=(0, 1, 2, 4)).max()) * float(w_inv_scale)
+
+
+def _tail_prob_operands(wsplit: Tensor, w_inv_scale: float, skip: Tensor, prob_table: Tensor) -> dict:
+    """What a split-f16 deconv_prob_zm call that does not bring them needs for prob on the matrix cores, derived from what it does
+    bring: the operands from the table (the same 216 weights), the gain from the conv11 operand and max |skip| with one pass over skip.
+    The model passes them instead (packed once, conv0's published bound); both ways give the same bits."""
+    w = prob_table.reshape(3, 2, 3, 3, 4).permute(1, 4, 3, 2, 0).reshape(1, 8, 3, 3, 3)     # [kx][h][ky][kz][i] -> [1][c][kz][ky][kx]
+    wm, wms = split_pack_prob(w, f16=True)
+    return {"prob_mfma": wm, "prob_inv_scale": wms, "skip_bound": skip.abs().amax().reshape(1),
+            "y_gain": deconv_prob_gain(wsplit, w_inv_scale)}
+
+
 def deconv_prob_zm(x_cl: Tensor, wsplit: Tensor, bias: Tensor, skip: Tensor, prob_table: Tensor, in_bound: Optional[Tensor] = None,
-                   w_inv_scale: float = 1.0) -> Tensor:
+                   w_inv_scale: float = 1.0, prob_mfma: Optional[Tensor] = None, prob_inv_scale: float = 1.0,
+                   skip_bound: Optional[Tensor] = None, y_gain: float = 0.0) -> Tensor:
     """conv11 + residual + prob in one launch: x_cl [D,H,W,16], skip [2D,2H,2W,8] channels-last -> [2D,2H,2W].  in_bound given: the
-    transposed convolution in split-f16 arithmetic (wsplit / w_inv_scale from split_pack_deconv_prob(..., f16=True))."""
+    transposed convolution in split-f16 arithmetic (wsplit / w_inv_scale from split_pack_deconv_prob(..., f16=True)).
+    prob_mfma given (split-f16 only): prob on the matrix cores as well, on the operands prob_mfma / prob_inv_scale of split_pack_prob;
+    skip_bound a 1-element device tensor >= max |skip| and y_gain = deconv_prob_gain(wsplit, w_inv_scale) bound the volume between
+    the two layers.  A split-f16 call without them derives them (_tail_prob_operands: a pass over skip and two host reads), so that
+    the form and the bits of a call do not depend on who packed its operands; the split-bf16 call keeps prob on the VALU, and
+    CDS_DPZ_PROB_MFMA=0 (read per launch by the library) does so for split-f16 too."""
     D, H, W, Cin = x_cl.shape
     if Cin != 16 or tuple(skip.shape) != (2 * D, 2 * H, 2 * W, 8):
         raise ValueError("deconv_prob_zm: x [D,H,W,16] and skip [2D,2H,2W,8]")
@@ -708,9 +753,22 @@ def deconv_prob_zm(x_cl: Tensor, wsplit: Tensor, bias: Tensor, skip: Tensor, pro
     out = torch.empty((2 * D, 2 * H, 2 * W), dtype=torch.float32, device=x_cl.device)
     lib = _lib.load()
     args = (_dev(x_cl, "x"), wsplit.data_ptr(), _dev(bias, "bias"), _dev(skip, "skip"), _dev(prob_table, "prob_table"), out.data_ptr(), D, H, W)
-    if in_bound is not None:
-        check(lib.cds_deconv_prob_zm_sf16_f32(*args, _dev(in_bound, "in_bound"), float(w_inv_scale), _stream(x_cl)),
-              "cds_deconv_prob_zm_sf16_f32")
+    # the two split-f16 entries: prob on the VALU (reached with CDS_DPZ_PROB_MFMA=0) / on the matrix cores
+    sf16, sf16_mfma = lib.cds_deconv_prob_zm_sf16_f32, lib.cds_deconv_prob_zm_sf16_mfma_f32
+    valu = os.environ.get("CDS_DPZ_PROB_MFMA", "1").strip() == "0"      # the library reads the knob as well; here it spares the derivation
+    if in_bound is not None and prob_mfma is None and not valu:
+        d = _tail_prob_operands(wsplit, w_inv_scale, skip, prob_table)
+        prob_mfma, prob_inv_scale, skip_bound, y_gain = d["prob_mfma"], d["prob_inv_scale"], d["skip_bound"], d["y_gain"]
+    if prob_mfma is not None:
+        if in_bound is None or skip_bound is None:
+            raise ValueError("deconv_prob_zm: prob on the matrix cores needs the split-f16 form (in_bound) and skip_bound")
+        if prob_mfma.dtype != torch.int16 or not prob_mfma.is_cuda or not prob_mfma.is_contiguous() or prob_mfma.numel() != 3 * 3 * 64 * 8:
+            raise ValueError("deconv_prob_zm: prob_mfma must be the contiguous int16 device tensor from split_pack_prob")
+        check(sf16_mfma(*args[:5], prob_mfma.data_ptr(), *args[5:], _dev(in_bound, "in_bound"), float(w_inv_scale),
+                        _dev(skip_bound, "skip_bound"), float(y_gain), float(prob_inv_scale), _stream(x_cl)),
+              "cds_deconv_prob_zm_sf16_mfma_f32")
+    elif in_bound is not None:
+        check(sf16(*args, _dev(in_bound, "in_bound"), float(w_inv_scale), _stream(x_cl)), "cds_deconv_prob_zm_sf16_f32")
     else:
         check(lib.cds_deconv_prob_zm_f32(*args, _stream(x_cl)), "cds_deconv_prob_zm_f32")
     return out

@@ -260,7 +260,7 @@ int cds_deconv3d_zm_sf16_f32(const float* x, const void* weight_cls, const float
  * (models/module.py:125-160, :495), the residual `conv0 + conv11(x)` (:498) and prob = Conv3d(8 -> 1, k3, p1, bias=False)
  * (:499).  x [D][H][W][16] channels-last input cells, skip [2D][2H][2W][8] channels-last, out [2D][2H][2W] fp32.  The 8-channel
  * full-resolution volume between the two layers stays in LDS (z-marching workgroups, csrc/deconv_prob_zm.hip); the transposed
- * convolution runs in split-bf16 arithmetic on the matrix cores, prob in packed fp32 on the VALU.
+ * convolution runs in split-bf16 arithmetic on the matrix cores, prob in plain fp32 on the VALU.
  * weight_split from ops.split_pack_deconv_prob (int16 [2][5][3][64][8]), bias [8], prob_table from ops.pack_prob_table
  * (float [3 kx][2][3 ky][3 kz][4]). */
 int cds_deconv_prob_zm_f32(const float* x, const void* weight_split, const float* bias, const float* skip,
@@ -269,6 +269,14 @@ int cds_deconv_prob_zm_f32(const float* x, const void* weight_split, const float
  * in_bound: DEVICE scalar >= max |x|, conv9's out_bound). */
 int cds_deconv_prob_zm_sf16_f32(const float* x, const void* weight_split, const float* bias, const float* skip, const float* prob_table,
                                 float* out, int D, int H, int W, const float* in_bound, float w_inv_scale, void* stream);
+/* The split-f16 tail with prob on the matrix cores too: the consumers keep the volume between the layers as two fp16 terms, the prob
+ * waves run a tap-expanded GEMM on it (csrc/deconv_prob_zm.hip).  prob_mfma / p_inv_scale from ops.split_pack_prob (int16 [3][3][64][8]
+ * and 1 / scale); skip_bound: DEVICE scalar >= max |skip| (conv0's out_bound); y_gain >= max over cout of sum |folded conv11 weight| (ops.deconv_prob_gain).
+ * CDS_DPZ_PROB_MFMA=0 (read per launch) runs prob on the VALU from prob_table: the kernel of cds_deconv_prob_zm_sf16_f32. */
+int cds_deconv_prob_zm_sf16_mfma_f32(const float* x, const void* weight_split, const float* bias, const float* skip,
+                                     const float* prob_table, const void* prob_mfma, float* out, int D, int H, int W,
+                                     const float* in_bound, float w_inv_scale, const float* skip_bound, float y_gain, float p_inv_scale,
+                                     void* stream);
 
 
 /*

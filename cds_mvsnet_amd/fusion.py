@@ -18,14 +18,21 @@ D2HC-RMVSNet popularised; no outside implementation was available to compare aga
     python -m cds_mvsnet_amd.fusion --testpath <scenes> --outdir <out> --testlist <list> [--filter_method normal|dynamic]
         [--conf 0,0,0] [--thres_disp 1.0] [--thres_view 3] [--dyn_dist_base 0.25] [--dyn_rel_base 0.000769] [--dyn_views 2,10]
 
+        [--normals [--normal_radius 2] [--normal_jump 0.01] [--normal_min_pts 6]] [--merge_voxel SIZE [--merge_min_points K]]
+
 re-fuses saved depth maps (``<out>/<scan>/``, pairs from ``<scenes>/<scan>/pair.txt``) into ``<out>/<scan>.ply`` without
 running the network again.
+
+``--normals`` and ``--merge_voxel`` make the cloud usable outside this project: every point gets the oriented
+normal of its reference view's depth map (``cds_depth_normals_f32``; it faces that camera), and the concatenation of the views,
+in which a surface seen by ten views is written ten times, is merged to one point per occupied voxel (``cds_voxel_merge_f32``).
+With either option the views' points stay on the device until the scan is merged and are downloaded once.
 """
 from __future__ import annotations
 
 import argparse
 import os
-from typing import Dict, List, Sequence, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -100,16 +107,25 @@ def fuse_view_dynamic(ref_depth: torch.Tensor, ref_conf: torch.Tensor, ref_cam: 
     return out
 
 
-def write_ply(path: str, points: np.ndarray, colors: np.ndarray) -> None:
+_PLY_XYZ = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
+_PLY_NORMAL = [("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")]
+_PLY_RGB = [("red", "u1"), ("green", "u1"), ("blue", "u1")]
+
+
+def write_ply(path: str, points: np.ndarray, colors: np.ndarray, normals: Optional[np.ndarray] = None) -> None:
     """Binary little-endian PLY with x,y,z float32 + red,green,blue uint8 vertices (what plyfile writes in
-    test.py:370-382)."""
+    test.py:370-382).  With ``normals`` [N,3] the vertex is x y z nx ny nz red green blue, the order Open3D and MeshLab write."""
     n = int(points.shape[0])
-    rec = np.empty(n, dtype=[("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1")])
+    if normals is not None and tuple(normals.shape) != (n, 3):
+        raise ValueError(f"write_ply: {tuple(normals.shape)} normals for {n} points")
+    fields = _PLY_XYZ + (_PLY_NORMAL if normals is not None else []) + _PLY_RGB
+    rec = np.empty(n, dtype=fields)
     rec["x"], rec["y"], rec["z"] = points[:, 0], points[:, 1], points[:, 2]
+    if normals is not None:
+        rec["nx"], rec["ny"], rec["nz"] = normals[:, 0], normals[:, 1], normals[:, 2]
     rec["red"], rec["green"], rec["blue"] = colors[:, 0], colors[:, 1], colors[:, 2]
     header = ("ply\nformat binary_little_endian 1.0\n" f"element vertex {n}\n"
-              "property float x\nproperty float y\nproperty float z\n"
-              "property uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n")
+              + "".join(f"property {'float' if t == '<f4' else 'uchar'} {name}\n" for name, t in fields) + "end_header\n")
     with open(path, "wb") as f:
         f.write(header.encode("ascii"))
         rec.tofile(f)
@@ -129,6 +145,32 @@ def read_ply(path: str) -> Tuple[np.ndarray, np.ndarray]:
     return np.stack([rec["x"], rec["y"], rec["z"]], -1), np.stack([rec["red"], rec["green"], rec["blue"]], -1)
 
 
+def read_ply_full(path: str) -> Tuple[np.ndarray, np.ndarray, Optional[np.ndarray]]:
+    """A PLY written by :func:`write_ply`, with or without normals -> (points float32 [N,3], colors uint8 [N,3],
+    normals float32 [N,3] | None)."""
+    with open(path, "rb") as f:
+        n, props = None, []
+        while True:
+            line = f.readline()
+            if not line:
+                raise ValueError(f"{path}: PLY header without end_header")
+            tok = line.decode("ascii").split()
+            if tok[:2] == ["element", "vertex"]:
+                n = int(tok[2])
+            elif tok[:1] == ["property"]:
+                props.append((tok[1], tok[2]))
+            elif tok[:1] == ["end_header"]:
+                break
+        plain = [("float", c) for c in "xyz"] + [("uchar", c) for c in ("red", "green", "blue")]
+        full = plain[:3] + [("float", c) for c in ("nx", "ny", "nz")] + plain[3:]
+        if n is None or props not in (plain, full):
+            raise ValueError(f"{path}: not a vertex layout that write_ply produces: {props}")
+        has_n = props == full
+        rec = np.frombuffer(f.read(), dtype=_PLY_XYZ + (_PLY_NORMAL if has_n else []) + _PLY_RGB, count=n)
+    return (np.stack([rec["x"], rec["y"], rec["z"]], -1), np.stack([rec["red"], rec["green"], rec["blue"]], -1),
+            np.stack([rec["nx"], rec["ny"], rec["nz"]], -1) if has_n else None)
+
+
 def _load_view(scan_folder: str, vid: int):
     from PIL import Image
     depth = read_pfm(os.path.join(scan_folder, "depth_est", f"{vid:08d}.pfm"))[0]
@@ -141,15 +183,32 @@ def _load_view(scan_folder: str, vid: int):
 def filter_depth(pair_folder: str, scan_folder: str, plyfilename: str, conf: Sequence[float] = (0.0, 0.0, 0.0),
                  thres_disp: float = 1.0, thres_view: int = 3, n_src_views: int = 10, device: str = "cuda",
                  verbose: bool = False, method: str = "normal", dist_base: float = DYN_DIST_BASE,
-                 rel_base: float = DYN_REL_BASE, n_views: Sequence[int] = DYN_VIEWS) -> Dict[str, float]:
+                 rel_base: float = DYN_REL_BASE, n_views: Sequence[int] = DYN_VIEWS, normals: bool = False,
+                 normal_radius: int = 2, normal_jump: float = 0.01, normal_min_pts: int = 6,
+                 merge_voxel: Optional[float] = None, merge_min_points: int = 1) -> Dict[str, float]:
     """The reference's ``filter_depth`` for one scan: -> PLY at ``plyfilename`` and mean photo/geo/final mask rates.
     ``method="dynamic"`` fuses with :func:`fuse_view_dynamic` (``conf``, ``dist_base``, ``rel_base``, ``n_views``;
     ``thres_disp`` / ``thres_view`` are not used) and also returns ``admitted_at``: {n: share of the reference pixels
-    admitted at level n}, averaged over the reference views (their sum is the geometric mask rate)."""
+    admitted at level n}, averaged over the reference views (their sum is the geometric mask rate).
+
+    ``normals``: every point carries the normal of its reference view's ``depth_est`` map (:func:`ops.depth_normals` with
+    ``normal_radius`` / ``normal_jump`` / ``normal_min_pts``; only pixels whose three confidences exceed ``conf`` enter a fit).
+    A kept pixel without a normal is dropped; ``no_normal`` is the dropped share of the otherwise kept pixels of the scan
+    (``mean_final_mask`` still describes the fusion mask, before that).  ``merge_voxel``: the scan's points are merged to one per
+    occupied voxel of that side (:func:`pointcloud.merge_voxels`), voxels with fewer than ``merge_min_points`` points dropped;
+    ``points`` then counts the merged cloud and ``merged_from`` the points that went in.  With either option the views' points
+    stay on the device until the scan is done; with neither, nothing changes."""
     if method not in ("normal", "dynamic"):
         raise ValueError(f"filter_depth: method must be 'normal' or 'dynamic', got {method!r}")
+    cloud = bool(normals) or merge_voxel is not None
+    if merge_voxel is not None and not (float(merge_voxel) > 0 and np.isfinite(float(merge_voxel))):
+        raise ValueError(f"filter_depth: merge_voxel must be positive, got {merge_voxel}")
     pairs = read_pair_file(os.path.join(pair_folder, "pair.txt"))
     cache: Dict[int, tuple] = {}
+    dev_pts: List[torch.Tensor] = []       # the device-resident path of normals / merge_voxel: per view [k,3] points,
+    dev_col: List[torch.Tensor] = []       # uint8 colours, normals and two counts (kept by the fusion, kept with a normal)
+    dev_nrm: List[torch.Tensor] = []
+    dev_cnt: List[torch.Tensor] = []
 
     def view(vid):
         if vid not in cache:
@@ -177,6 +236,19 @@ def filter_depth(pair_folder: str, scan_folder: str, plyfilename: str, conf: Seq
             out = fuse_view(rd, rc, rcam, torch.stack([s[0] for s in sv]), torch.stack([s[1] for s in sv]),
                             torch.stack([s[2] for s in sv]), conf, thres_disp, thres_view)
         keep = out["mask"] > 0.5
+        if cloud:
+            kept = keep.sum()
+            if normals:
+                th = torch.tensor([float(c) for c in conf], dtype=torch.float32, device=rc.device).view(3, 1, 1)
+                nrm, ok = ops.depth_normals(rd, rcam[1, :3, :3], rcam[0], valid=(rc > th).all(0), radius=normal_radius,
+                                            jump=normal_jump, min_pts=normal_min_pts)
+                keep = keep & (ok > 0)
+                dev_nrm.append(nrm[:, keep].t().contiguous())
+            dev_pts.append(out["points"][:, keep].t().contiguous())
+            img = torch.from_numpy(np.ascontiguousarray(rimg())).to(device)
+            dev_col.append((img[keep] * 255).to(torch.uint8))
+            dev_cnt.append(torch.stack([kept, keep.sum(), torch.as_tensor(keep.numel(), device=kept.device)]))
+            continue
         pts = out["points"][:, keep].t().contiguous().cpu().numpy()
         img = torch.from_numpy(np.ascontiguousarray(rimg())).to(device)            # [h,w,3]
         col = (img[keep] * 255).to(torch.uint8).cpu().numpy()
@@ -185,17 +257,74 @@ def filter_depth(pair_folder: str, scan_folder: str, plyfilename: str, conf: Seq
         rates.append(float(keep.float().mean()))
         if verbose:
             print(f"processing {scan_folder}, ref-view{ref:02d}, final-mask:{rates[-1]:.4f}")
-    p_all = np.concatenate(pts_all, 0) if pts_all else np.zeros((0, 3), np.float32)
-    c_all = np.concatenate(col_all, 0) if col_all else np.zeros((0, 3), np.uint8)
-    write_ply(plyfilename, p_all, c_all)
-    info = {"points": int(p_all.shape[0]), "mean_final_mask": float(np.mean(rates)) if rates else 0.0}
+    if cloud:
+        info = _finish_cloud(plyfilename, dev_pts, dev_col, dev_nrm if normals else None, dev_cnt, merge_voxel,
+                             merge_min_points, device, verbose, scan_folder)
+    else:
+        p_all = np.concatenate(pts_all, 0) if pts_all else np.zeros((0, 3), np.float32)
+        c_all = np.concatenate(col_all, 0) if col_all else np.zeros((0, 3), np.uint8)
+        write_ply(plyfilename, p_all, c_all)
+        info = {"points": int(p_all.shape[0]), "mean_final_mask": float(np.mean(rates)) if rates else 0.0}
     if method == "dynamic":
         share = np.mean(hist, 0) if hist else np.zeros(int(n_views[1]) + 1)
         info["admitted_at"] = {n: float(share[n]) for n in range(int(n_views[0]), int(n_views[1]) + 1)}
     return info
 
 
+def _finish_cloud(plyfilename, dev_pts, dev_col, dev_nrm, dev_cnt, merge_voxel, merge_min_points, device, verbose,
+                  scan_folder) -> Dict[str, float]:
+    """The end of the device-resident path of :func:`filter_depth`: concatenate the views, merge once, download once."""
+    from .pointcloud import merge_voxels
+    pts = torch.cat(dev_pts) if dev_pts else torch.zeros((0, 3), dtype=torch.float32, device=device)
+    col = torch.cat(dev_col) if dev_col else torch.zeros((0, 3), dtype=torch.uint8, device=device)
+    nrm = None
+    if dev_nrm is not None:
+        nrm = torch.cat(dev_nrm) if dev_nrm else torch.zeros((0, 3), dtype=torch.float32, device=device)
+    cnt = torch.stack(dev_cnt).cpu().numpy().astype(np.float64) if dev_cnt else np.zeros((0, 3))    # kept, with normal, pixels
+    if verbose:
+        for k, with_n, px in cnt:
+            print(f"processing {scan_folder}, final-mask:{k / px:.4f}, with a normal:{with_n / px:.4f}")
+    info = {"points": int(pts.shape[0]), "mean_final_mask": float(np.mean(cnt[:, 0] / cnt[:, 2])) if len(cnt) else 0.0}
+    if dev_nrm is not None:
+        kept = float(cnt[:, 0].sum())
+        info["no_normal"] = float((kept - cnt[:, 1].sum()) / kept) if kept > 0 else 0.0
+    if merge_voxel is not None:
+        m = merge_voxels(pts, col, float(merge_voxel), normals=nrm, min_points=merge_min_points)
+        info["merged_from"] = info["points"]
+        pts, col, nrm = m["points"], m["colors"], m["normals"]
+        info["points"] = int(pts.shape[0])
+    write_ply(plyfilename, pts.cpu().numpy(), col.cpu().numpy(), None if nrm is None else nrm.cpu().numpy())
+    return info
+
+
 # --------------------------------------------------------------------------------------------------------------- CLI
+def add_cloud_args(ap: argparse.ArgumentParser, normals: bool = True) -> None:
+    """The options of DESIGN §1.8, shared by the fusion command lines (gipuma takes the merge only)."""
+    if normals:
+        ap.add_argument("--normals", action="store_true",
+                        help="write nx ny nz: the oriented normal of each point, from its reference view's depth map")
+        ap.add_argument("--normal_radius", type=int, default=2, help="normals: window radius in pixels, 1..4")
+        ap.add_argument("--normal_jump", type=float, default=0.01,
+                        help="normals: a neighbour enters the fit when its depth is within this share of the centre's")
+        ap.add_argument("--normal_min_pts", type=int, default=6, help="normals: pixels a fit needs, 3..(2 radius + 1)^2")
+    ap.add_argument("--merge_voxel", type=float, default=None, metavar="SIZE",
+                    help="merge the fused cloud to one point per occupied voxel of this side (world units)")
+    ap.add_argument("--merge_min_points", type=int, default=1, metavar="K",
+                    help="--merge_voxel: drop voxels with fewer than K points")
+
+
+def cloud_kwargs(args: argparse.Namespace) -> dict:
+    """The arguments of :func:`add_cloud_args` as keyword arguments of :func:`filter_depth`."""
+    return dict(normals=args.normals, normal_radius=args.normal_radius, normal_jump=args.normal_jump,
+                normal_min_pts=args.normal_min_pts, merge_voxel=args.merge_voxel, merge_min_points=args.merge_min_points)
+
+
+def format_cloud(info: Dict[str, float]) -> str:
+    """", no normal 1.2%, merged from 25700000" for the keys the options of DESIGN §1.8 add; "" without them."""
+    text = f", no normal {100.0 * info['no_normal']:.1f}%" if "no_normal" in info else ""
+    return text + (f", merged from {info['merged_from']}" if "merged_from" in info else "")
+
+
 def _floats(text: str, n: int, what: str) -> List[float]:
     vals = [float(v) for v in text.split(",")]
     if len(vals) != n:
@@ -221,6 +350,7 @@ def parse_args(argv=None) -> argparse.Namespace:
     ap.add_argument("--dyn_rel_base", type=float, default=DYN_REL_BASE, help="dynamic: relative depth difference per level")
     ap.add_argument("--dyn_views", default="2,10", help="dynamic: n_min,n_max")
     ap.add_argument("--device", default="cuda")
+    add_cloud_args(ap)
     args = ap.parse_args(argv)
     args.conf = _floats(args.conf, 3, "--conf")
     args.dyn_views = tuple(int(v) for v in _floats(args.dyn_views, 2, "--dyn_views"))
@@ -236,9 +366,11 @@ def main(argv=None) -> Dict[str, Dict[str, float]]:
         info = filter_depth(os.path.join(args.testpath, scan), os.path.join(args.outdir, scan),
                             os.path.join(args.outdir, f"{scan}.ply"), conf=args.conf, thres_disp=args.thres_disp,
                             thres_view=args.thres_view, device=args.device, method=args.filter_method,
-                            dist_base=args.dyn_dist_base, rel_base=args.dyn_rel_base, n_views=args.dyn_views)
+                            dist_base=args.dyn_dist_base, rel_base=args.dyn_rel_base, n_views=args.dyn_views,
+                            **cloud_kwargs(args))
         out[scan] = info
         extra = f", admitted at {format_admitted(info['admitted_at'])}" if "admitted_at" in info else ""
+        extra += format_cloud(info)
         print(f"{scan}.ply: {info['points']} points, final mask {info['mean_final_mask']:.3f}{extra}", flush=True)
     return out
 

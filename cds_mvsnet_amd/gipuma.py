@@ -40,7 +40,7 @@ import argparse
 import os
 import shutil
 import struct
-from typing import Dict, List, Sequence, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -161,14 +161,22 @@ def load_scan(scan_folder: str) -> Dict[str, np.ndarray]:
 
 def filter_scan(scan_folder: str, plyfilename: str, prob_threshold: Sequence[float] = (0.0, 0.0, 0.0),
                 disp_threshold: float = 0.2, num_consistent: int = 3, depth_min: float = DEPTH_MIN,
-                depth_max: float = DEPTH_MAX, device: str = "cuda") -> Dict[str, int]:
-    """Fuse one ``infer`` scan folder into a PLY at ``plyfilename`` (steps 1-4). -> {"points", "views"}."""
+                depth_max: float = DEPTH_MAX, device: str = "cuda", merge_voxel: Optional[float] = None,
+                merge_min_points: int = 1) -> Dict[str, int]:
+    """Fuse one ``infer`` scan folder into a PLY at ``plyfilename`` (steps 1-4). -> {"points", "views"}.  ``merge_voxel``: the
+    emitted cloud is merged to one point per occupied voxel of that side, voxels with fewer than ``merge_min_points`` points
+    dropped (:func:`pointcloud.merge_voxels`); the dict then also has "merged_from"."""
     s = load_scan(scan_folder)
     out = fuse_views(torch.from_numpy(s["depths"]).to(device), torch.from_numpy(s["confs"]).to(device), s["cams"],
                      torch.from_numpy(s["images"]).to(device), prob_threshold, disp_threshold, num_consistent, depth_min,
                      depth_max)
+    info = {"points": int(out["points"].shape[0]), "views": int(len(s["ids"]))}
+    if merge_voxel is not None:
+        from .pointcloud import merge_voxels
+        out = merge_voxels(out["points"], out["colors"], float(merge_voxel), min_points=merge_min_points)
+        info = {"points": int(out["points"].shape[0]), "views": info["views"], "merged_from": info["points"]}
     write_ply(plyfilename, out["points"].cpu().numpy(), out["colors"].cpu().numpy())
-    return {"points": int(out["points"].shape[0]), "views": int(len(s["ids"]))}
+    return info
 
 
 def write_dmb(path: str, image: np.ndarray) -> None:
@@ -238,6 +246,8 @@ def parse_args(argv=None) -> argparse.Namespace:
     ap.add_argument("--num_consistent", type=int, default=3)
     ap.add_argument("--export_fusibile", action="store_true",
                     help="also write fusibile's inputs (depth_est/*_prob_filtered.pfm, points_mvsnet/)")
+    from .fusion import add_cloud_args
+    add_cloud_args(ap, normals=False)          # normals are not implemented for this method
     args = ap.parse_args(argv)
     args.prob_threshold = _thresholds(args.prob_threshold)
     return args
@@ -253,8 +263,9 @@ def main(argv=None) -> Dict[str, Dict[str, int]]:
         if args.export_fusibile:
             export_fusibile_inputs(folder, args.prob_threshold)
         out[scan] = filter_scan(folder, os.path.join(args.outdir, f"{scan}.ply"), args.prob_threshold, args.disp_threshold,
-                                args.num_consistent)
-        print(f"{scan}.ply: {out[scan]['points']} points from {out[scan]['views']} views", flush=True)
+                                args.num_consistent, merge_voxel=args.merge_voxel, merge_min_points=args.merge_min_points)
+        merged = f", merged from {out[scan]['merged_from']}" if "merged_from" in out[scan] else ""
+        print(f"{scan}.ply: {out[scan]['points']} points from {out[scan]['views']} views{merged}", flush=True)
     return out
 
 

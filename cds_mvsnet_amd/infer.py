@@ -10,7 +10,8 @@ the reference views `idx % world == rank` (independent depth maps, no collective
 `images/%08d.jpg`, ready for the fusion step.  `--fuse` then writes `<out>/<scan>.ply` with the normal fusion (fusion.py) or,
 with `--filter_method gipuma`, the gipuma-style one (gipuma.py; `--prob_threshold`, `--disp_threshold`, `--num_consistent`),
 or, with `--filter_method dynamic`, the dynamic consistency check (fusion.py; `--conf`, `--dyn_dist_base`, `--dyn_rel_base`,
-`--dyn_views`).
+`--dyn_views`).  `--normals` (`--normal_radius`, `--normal_jump`, `--normal_min_pts`; not for gipuma) adds each point's oriented
+normal and `--merge_voxel SIZE` (`--merge_min_points K`) merges the scan to one point per occupied voxel.
 `--save_stages` also writes the three stages' own depth maps, `<out>/<scan>/depth_stage{1,2,3}/%08d.pfm`, at their resolutions
 (what evaluations/precision.py scores stage by stage; `python -m cds_mvsnet_amd.depth_eval --folders ...`).
 
@@ -218,7 +219,7 @@ def run(args) -> float:
     print(f"[{rank}] average time ({what}): {avg:.4f} s over {len(times)} depth maps")
     if args.fuse:
         # step 2 of the reference's test.py (pcd_filter, test.py:386-396): scans are independent -> shard over ranks
-        from .fusion import filter_depth, format_admitted
+        from .fusion import cloud_kwargs, filter_depth, format_admitted, format_cloud
         from .gipuma import filter_scan
         if world > 1:  # every rank's depth maps must be on disk before any scan is fused
             if not torch.distributed.is_initialized():
@@ -231,22 +232,26 @@ def run(args) -> float:
                 # the reference's gipuma_filter (test.py:419-426) without fusibile: cds_mvsnet_amd.gipuma
                 info = filter_scan(os.path.join(args.outdir, scan), os.path.join(args.outdir, f"{scan}.ply"),
                                    prob_threshold=[float(p) for p in args.prob_threshold.split(",")],
-                                   disp_threshold=args.disp_threshold, num_consistent=args.num_consistent, device=str(dev))
-                print(f"[{rank}] {scan}.ply: {info['points']} points from {info['views']} views (gipuma)", flush=True)
+                                   disp_threshold=args.disp_threshold, num_consistent=args.num_consistent, device=str(dev),
+                                   merge_voxel=args.merge_voxel, merge_min_points=args.merge_min_points)
+                print(f"[{rank}] {scan}.ply: {info['points']} points from {info['views']} views{format_cloud(info)} (gipuma)",
+                      flush=True)
                 continue
             if args.filter_method == "dynamic":
                 # the dynamic consistency check: one setting for every scene, thresholds graded by view count
                 info = filter_depth(os.path.join(args.testpath, scan), os.path.join(args.outdir, scan),
                                     os.path.join(args.outdir, f"{scan}.ply"), conf=[float(c) for c in args.conf.split(",")],
                                     device=str(dev), method="dynamic", dist_base=args.dyn_dist_base,
-                                    rel_base=args.dyn_rel_base, n_views=[int(v) for v in args.dyn_views.split(",")])
+                                    rel_base=args.dyn_rel_base, n_views=[int(v) for v in args.dyn_views.split(",")],
+                                    **cloud_kwargs(args))
                 print(f"[{rank}] {scan}.ply: {info['points']} points, final mask {info['mean_final_mask']:.3f}, admitted at "
-                      f"{format_admitted(info['admitted_at'])} (dynamic)", flush=True)
+                      f"{format_admitted(info['admitted_at'])}{format_cloud(info)} (dynamic)", flush=True)
                 continue
             info = filter_depth(os.path.join(args.testpath, scan), os.path.join(args.outdir, scan),
                                 os.path.join(args.outdir, f"{scan}.ply"), conf=[float(c) for c in args.conf.split(",")],
-                                thres_disp=args.thres_disp, thres_view=args.thres_view, device=str(dev))
-            print(f"[{rank}] {scan}.ply: {info['points']} points, final mask {info['mean_final_mask']:.3f}", flush=True)
+                                thres_disp=args.thres_disp, thres_view=args.thres_view, device=str(dev), **cloud_kwargs(args))
+            print(f"[{rank}] {scan}.ply: {info['points']} points, final mask {info['mean_final_mask']:.3f}{format_cloud(info)}",
+                  flush=True)
     return avg
 
 
@@ -293,7 +298,13 @@ def parse_args(argv=None) -> argparse.Namespace:
     ap.add_argument("--dyn_rel_base", type=float, default=1.0 / 1300.0, help="dynamic: relative depth difference per level")
     ap.add_argument("--dyn_views", default="2,10", metavar="n_min,n_max",
                     help="dynamic: a pixel is kept when n views agree at level n for some n in this range")
-    return ap.parse_args(argv)
+    from .fusion import add_cloud_args
+    add_cloud_args(ap)
+    args = ap.parse_args(argv)
+    if args.normals and args.filter_method == "gipuma":
+        ap.error("--normals is not implemented for --filter_method gipuma (its fused point is an average over views); "
+                 "use normal or dynamic")
+    return args
 
 
 def main(argv=None):

@@ -1431,6 +1431,35 @@ def depth_fusion_dynamic(ref_depth: Tensor, ref_conf: Tensor, src_depths: Tensor
     return fused, mask, points, admit, levels
 
 
+def depth_normals(depth: Tensor, K, E, valid: Optional[Tensor] = None, radius: int = 2, jump: float = 0.01, min_pts: int = 6):
+    """One oriented world-frame normal per pixel of a z-depth map: the inverse-depth plane fit of cds_depth_normals_f32 (rule:
+    include/cds_mvsnet_hip.h).  depth [h,w] (device), K [3,3] and E [4,4] world -> camera (any device; they go to
+    the kernel from the host), valid [h,w] uint8 / bool on the device or None (all valid); a neighbour enters a pixel's fit when
+    its depth is within ``jump`` (relative) of the centre's; at least ``min_pts`` of the (2 radius + 1)^2 must.
+    -> (normals [3,h,w] float32, ok [h,w] uint8); normals are (0,0,0) where ok is 0."""
+    if depth.dim() != 2:
+        raise ValueError(f"depth_normals: depth must be [h,w], got {tuple(depth.shape)}")
+    h, w = depth.shape
+    K = torch.as_tensor(K).detach().to("cpu", torch.float32)
+    E = torch.as_tensor(E).detach().to("cpu", torch.float32)
+    if tuple(K.shape) != (3, 3) or tuple(E.shape) != (4, 4):
+        raise ValueError(f"depth_normals: K must be [3,3] and E [4,4], got {tuple(K.shape)}, {tuple(E.shape)}")
+    cam = torch.cat([K.reshape(9), E.reshape(16)]).contiguous()
+    vptr = None
+    if valid is not None:
+        if valid.dtype == torch.bool:
+            valid = valid.view(torch.uint8)
+        if tuple(valid.shape) != (h, w):
+            raise ValueError(f"depth_normals: valid must be [{h},{w}], got {tuple(valid.shape)}")
+        vptr = _dev_int(valid, torch.uint8, "valid")
+    normals = torch.empty((3, h, w), dtype=torch.float32, device=depth.device)
+    ok = torch.empty((h, w), dtype=torch.uint8, device=depth.device)
+    check(_lib.load().cds_depth_normals_f32(_dev(depth, "depth"), vptr, _host(cam, "cam"), h, w, int(radius), float(jump),
+                                            int(min_pts), normals.data_ptr(), ok.data_ptr(), _stream(depth)),
+          "cds_depth_normals_f32")
+    return normals, ok
+
+
 def _refine_range(lo, hi, device) -> Tensor:
     """(depth_min, depth_max, interval) of the Refinement kernels: a 3-element device tensor (geometry block) with hi None, or two
     Python floats = limits that are already in interval units (interval 1: module.py's network on its own)."""

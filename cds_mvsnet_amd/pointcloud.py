@@ -1,5 +1,6 @@
 """Point-cloud primitives of the DTU and Tanks and Temples evaluations on the GPU: capped nearest-neighbour distances (with
-or without the index of the neighbour), greedy thinning to a minimum spacing, and a PLY vertex reader.
+or without the index of the neighbour), greedy thinning to a minimum spacing, voxel grouping with the merge of a fused cloud
+to one attributed point per voxel (``csrc/cloud.hip``), and a PLY vertex reader.
 
 The hot paths are the HIP kernels of ``csrc/pointcloud.hip`` and ``csrc/registration.hip`` (``include/cds_mvsnet_hip.h``): a
 sparse uniform grid with 64-bit cell keys and a hash table, queried one point per lane.  torch is used for device memory
@@ -99,6 +100,92 @@ def _offsets(counts: Tensor) -> Tensor:
     out = torch.zeros(counts.numel() + 1, dtype=torch.int32, device=counts.device)
     out[1:] = torch.cumsum(counts, 0).to(torch.int32)
     return out
+
+
+def voxel_groups(points: Tensor, voxel: float, what: str = "voxel_groups"):
+    """The occupied voxels of side ``voxel`` of ``points`` [N,3] (N >= 1, float32, device), Open3D's frame: origin
+    ``o = float32(min - voxel / 2)`` per axis, voxel index ``floorf((p - o) / voxel)`` in fp32 (cds_grid_keys_f32), the grid's
+    key packing.  -> (perm int64 [N]: the input indices sorted by key, stable; start int32 [V+1]: voxel v holds
+    perm[start[v]:start[v+1]]; keys int64 [V] ascending; counts int64 [V]).  What cds_voxel_mean_f32 and cds_voxel_merge_f32
+    take."""
+    if not (voxel > 0 and math.isfinite(voxel)):
+        raise ValueError(f"{what}: voxel must be positive, got {voxel}")
+    n = points.shape[0]
+    lo, hi = torch.aminmax(points, dim=0)
+    lo, hi = lo.double().cpu().numpy(), hi.double().cpu().numpy()
+    if not (np.isfinite(lo).all() and np.isfinite(hi).all()):
+        raise ValueError(f"{what}: points must be finite")
+    origin = (lo - 0.5 * float(voxel)).astype(np.float32)
+    dims = np.floor((hi - origin.astype(np.float64)) / float(np.float32(voxel))).astype(np.int64) + 2
+    if int(dims.max()) > _MAX_AXIS:
+        raise ValueError(f"{what}: {int(dims.max())} voxels along one axis, at most {_MAX_AXIS}")
+    frame = torch.tensor([*origin.tolist(), float(voxel), 0.0, *dims.tolist()], dtype=torch.float32)
+    keys = torch.empty(n, dtype=torch.int64, device=points.device)
+    check(_lib.load().cds_grid_keys_f32(points.data_ptr(), n, frame.data_ptr(), keys.data_ptr(), _stream(points)),
+          "cds_grid_keys_f32")
+    skeys, perm = torch.sort(keys, stable=True)
+    ukeys, counts = torch.unique_consecutive(skeys, return_counts=True)
+    return perm, _offsets(counts), ukeys, counts
+
+
+def pack_colors(colors: Tensor) -> Tensor:
+    """uint8 [N,3] (r, g, b) -> int32 [N] holding r | g << 8 | b << 16 (gipuma's packing; the bytes r g b 0 in memory)."""
+    out = torch.zeros((colors.shape[0], 4), dtype=torch.uint8, device=colors.device)
+    out[:, :3] = colors
+    return out.view(torch.int32).reshape(-1)
+
+
+def unpack_colors(packed: Tensor) -> Tensor:
+    """The inverse of :func:`pack_colors`: int32 [N] -> uint8 [N,3]."""
+    return packed.contiguous().view(torch.uint8).view(-1, 4)[:, :3].contiguous()
+
+
+def merge_voxels(points: Tensor, colors: Tensor, voxel: float, normals: Optional[Tensor] = None, min_points: int = 1) -> dict:
+    """One attributed point per occupied voxel of side ``voxel`` (cds_voxel_merge_f32): points [N,3] float32,
+    colors uint8 [N,3] (or already packed, int32 [N]), normals [N,3] float32 or None, all on the device.  Position: the float64
+    mean in input order, rounded once, the same bits as ``tt_eval.voxel_down_sample``; colour: the mean per channel rounded
+    half up; normal: the float64 sum of the voxel's normals, normalised ((0,0,0) if they cancel); count: the voxel's points.
+    Voxels with fewer than ``min_points`` points are dropped (isolated points are mostly outliers).  The output is in ascending
+    voxel-key order, ``voxel_down_sample``'s frame and ordering.
+    -> {"points" float32 [V,3], "colors" uint8 [V,3], "normals" float32 [V,3] | None, "counts" int32 [V]}."""
+    points = _points(points, "points")
+    n, dev = points.shape[0], points.device
+    if not (voxel > 0 and math.isfinite(voxel)):
+        raise ValueError(f"merge_voxels: voxel must be positive, got {voxel}")
+    if int(min_points) < 1:
+        raise ValueError(f"merge_voxels: min_points must be >= 1, got {min_points}")
+    if colors.dtype == torch.uint8 and tuple(colors.shape) == (n, 3):
+        packed = pack_colors(colors.to(dev))
+    elif colors.dtype == torch.int32 and tuple(colors.shape) == (n,):
+        packed = colors.contiguous()
+    else:
+        raise ValueError(f"merge_voxels: colors must be uint8 [{n},3] or packed int32 [{n}], got {colors.dtype} "
+                         f"{tuple(colors.shape)}")
+    if not packed.is_cuda:
+        raise RuntimeError("merge_voxels: colors must be a ROCm (cuda) tensor; there is no CPU fallback")
+    if normals is not None:
+        normals = _points(normals, "normals")
+        if normals.shape[0] != n:
+            raise ValueError(f"merge_voxels: {normals.shape[0]} normals for {n} points")
+    if n == 0:
+        return {"points": points.clone(), "colors": torch.zeros((0, 3), dtype=torch.uint8, device=dev),
+                "normals": None if normals is None else normals.clone(), "counts": torch.zeros(0, dtype=torch.int32, device=dev)}
+    perm, start, ukeys, _ = voxel_groups(points, voxel, "merge_voxels")
+    v = ukeys.numel()
+    out_p = torch.empty((v, 3), dtype=torch.float32, device=dev)
+    out_c = torch.empty(v, dtype=torch.int32, device=dev)
+    out_n = torch.empty((v, 3), dtype=torch.float32, device=dev) if normals is not None else None
+    out_k = torch.empty(v, dtype=torch.int32, device=dev)
+    check(_lib.load().cds_voxel_merge_f32(points.data_ptr(), packed.data_ptr(), normals.data_ptr() if normals is not None else None,
+                                          n, perm.data_ptr(), start.data_ptr(), v, out_p.data_ptr(), out_c.data_ptr(),
+                                          out_n.data_ptr() if out_n is not None else None, out_k.data_ptr(), _stream(points)),
+          "cds_voxel_merge_f32")
+    out_c = unpack_colors(out_c)
+    if int(min_points) > 1:
+        keep = out_k >= int(min_points)
+        out_p, out_c, out_k = out_p[keep], out_c[keep], out_k[keep]
+        out_n = out_n[keep] if out_n is not None else None
+    return {"points": out_p, "colors": out_c, "normals": out_n, "counts": out_k}
 
 
 def default_cell(points: Tensor) -> float:

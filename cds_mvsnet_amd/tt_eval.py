@@ -42,7 +42,7 @@ from . import _lib, mvs_io
 from ._lib import check
 from .dtu_eval import _Phases, _mean
 from .ops import _stream
-from .pointcloud import _MAX_AXIS, PointGrid, _grid_args, _offsets, _points, index_grid, nearest_distance, read_ply_points
+from .pointcloud import PointGrid, _grid_args, _points, index_grid, nearest_distance, read_ply_points, voxel_groups
 
 Tensor = torch.Tensor
 
@@ -148,24 +148,10 @@ def voxel_down_sample(points: Tensor, voxel: float, return_info: bool = False):
     if n == 0:
         e = torch.zeros(0, dtype=torch.int64, device=dev)
         return (points.clone(), e, e.clone()) if return_info else points.clone()
-    lib = _lib.load()
-    lo, hi = torch.aminmax(points, dim=0)
-    lo, hi = lo.double().cpu().numpy(), hi.double().cpu().numpy()
-    if not (np.isfinite(lo).all() and np.isfinite(hi).all()):
-        raise ValueError("voxel_down_sample: points must be finite")
-    origin = (lo - 0.5 * float(voxel)).astype(np.float32)
-    dims = np.floor((hi - origin.astype(np.float64)) / float(np.float32(voxel))).astype(np.int64) + 2
-    if int(dims.max()) > _MAX_AXIS:
-        raise ValueError(f"voxel_down_sample: {int(dims.max())} voxels along one axis, at most {_MAX_AXIS}")
-    frame = torch.tensor([*origin.tolist(), float(voxel), 0.0, *dims.tolist()], dtype=torch.float32)
-    stream = _stream(points)
-    keys = torch.empty(n, dtype=torch.int64, device=dev)
-    check(lib.cds_grid_keys_f32(points.data_ptr(), n, frame.data_ptr(), keys.data_ptr(), stream), "cds_grid_keys_f32")
-    skeys, perm = torch.sort(keys, stable=True)
-    ukeys, counts = torch.unique_consecutive(skeys, return_counts=True)
-    start = _offsets(counts)
+    perm, start, ukeys, counts = voxel_groups(points, voxel, "voxel_down_sample")
     out = torch.empty((ukeys.numel(), 3), dtype=torch.float32, device=dev)
-    check(lib.cds_voxel_mean_f32(points.data_ptr(), n, perm.data_ptr(), start.data_ptr(), ukeys.numel(), out.data_ptr(), stream),
+    check(_lib.load().cds_voxel_mean_f32(points.data_ptr(), n, perm.data_ptr(), start.data_ptr(), ukeys.numel(), out.data_ptr(),
+                                         _stream(points)),
           "cds_voxel_mean_f32")
     return (out, ukeys, counts) if return_info else out
 

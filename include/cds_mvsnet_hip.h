@@ -551,6 +551,52 @@ int cds_depth_fusion_dynamic_f32(const float* ref_depth, const float* ref_conf, 
                                  void* stream);
 
 /*
+ * Oriented normals of a depth map (csrc/cloud.hip): an inverse-depth plane fit.  For a plane n.X = rho and
+ * X = z Kinv p, 1/z is an affine function g.p of the pixel p = (px, py, 1) and n is proportional to K^T g, so the fit is exact on
+ * planes, closed form, and needs no eigen-solver.
+ *   depth [h][w] fp32 (z-depth); valid [h][w] uint8 or NULL (every pixel valid); cam_host: 25 floats on the HOST, K 3x3 then
+ *   E 4x4 (world -> camera), row-major; normals [3][h][w] fp32 (world frame); ok [h][w] uint8 (0 / 1)
+ * The rule, per pixel (x, y):
+ *   1. A pixel is valid when valid is non-zero there and its depth is finite and > 0.  A centre that is not valid gets ok = 0 and
+ *      the normal (0, 0, 0).
+ *   2. Window: the centre has depth dc.  Visit dy = -r..r (outer), dx = -r..r (inner).  A neighbour q enters the fit when it is
+ *      inside the image, valid, and |dq - dc| <= jump * dc, evaluated in fp64 from the fp32 values (the difference and the
+ *      product of two floats are exact in fp64: the decision is reproducible bit for bit).
+ *   3. Over the entering pixels, v = (dx, dy, 1): S = sum v v^T (integers), b = sum v * (1.0 / (double)dq) in fp64 in visiting
+ *      order (b0 += (double)dx * inv, b1 += (double)dy * inv, b2 += inv), n = their number.
+ *   4. det S and A = adj(S) exactly, in integers; t = A b in fp64, row i as (A[i][0] b0 + A[i][1] b1) + A[i][2] b2.  No
+ *      division.  The fitted inverse depth of the centre has the sign of t[2].  The pixel has a normal iff n >= min_pts,
+ *      det S != 0 and t[2] > 0.
+ *   5. g = (t0, t1, (t2 - t0 px) - t1 py) with (px, py) = (x + 0.5, y + 0.5), the pixel coordinates of the fused point
+ *      (store_world_point), so normal and point describe the same ray.  nc = -K^T g: nc[j] = -((K[0][j] g0 + K[1][j] g1) +
+ *      K[2][j] g2).  Then nc . (Kinv p) = -t[2] < 0: the normal faces the camera.
+ *   6. nw = R^T nc with R = E[:3,:3], nw[j] = (R[0][j] nc0 + R[1][j] nc1) + R[2][j] nc2; norm = sqrt((nw0^2 + nw1^2) + nw2^2);
+ *      normal = fp32(nw / norm), one rounding.  A norm that is zero or not finite gives ok = 0 and (0, 0, 0).
+ *   ok depends only on integer counts and fp64-exact or fixed-order fp64 expressions: it is the same on every machine.
+ *   CDS_EINVAL: a null depth, cam_host, normals or ok; h or w < 1, h * w >= 2^31 or h > 524280; radius outside 1..4;
+ *   jump not > 0; min_pts outside 3..(2 radius + 1)^2.
+ */
+int cds_depth_normals_f32(const float* depth, const unsigned char* valid, const float* cam_host, int h, int w, int radius,
+                          float jump, int min_pts, float* normals, unsigned char* ok, void* stream);
+
+/*
+ * One attributed point per occupied voxel (csrc/cloud.hip).  Voxels as in cds_voxel_mean_f32: voxel v of n_voxels
+ * holds the points perm[start[v] .. start[v + 1]); keys, stable sort and offsets are the caller's.
+ *   points [n][3] fp32; colors [n] uint32 packed r | g << 8 | b << 16; normals [n][3] fp32 or NULL (then out_normals is not
+ *   written and may be NULL)
+ *   out_points [v][3]  the fp64 mean in perm order, rounded once: bit for bit cds_voxel_mean_f32
+ *   out_colors [v]     per channel (2 sum + k) / (2 k) in integers (round half up), k the voxel's point count; packed as colors
+ *   out_normals [v][3] the fp64 sum of the voxel's normals in perm order, divided by its norm sqrt((sx^2 + sy^2) + sz^2) and
+ *                      rounded once; (0, 0, 0) when the norm is zero or not finite.  Opposing faces inside one voxel are not
+ *                      separated.
+ *   out_counts [v]     k, int32
+ *   CDS_EINVAL: n or n_voxels < 0, n_voxels > n, n >= 2^31, a null required pointer (n_voxels == 0 returns 0 first).
+ */
+int cds_voxel_merge_f32(const float* points, const unsigned* colors, const float* normals, long long n, const long long* perm,
+                        const int* start, long long n_voxels, float* out_points, unsigned* out_colors, float* out_normals,
+                        int* out_counts, void* stream);
+
+/*
  * Norm-curvature bookkeeping of one FeatureNet level (module.py:250-251,257-258,264-265) in one launch:
  *   nc_sum[i] = (a[i]^2 + b[i]^2 + c[i]^2) / 3,  nc_abs[i] = |c[i]|   for the three DynamicConv curvature maps of the level
  */

@@ -147,6 +147,9 @@ SIGNATURES = {
     "cds_depth_fusion_dynamic_f32": [P, P, P, P, P, P, P, P, P, P, I, I, I, P, F, F, I, I, P],
     "cds_depth_normals_f32": [P, P, P, I, I, I, F, I, P, P, P],
     "cds_voxel_merge_f32": [P, P, P, L, P, P, L, P, P, P, P, P],
+    "cds_tsdf_integrate_f32": [P, L, P, P, DB, P, P, P, P, I, I, I, P, P, P, P, P],
+    "cds_tsdf_classify": [P, P, L, P, P, P, P, I, P, P, P, P, P],
+    "cds_tsdf_emit": [P, P, L, P, P, P, P, P, P, P, P, P, P, L, L, P, P, P, P, P],
     "cds_grid_hash_log2_slots": [L],
     "cds_grid_keys_f32": [P, L, P, P, P],
     "cds_grid_hash_build": [P, L, L, P, P, I, P],

@@ -27,6 +27,9 @@ running the network again.
 normal of its reference view's depth map (``cds_depth_normals_f32``; it faces that camera), and the concatenation of the views,
 in which a surface seen by ten views is written ten times, is merged to one point per occupied voxel (``cds_voxel_merge_f32``).
 With either option the views' points stay on the device until the scan is merged and are downloaded once.
+
+``filter_depth(collect=...)`` hands the same pass to a later stage: per reference view the fused depth, the mask, the image, the
+camera and the kept points, on the device.  :mod:`cds_mvsnet_amd.mesh` builds a triangle mesh from them.
 """
 from __future__ import annotations
 
@@ -185,7 +188,8 @@ def filter_depth(pair_folder: str, scan_folder: str, plyfilename: str, conf: Seq
                  verbose: bool = False, method: str = "normal", dist_base: float = DYN_DIST_BASE,
                  rel_base: float = DYN_REL_BASE, n_views: Sequence[int] = DYN_VIEWS, normals: bool = False,
                  normal_radius: int = 2, normal_jump: float = 0.01, normal_min_pts: int = 6,
-                 merge_voxel: Optional[float] = None, merge_min_points: int = 1) -> Dict[str, float]:
+                 merge_voxel: Optional[float] = None, merge_min_points: int = 1,
+                 collect: Optional[List[dict]] = None) -> Dict[str, float]:
     """The reference's ``filter_depth`` for one scan: -> PLY at ``plyfilename`` and mean photo/geo/final mask rates.
     ``method="dynamic"`` fuses with :func:`fuse_view_dynamic` (``conf``, ``dist_base``, ``rel_base``, ``n_views``;
     ``thres_disp`` / ``thres_view`` are not used) and also returns ``admitted_at``: {n: share of the reference pixels
@@ -197,9 +201,16 @@ def filter_depth(pair_folder: str, scan_folder: str, plyfilename: str, conf: Seq
     (``mean_final_mask`` still describes the fusion mask, before that).  ``merge_voxel``: the scan's points are merged to one per
     occupied voxel of that side (:func:`pointcloud.merge_voxels`), voxels with fewer than ``merge_min_points`` points dropped;
     ``points`` then counts the merged cloud and ``merged_from`` the points that went in.  With either option the views' points
-    stay on the device until the scan is done; with neither, nothing changes."""
+    stay on the device until the scan is done; with neither, nothing changes.
+
+    ``collect``: a list that receives, per reference view and in ``pair.txt`` order, what a later stage needs of the same pass
+    (:func:`cds_mvsnet_amd.mesh.mesh_scan`), all on the device: {"depth" [h,w] the fused depth, "mask" bool [h,w] the
+    fusion mask, "image" uint8 [h,w,3], "cam" [2,4,4] (CPU), "points" [k,3] the kept world points}.  The cloud is written as
+    without it; ``plyfilename`` may then be None, and no cloud is written."""
     if method not in ("normal", "dynamic"):
         raise ValueError(f"filter_depth: method must be 'normal' or 'dynamic', got {method!r}")
+    if plyfilename is None and collect is None:
+        raise ValueError("filter_depth: plyfilename is None and nothing is collected")
     cloud = bool(normals) or merge_voxel is not None
     if merge_voxel is not None and not (float(merge_voxel) > 0 and np.isfinite(float(merge_voxel))):
         raise ValueError(f"filter_depth: merge_voxel must be positive, got {merge_voxel}")
@@ -220,6 +231,7 @@ def filter_depth(pair_folder: str, scan_folder: str, plyfilename: str, conf: Seq
     col_all: List[np.ndarray] = []
     rates = []
     hist: List[np.ndarray] = []
+    n_kept = 0
     for ref, srcs in pairs:
         srcs = srcs[:n_src_views]
         if not srcs:
@@ -236,6 +248,10 @@ def filter_depth(pair_folder: str, scan_folder: str, plyfilename: str, conf: Seq
             out = fuse_view(rd, rc, rcam, torch.stack([s[0] for s in sv]), torch.stack([s[1] for s in sv]),
                             torch.stack([s[2] for s in sv]), conf, thres_disp, thres_view)
         keep = out["mask"] > 0.5
+        img = torch.from_numpy(np.ascontiguousarray(rimg())).to(device)            # [h,w,3]
+        if collect is not None:
+            collect.append({"depth": out["depth"], "mask": keep, "image": (img * 255).to(torch.uint8), "cam": rcam,
+                            "points": out["points"][:, keep].t().contiguous()})
         if cloud:
             kept = keep.sum()
             if normals:
@@ -245,19 +261,22 @@ def filter_depth(pair_folder: str, scan_folder: str, plyfilename: str, conf: Seq
                 keep = keep & (ok > 0)
                 dev_nrm.append(nrm[:, keep].t().contiguous())
             dev_pts.append(out["points"][:, keep].t().contiguous())
-            img = torch.from_numpy(np.ascontiguousarray(rimg())).to(device)
             dev_col.append((img[keep] * 255).to(torch.uint8))
             dev_cnt.append(torch.stack([kept, keep.sum(), torch.as_tensor(keep.numel(), device=kept.device)]))
             continue
-        pts = out["points"][:, keep].t().contiguous().cpu().numpy()
-        img = torch.from_numpy(np.ascontiguousarray(rimg())).to(device)            # [h,w,3]
-        col = (img[keep] * 255).to(torch.uint8).cpu().numpy()
-        pts_all.append(pts)
-        col_all.append(col)
         rates.append(float(keep.float().mean()))
         if verbose:
             print(f"processing {scan_folder}, ref-view{ref:02d}, final-mask:{rates[-1]:.4f}")
-    if cloud:
+        if plyfilename is None:                      # nothing to write: count, do not download
+            n_kept += int(keep.sum())
+            continue
+        pts_all.append(out["points"][:, keep].t().contiguous().cpu().numpy())
+        col_all.append((img[keep] * 255).to(torch.uint8).cpu().numpy())
+    if plyfilename is None:
+        cnt = torch.stack(dev_cnt).cpu().numpy().astype(np.float64) if dev_cnt else np.zeros((0, 3))
+        info = {"points": n_kept + sum(int(p.shape[0]) for p in dev_pts),
+                "mean_final_mask": float(np.mean(rates)) if rates else (float(np.mean(cnt[:, 0] / cnt[:, 2])) if len(cnt) else 0.0)}
+    elif cloud:
         info = _finish_cloud(plyfilename, dev_pts, dev_col, dev_nrm if normals else None, dev_cnt, merge_voxel,
                              merge_min_points, device, verbose, scan_folder)
     else:

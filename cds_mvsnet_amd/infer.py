@@ -12,6 +12,8 @@ with `--filter_method gipuma`, the gipuma-style one (gipuma.py; `--prob_threshol
 or, with `--filter_method dynamic`, the dynamic consistency check (fusion.py; `--conf`, `--dyn_dist_base`, `--dyn_rel_base`,
 `--dyn_views`).  `--normals` (`--normal_radius`, `--normal_jump`, `--normal_min_pts`; not for gipuma) adds each point's oriented
 normal and `--merge_voxel SIZE` (`--merge_min_points K`) merges the scan to one point per occupied voxel.
+`--mesh_voxel SIZE` (`--mesh_trunc T`, `--mesh_min_weight N`; not for gipuma) also writes `<out>/<scan>_mesh.ply`, a triangle mesh
+from the same fusion pass (mesh.py).
 `--save_stages` also writes the three stages' own depth maps, `<out>/<scan>/depth_stage{1,2,3}/%08d.pfm`, at their resolutions
 (what evaluations/precision.py scores stage by stage; `python -m cds_mvsnet_amd.depth_eval --folders ...`).
 
@@ -221,6 +223,19 @@ def run(args) -> float:
         # step 2 of the reference's test.py (pcd_filter, test.py:386-396): scans are independent -> shard over ranks
         from .fusion import cloud_kwargs, filter_depth, format_admitted, format_cloud
         from .gipuma import filter_scan
+        from .mesh import format_mesh, mesh_scan
+
+        def fuse(scan, **kw):
+            """The cloud alone, or with --mesh_voxel cloud and mesh from one fusion pass."""
+            ply = os.path.join(args.outdir, f"{scan}.ply")
+            if args.mesh_voxel is None:
+                return filter_depth(os.path.join(args.testpath, scan), os.path.join(args.outdir, scan), ply, **kw)
+            info = mesh_scan(os.path.join(args.testpath, scan), os.path.join(args.outdir, scan),
+                             os.path.join(args.outdir, f"{scan}_mesh.ply"), args.mesh_voxel, args.mesh_trunc, args.mesh_min_weight,
+                             cloud_ply=ply, **kw)
+            print(f"[{rank}] {scan}_mesh.ply: {format_mesh(info)}", flush=True)
+            return info["cloud"]
+
         if world > 1:  # every rank's depth maps must be on disk before any scan is fused
             if not torch.distributed.is_initialized():
                 torch.distributed.init_process_group("nccl", device_id=dev)
@@ -239,17 +254,14 @@ def run(args) -> float:
                 continue
             if args.filter_method == "dynamic":
                 # the dynamic consistency check: one setting for every scene, thresholds graded by view count
-                info = filter_depth(os.path.join(args.testpath, scan), os.path.join(args.outdir, scan),
-                                    os.path.join(args.outdir, f"{scan}.ply"), conf=[float(c) for c in args.conf.split(",")],
-                                    device=str(dev), method="dynamic", dist_base=args.dyn_dist_base,
-                                    rel_base=args.dyn_rel_base, n_views=[int(v) for v in args.dyn_views.split(",")],
-                                    **cloud_kwargs(args))
+                info = fuse(scan, conf=[float(c) for c in args.conf.split(",")], device=str(dev), method="dynamic",
+                            dist_base=args.dyn_dist_base, rel_base=args.dyn_rel_base,
+                            n_views=[int(v) for v in args.dyn_views.split(",")], **cloud_kwargs(args))
                 print(f"[{rank}] {scan}.ply: {info['points']} points, final mask {info['mean_final_mask']:.3f}, admitted at "
                       f"{format_admitted(info['admitted_at'])}{format_cloud(info)} (dynamic)", flush=True)
                 continue
-            info = filter_depth(os.path.join(args.testpath, scan), os.path.join(args.outdir, scan),
-                                os.path.join(args.outdir, f"{scan}.ply"), conf=[float(c) for c in args.conf.split(",")],
-                                thres_disp=args.thres_disp, thres_view=args.thres_view, device=str(dev), **cloud_kwargs(args))
+            info = fuse(scan, conf=[float(c) for c in args.conf.split(",")], thres_disp=args.thres_disp,
+                        thres_view=args.thres_view, device=str(dev), **cloud_kwargs(args))
             print(f"[{rank}] {scan}.ply: {info['points']} points, final mask {info['mean_final_mask']:.3f}{format_cloud(info)}",
                   flush=True)
     return avg
@@ -300,7 +312,17 @@ def parse_args(argv=None) -> argparse.Namespace:
                     help="dynamic: a pixel is kept when n views agree at level n for some n in this range")
     from .fusion import add_cloud_args
     add_cloud_args(ap)
+    from .mesh import add_mesh_args, check_voxel
+    add_mesh_args(ap)
     args = ap.parse_args(argv)
+    if args.mesh_voxel is not None:
+        if args.filter_method == "gipuma":
+            ap.error("--mesh_voxel is not implemented for --filter_method gipuma (its fused point has no single depth map); "
+                     "use normal or dynamic")
+        try:
+            check_voxel(args.mesh_voxel, args.mesh_trunc, "--mesh_voxel")
+        except ValueError as e:
+            ap.error(str(e))
     if args.normals and args.filter_method == "gipuma":
         ap.error("--normals is not implemented for --filter_method gipuma (its fused point is an average over views); "
                  "use normal or dynamic")

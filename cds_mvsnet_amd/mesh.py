@@ -1,0 +1,352 @@
+"""A triangle mesh from the fused depth maps of a scan, on the GPU (the rule is in include/cds_mvsnet_hip.h).
+
+The fused depth map, consistency mask, camera and image of every reference view, all on the device at the end of
+:func:`cds_mvsnet_amd.fusion.filter_depth`, are integrated into a sparse truncated signed distance volume (blocks of 8x8x8
+lattice points around the kept points) and the zero level set is extracted as the triangles of the six Freudenthal tetrahedra
+of every cube: welded vertices, consistent winding, colours, a fixed order.  The hot paths are the kernels of ``csrc/tsdf.hip``
+(``cds_tsdf_integrate_f32``, ``cds_tsdf_classify``, ``cds_tsdf_emit``); torch does the keys, unique and prefix sums that lay
+the blocks out.  There is no CPU path.
+
+    python -m cds_mvsnet_amd.mesh --testpath <scenes> --outdir <out> --testlist <list> --mesh_voxel SIZE [--mesh_trunc T]
+        [--mesh_min_weight 2] [--filter_method normal|dynamic] [--conf 0,0,0] [--thres_disp 1.0] [--thres_view 3]
+        [--dyn_dist_base 0.25] [--dyn_rel_base 0.000769] [--dyn_views 2,10]
+
+fuses the saved depth maps of ``<out>/<scan>/`` as ``python -m cds_mvsnet_amd.fusion`` does and writes
+``<out>/<scan>_mesh.ply``.  ``infer ... --fuse --mesh_voxel SIZE`` writes cloud and mesh from one fusion pass.
+"""
+from __future__ import annotations
+
+import argparse
+import math
+import os
+from typing import Dict, Optional, Sequence
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import check
+
+Tensor = torch.Tensor
+
+MAX_CELLS = 1 << 26            # cells of the dense block table (CDS_TSDF_MAX_CELLS): 256 MiB of int32
+MAX_CHUNK = 32                 # views per launch the kernel takes (CDS_TSDF_MAX_CHUNK)
+CHUNK_VIEWS = 32               # views per launch of TsdfVolume.integrate (profiles/tsdf_mesh.md: 3.5 x faster than 1)
+
+
+def check_voxel(voxel, trunc=None, what: str = "mesh"):
+    """-> (voxel, trunc) as floats; trunc defaults to 4 voxels.  ValueError unless voxel > 0 and voxel <= trunc <= 8 voxel."""
+    try:
+        size = float(voxel)
+    except (TypeError, ValueError):
+        size = math.nan
+    if not (size > 0 and math.isfinite(size)):
+        raise ValueError(f"{what}: voxel must be positive, got {voxel}")
+    voxel = size
+    trunc = 4.0 * voxel if trunc is None else float(trunc)
+    if not (voxel <= trunc <= 8.0 * voxel):
+        raise ValueError(f"{what}: trunc must lie in [voxel, 8 voxel] = [{voxel}, {8.0 * voxel}], got {trunc} (the band of +-trunc "
+                         "along a ray must stay inside the blocks next to its point)")
+    return voxel, trunc
+
+
+def check_grid(nb, voxel: float, what: str = "mesh") -> None:
+    cells = int(nb[0]) * int(nb[1]) * int(nb[2])
+    if cells > MAX_CELLS:
+        raise ValueError(f"{what}: a voxel of {voxel} gives a grid of {int(nb[0])} x {int(nb[1])} x {int(nb[2])} = {cells} blocks, "
+                         f"at most {MAX_CELLS}: raise --mesh_voxel")
+
+
+class TsdfVolume:
+    """The sparse volume of one scan.  ``points`` [N,3] float32 on the device: the kept points of every view; they fix the frame
+    (origin, blocks per axis) and the allocated blocks (a block that holds a point, and its 26 neighbours inside the grid).
+
+    Attributes: ``voxel``, ``trunc``, ``origin`` (float64 numpy [3]), ``nb`` (int64 numpy [3]: blocks per axis x, y, z),
+    ``keys`` int32 [NB] ascending, ``table`` int32 [nbz,nby,nbx] (-1: no block), ``sum`` float32 [NB,512], ``n`` / ``nc``
+    int32 [NB,512], ``rgb`` int32 [3,NB,512]."""
+
+    def __init__(self, points: Tensor, voxel: float, trunc: Optional[float] = None):
+        voxel, trunc = check_voxel(voxel, trunc, "TsdfVolume")
+        if not isinstance(points, torch.Tensor) or points.dim() != 2 or points.shape[1] != 3 or points.dtype != torch.float32:
+            raise ValueError(f"TsdfVolume: points must be a float32 [N,3] tensor, got {getattr(points, 'shape', type(points))}")
+        if not points.is_cuda:
+            raise RuntimeError("TsdfVolume: points must be a ROCm (cuda) tensor; there is no CPU fallback")
+        if points.shape[0] == 0:
+            self._setup(np.zeros(3), voxel, trunc, np.ones(3, np.int64), torch.zeros(0, dtype=torch.int64, device=points.device))
+            return
+        lo, hi = torch.aminmax(points, dim=0)
+        lo, hi = lo.double().cpu().numpy(), hi.double().cpu().numpy()
+        if not (np.isfinite(lo).all() and np.isfinite(hi).all()):
+            raise ValueError("TsdfVolume: points must be finite")
+        b = 8.0 * voxel
+        origin = (np.floor(lo / b) - 1.0) * b
+        nbf = np.floor((hi - origin) / b) + 2.0
+        if not (np.isfinite(origin).all() and float(nbf.max()) < 2.0 ** 31):
+            raise ValueError(f"TsdfVolume: a voxel of {voxel} is too small for this scan: raise --mesh_voxel")
+        nb = nbf.astype(np.int64)
+        check_grid(nb, voxel, "TsdfVolume")
+        dev = points.device
+        bi = torch.floor((points.double() - torch.from_numpy(origin).to(dev)) / b).long()
+        own = torch.unique((bi[:, 2] * int(nb[1]) + bi[:, 1]) * int(nb[0]) + bi[:, 0])
+        ox, oy, oz = own % int(nb[0]), (own // int(nb[0])) % int(nb[1]), own // (int(nb[0]) * int(nb[1]))
+        near = []
+        for dz in (-1, 0, 1):
+            for dy in (-1, 0, 1):
+                for dx in (-1, 0, 1):
+                    x, y, z = ox + dx, oy + dy, oz + dz
+                    ok = (x >= 0) & (x < int(nb[0])) & (y >= 0) & (y < int(nb[1])) & (z >= 0) & (z < int(nb[2]))
+                    near.append(((z * int(nb[1]) + y) * int(nb[0]) + x)[ok])
+        self._setup(origin, voxel, trunc, nb, torch.unique(torch.cat(near)))
+
+    @classmethod
+    def from_blocks(cls, origin, voxel: float, trunc: float, nb, keys, device="cuda") -> "TsdfVolume":
+        """A volume with a given frame and block set (``keys``: block keys (bz nby + by) nbx + bx, any order), zeroed."""
+        voxel, trunc = check_voxel(voxel, trunc, "TsdfVolume")
+        nb = np.asarray(nb, np.int64).reshape(3)
+        if int(nb.min()) < 1:
+            raise ValueError(f"TsdfVolume: blocks per axis must be >= 1, got {nb.tolist()}")
+        check_grid(nb, voxel, "TsdfVolume")
+        keys = torch.unique(torch.as_tensor(np.asarray(keys, np.int64)).to(device))
+        if keys.numel() and (int(keys[0]) < 0 or int(keys[-1]) >= int(nb[0]) * int(nb[1]) * int(nb[2])):
+            raise ValueError("TsdfVolume: block keys outside the grid")
+        self = cls.__new__(cls)
+        self._setup(np.asarray(origin, np.float64).reshape(3), voxel, trunc, nb, keys)
+        return self
+
+    def _setup(self, origin, voxel, trunc, nb, keys64: Tensor) -> None:
+        dev = keys64.device
+        self.voxel, self.trunc, self.origin, self.nb, self.device = voxel, trunc, origin, nb, dev
+        self.n_blocks = k = int(keys64.numel())
+        self.keys = keys64.to(torch.int32)
+        self.table = torch.full((int(nb[2]), int(nb[1]), int(nb[0])), -1, dtype=torch.int32, device=dev)
+        self.table.view(-1)[keys64] = torch.arange(k, dtype=torch.int32, device=dev)
+        self.sum = torch.zeros((k, 512), dtype=torch.float32, device=dev)
+        self.n = torch.zeros((k, 512), dtype=torch.int32, device=dev)
+        self.nc = torch.zeros((k, 512), dtype=torch.int32, device=dev)
+        self.rgb = torch.zeros((3, k, 512), dtype=torch.int32, device=dev)
+        self._frame = torch.tensor([*origin.tolist(), voxel], dtype=torch.float64)          # host arguments of the kernels
+        self._dims = torch.tensor(nb.tolist(), dtype=torch.int32)
+
+    def _stream(self):
+        return torch.cuda.current_stream(self.device).cuda_stream
+
+    def integrate(self, depths: Tensor, masks: Tensor, images: Tensor, cams: Tensor, chunk: int = CHUNK_VIEWS) -> None:
+        """Add views in the order given: depths [V,h,w] float32, masks [V,h,w] (bool, uint8 or float: non-zero keeps the
+        pixel), images [V,h,w,3] uint8, all on the volume's device; cams [V,2,4,4] float32 (extrinsic; intrinsic in [:3,:3]),
+        any device.  ``chunk`` views go into one launch (1..32); the result does not depend on it."""
+        if not (1 <= int(chunk) <= MAX_CHUNK):
+            raise ValueError(f"TsdfVolume.integrate: chunk must lie in 1..{MAX_CHUNK}, got {chunk}")
+        if depths.dim() != 3 or depths.dtype != torch.float32:
+            raise ValueError(f"TsdfVolume.integrate: depths must be float32 [V,h,w], got {depths.dtype} {tuple(depths.shape)}")
+        v, h, w = depths.shape
+        if tuple(masks.shape) != (v, h, w) or tuple(images.shape) != (v, h, w, 3) or images.dtype != torch.uint8 or \
+                tuple(cams.shape) != (v, 2, 4, 4):
+            raise ValueError(f"TsdfVolume.integrate: for depths {tuple(depths.shape)} masks must be [V,h,w], images uint8 [V,h,w,3] "
+                             f"and cams [V,2,4,4]; got {tuple(masks.shape)}, {images.dtype} {tuple(images.shape)}, {tuple(cams.shape)}")
+        for t, name in ((depths, "depths"), (masks, "masks"), (images, "images")):
+            if t.device != self.device:
+                raise RuntimeError(f"TsdfVolume.integrate: {name} must be on {self.device}; there is no CPU fallback")
+        if v == 0 or self.n_blocks == 0:
+            return
+        depths, images = depths.contiguous(), images.contiguous()
+        masks = (masks != 0).to(torch.uint8).contiguous()
+        cam = cams.detach().to(torch.float32).to(self.device).double()
+        ok = (masks != 0) & torch.isfinite(depths) & (depths > 0)
+        far = torch.where(ok, depths, torch.full_like(depths, -math.inf)).flatten(1).amax(1).double()
+        tab = torch.zeros((v, 24), dtype=torch.float64, device=self.device)
+        tab[:, 0:9] = cam[:, 0, :3, :3].reshape(v, 9)
+        tab[:, 9:12] = cam[:, 0, :3, 3]
+        tab[:, 12:21] = cam[:, 1, :3, :3].reshape(v, 9)
+        tab[:, 21] = far
+        lib, hw = _lib.load(), h * w
+        with torch.cuda.device(self.device):
+            for v0 in range(0, v, int(chunk)):
+                nv = min(int(chunk), v - v0)
+                check(lib.cds_tsdf_integrate_f32(self.keys.data_ptr(), self.n_blocks, self._frame.data_ptr(), self._dims.data_ptr(),
+                                                 self.trunc, depths.data_ptr() + 4 * v0 * hw, masks.data_ptr() + v0 * hw,
+                                                 images.data_ptr() + 3 * v0 * hw, tab.data_ptr() + 8 * 24 * v0, nv, h, w,
+                                                 self.sum.data_ptr(), self.n.data_ptr(), self.nc.data_ptr(), self.rgb.data_ptr(),
+                                                 self._stream()), "cds_tsdf_integrate_f32")
+
+    def extract(self, min_weight: int = 2) -> Dict[str, Tensor]:
+        """The zero level set over the cubes whose eight corners were seen at least ``min_weight`` times
+        -> {"vertices" float32 [V,3], "colors" uint8 [V,3], "faces" int32 [F,3]} on the device."""
+        if int(min_weight) < 1:
+            raise ValueError(f"TsdfVolume.extract: min_weight must be >= 1, got {min_weight}")
+        dev, k = self.device, self.n_blocks
+        empty = {"vertices": torch.zeros((0, 3), dtype=torch.float32, device=dev),
+                 "colors": torch.zeros((0, 3), dtype=torch.uint8, device=dev), "faces": torch.zeros((0, 3), dtype=torch.int32, device=dev)}
+        if k == 0:
+            return empty
+        lib = _lib.load()
+        vmask = torch.empty((k, 512), dtype=torch.uint8, device=dev)
+        tcount = torch.empty((k, 512), dtype=torch.uint8, device=dev)
+        bv = torch.empty(k, dtype=torch.int32, device=dev)
+        bt = torch.empty(k, dtype=torch.int32, device=dev)
+        frame = (self._frame.data_ptr(), self._dims.data_ptr())
+        with torch.cuda.device(dev):
+            check(lib.cds_tsdf_classify(self.keys.data_ptr(), self.table.data_ptr(), k, *frame, self.sum.data_ptr(), self.n.data_ptr(),
+                                        int(min_weight), vmask.data_ptr(), tcount.data_ptr(), bv.data_ptr(), bt.data_ptr(),
+                                        self._stream()), "cds_tsdf_classify")
+            ends = torch.stack([torch.cumsum(bv, 0, dtype=torch.int64), torch.cumsum(bt, 0, dtype=torch.int64)])
+            nv, nf = (int(x) for x in ends[:, -1].cpu())
+            if nv >= 2 ** 31 or nf >= 2 ** 31:
+                raise ValueError(f"TsdfVolume.extract: {nv} vertices and {nf} faces, at most 2^31 - 1 each: raise --mesh_voxel")
+            if nv == 0:
+                return empty
+            vfirst = (ends[0] - bv).to(torch.int32)
+            tfirst = (ends[1] - bt).to(torch.int32)
+            vstart = torch.empty((k, 512), dtype=torch.int32, device=dev)
+            out = {"vertices": torch.empty((nv, 3), dtype=torch.float32, device=dev),
+                   "colors": torch.empty((nv, 3), dtype=torch.uint8, device=dev),
+                   "faces": torch.empty((nf, 3), dtype=torch.int32, device=dev)}
+            check(lib.cds_tsdf_emit(self.keys.data_ptr(), self.table.data_ptr(), k, *frame, self.sum.data_ptr(), self.n.data_ptr(),
+                                    self.nc.data_ptr(), self.rgb.data_ptr(), vmask.data_ptr(), tcount.data_ptr(), vfirst.data_ptr(),
+                                    tfirst.data_ptr(), nv, nf, vstart.data_ptr(), out["vertices"].data_ptr(), out["colors"].data_ptr(),
+                                    out["faces"].data_ptr() if nf else None, self._stream()), "cds_tsdf_emit")
+        return out
+
+
+# --------------------------------------------------------------------------------------------------------------------- PLY
+_VERTEX = [("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1")]
+_FACE = [("k", "u1"), ("v", "<i4", (3,))]
+_HEADER = ("ply\nformat binary_little_endian 1.0\nelement vertex {}\nproperty float x\nproperty float y\nproperty float z\n"
+           "property uchar red\nproperty uchar green\nproperty uchar blue\nelement face {}\n"
+           "property list uchar int vertex_indices\nend_header\n")
+
+
+def write_mesh_ply(path: str, vertices: np.ndarray, colors: np.ndarray, faces: np.ndarray) -> None:
+    """Binary little-endian PLY: vertex x y z red green blue, face ``property list uchar int vertex_indices`` (triangles).
+    No normals: viewers derive them from the winding."""
+    vertices, colors, faces = np.asarray(vertices), np.asarray(colors), np.asarray(faces)
+    nv, nf = int(vertices.shape[0]), int(faces.shape[0])
+    if tuple(vertices.shape) != (nv, 3) or tuple(colors.shape) != (nv, 3) or tuple(faces.shape) != (nf, 3):
+        raise ValueError(f"write_mesh_ply: vertices [V,3], colors [V,3], faces [F,3] expected, got {vertices.shape}, {colors.shape}, "
+                         f"{faces.shape}")
+    if nf and (int(faces.min()) < 0 or int(faces.max()) >= nv):
+        raise ValueError(f"write_mesh_ply: faces index outside the {nv} vertices")
+    vrec = np.empty(nv, dtype=_VERTEX)
+    for i, c in enumerate("xyz"):
+        vrec[c] = vertices[:, i]
+    for i, c in enumerate(("red", "green", "blue")):
+        vrec[c] = colors[:, i]
+    frec = np.empty(nf, dtype=_FACE)
+    frec["k"] = 3
+    frec["v"] = faces
+    with open(path, "wb") as f:
+        f.write(_HEADER.format(nv, nf).encode("ascii"))
+        vrec.tofile(f)
+        frec.tofile(f)
+
+
+def read_mesh_ply(path: str):
+    """A file of :func:`write_mesh_ply` -> (vertices float32 [V,3], colors uint8 [V,3], faces int32 [F,3])."""
+    with open(path, "rb") as f:
+        counts, lines = {}, []
+        while True:
+            line = f.readline()
+            if not line:
+                raise ValueError(f"{path}: PLY header without end_header")
+            line = line.decode("ascii", "replace").strip()
+            lines.append(line)
+            tok = line.split()
+            if tok[:1] == ["element"]:
+                counts[tok[1]] = int(tok[2])
+            if line == "end_header":
+                break
+        if "\n".join(lines) + "\n" != _HEADER.format(counts.get("vertex"), counts.get("face")):
+            raise ValueError(f"{path}: not the layout that write_mesh_ply produces")
+        nv, nf = counts["vertex"], counts["face"]
+        vraw = f.read(np.dtype(_VERTEX).itemsize * nv)
+        fraw = f.read(np.dtype(_FACE).itemsize * nf)
+        if len(vraw) != np.dtype(_VERTEX).itemsize * nv or len(fraw) != np.dtype(_FACE).itemsize * nf:
+            raise ValueError(f"{path}: truncated")
+        vrec, frec = np.frombuffer(vraw, dtype=_VERTEX, count=nv), np.frombuffer(fraw, dtype=_FACE, count=nf)
+    if nf and not (frec["k"] == 3).all():
+        raise ValueError(f"{path}: faces that are not triangles")
+    return (np.stack([vrec["x"], vrec["y"], vrec["z"]], -1).reshape(nv, 3), np.stack([vrec["red"], vrec["green"], vrec["blue"]], -1)
+            .reshape(nv, 3), np.ascontiguousarray(frec["v"]).reshape(nf, 3))
+
+
+# -------------------------------------------------------------------------------------------------------------------- scans
+def mesh_views(views: Sequence[dict], voxel: float, trunc: Optional[float] = None, min_weight: int = 2, device="cuda"):
+    """Allocation, integration and extraction for the per-view records that ``filter_depth(collect=...)`` gathers
+    -> (mesh dict of :meth:`TsdfVolume.extract`, the volume)."""
+    dev = torch.device(device)
+    pts = torch.cat([v["points"] for v in views]) if views else torch.zeros((0, 3), dtype=torch.float32, device=dev)
+    vol = TsdfVolume(pts, voxel, trunc)
+    if views and vol.n_blocks:
+        vol.integrate(torch.stack([v["depth"] for v in views]), torch.stack([v["mask"] for v in views]),
+                      torch.stack([v["image"] for v in views]), torch.stack([v["cam"] for v in views]))
+    return vol.extract(min_weight), vol
+
+
+def mesh_scan(pair_folder: str, scan_folder: str, plyfilename: str, voxel: float, trunc: Optional[float] = None, min_weight: int = 2,
+              method: str = "normal", cloud_ply: Optional[str] = None, device: str = "cuda", **fusion_options) -> Dict[str, object]:
+    """One scan from saved depth maps to a mesh at ``plyfilename``: the fusion pass of :func:`fusion.filter_depth` (``method``
+    "normal" or "dynamic" and its ``fusion_options``), then allocation from every view's kept points, integration of the fused
+    depth maps in ``pair.txt`` order and extraction.  ``cloud_ply``: also write the fused cloud there, from the same pass and byte
+    for byte what ``filter_depth`` writes alone.  -> {"vertices", "faces", "blocks": counts, "cloud": filter_depth's result}."""
+    from .fusion import filter_depth
+    if method == "gipuma":
+        raise ValueError("mesh_scan: gipuma fusion is not supported (its fused point has no single depth map); use normal or dynamic")
+    voxel, trunc = check_voxel(voxel, trunc, "mesh_scan")
+    if int(min_weight) < 1:
+        raise ValueError(f"mesh_scan: min_weight must be >= 1, got {min_weight}")
+    views: list = []
+    cloud = filter_depth(pair_folder, scan_folder, cloud_ply, device=device, method=method, collect=views, **fusion_options)
+    mesh, vol = mesh_views(views, voxel, trunc, min_weight, device)
+    write_mesh_ply(plyfilename, mesh["vertices"].cpu().numpy(), mesh["colors"].cpu().numpy(), mesh["faces"].cpu().numpy())
+    return {"vertices": int(mesh["vertices"].shape[0]), "faces": int(mesh["faces"].shape[0]), "blocks": vol.n_blocks, "cloud": cloud}
+
+
+def format_mesh(info: Dict[str, object]) -> str:
+    return f"{info['vertices']} vertices, {info['faces']} faces, {info['blocks']} blocks"
+
+
+# ---------------------------------------------------------------------------------------------------------------------- CLI
+def add_mesh_args(ap: argparse.ArgumentParser, required: bool = False) -> None:
+    """The options of DESIGN §1.9, shared with ``infer --fuse``."""
+    ap.add_argument("--mesh_voxel", type=float, default=None, required=required, metavar="SIZE",
+                    help="write <outdir>/<scan>_mesh.ply: a triangle mesh from a TSDF volume with this lattice spacing (world units)")
+    ap.add_argument("--mesh_trunc", type=float, default=None, metavar="T",
+                    help="--mesh_voxel: truncation distance, between 1 and 8 voxels (default 4 voxels)")
+    ap.add_argument("--mesh_min_weight", type=int, default=2, metavar="N",
+                    help="--mesh_voxel: views a lattice point needs before its cubes are meshed")
+
+
+def main(argv=None) -> Dict[str, Dict[str, object]]:
+    from .fusion import DYN_DIST_BASE, DYN_REL_BASE, _floats
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--testpath", required=True, help="the scenes: <testpath>/<scan>/pair.txt")
+    ap.add_argument("--outdir", required=True, help="the infer output folder: <outdir>/<scan>/{depth_est,confidence,cams,images}")
+    ap.add_argument("--testlist", required=True, help="text file with one scan name per line")
+    ap.add_argument("--filter_method", default="normal", choices=["normal", "dynamic", "gipuma"])
+    ap.add_argument("--conf", default="0.0,0.0,0.0", help="per-stage confidence thresholds")
+    ap.add_argument("--thres_view", type=int, default=3, help="normal: consistent views a pixel needs")
+    ap.add_argument("--thres_disp", type=float, default=1.0, help="normal: re-projection distance threshold in pixels")
+    ap.add_argument("--dyn_dist_base", type=float, default=DYN_DIST_BASE, help="dynamic: pixels per level")
+    ap.add_argument("--dyn_rel_base", type=float, default=DYN_REL_BASE, help="dynamic: relative depth difference per level")
+    ap.add_argument("--dyn_views", default="2,10", help="dynamic: n_min,n_max")
+    ap.add_argument("--device", default="cuda")
+    add_mesh_args(ap, required=True)
+    args = ap.parse_args(argv)
+    if args.filter_method == "gipuma":
+        ap.error("--mesh_voxel is not implemented for --filter_method gipuma (its fused point has no single depth map); "
+                 "use normal or dynamic")
+    with open(args.testlist) as f:
+        scans = [ln.strip() for ln in f if ln.strip()]
+    out = {}
+    for scan in scans:
+        info = mesh_scan(os.path.join(args.testpath, scan), os.path.join(args.outdir, scan),
+                         os.path.join(args.outdir, f"{scan}_mesh.ply"), args.mesh_voxel, args.mesh_trunc, args.mesh_min_weight,
+                         method=args.filter_method, device=args.device, conf=_floats(args.conf, 3, "--conf"),
+                         thres_disp=args.thres_disp, thres_view=args.thres_view, dist_base=args.dyn_dist_base,
+                         rel_base=args.dyn_rel_base, n_views=tuple(int(v) for v in _floats(args.dyn_views, 2, "--dyn_views")))
+        out[scan] = info
+        print(f"{scan}_mesh.ply: {format_mesh(info)}", flush=True)
+    return out
+
+
+if __name__ == "__main__":
+    main()

@@ -597,6 +597,80 @@ int cds_voxel_merge_f32(const float* points, const unsigned* colors, const float
                         int* out_counts, void* stream);
 
 /*
+ * Sparse TSDF fusion and tetrahedra extraction: a triangle mesh from the fused depth maps (csrc/tsdf.hip).
+ *
+ * Frame.  voxel s > 0, truncation T with s <= T <= 8 s, both doubles.  Lattice point (i, j, k) lies at
+ *   X[a] = origin[a] + (double)idx[a] * s  (fp64).  Blocks are 8 x 8 x 8 lattice points; B = 8.0 * s.
+ *   From the kept points of the scan (fp32, lo / hi their per-axis minimum / maximum):
+ *     origin[a] = (floor((double)lo[a] / B) - 1.0) * B,   nb[a] = (int)floor(((double)hi[a] - origin[a]) / B) + 2.
+ *   The block of a point is floor(((double)p[a] - origin[a]) / B) per axis; it lies in 0 .. nb[a] - 2.
+ *   nb[0] nb[1] nb[2] <= CDS_TSDF_MAX_CELLS, else the voxel is too small for the scan.
+ *   Block key = (bz nb[1] + by) nb[0] + bx; local index of a point in its block = (lz 8 + ly) 8 + lx.
+ * Allocation.  A block exists iff it holds a kept point or is one of the 26 neighbours of such a block and lies inside the
+ *   grid.  Blocks are stored in ascending key order: keys [n_blocks] int32; table [nb[2]][nb[1]][nb[0]] int32 gives a block's
+ *   position in keys, or -1.  Since T <= 8 s, the band of +-T along every kept ray lies in existing blocks.
+ * Storage, [n_blocks][512] each: sum fp32, n int32, nc int32; rgb int32 [3][n_blocks][512].
+ *
+ * Integration of one lattice point X over the views in the order given, in fp64 from the fp32 camera entries
+ *   (cams [n_views][24] doubles: R 0..8 and t 9..11 the rows of E = [R | t] world -> camera, K 12..20 row-major, 21 the largest
+ *   depth of the view that passes step 4, -inf if none; 22, 23 unused):
+ *   1. Xc[r] = ((R[r][0] X0 + R[r][1] X1) + R[r][2] X2) + t[r];  z = Xc[2];  skip the view unless z > 0.
+ *   2. p[r] = (K[r][0] Xc0 + K[r][1] Xc1) + K[r][2] Xc2;  u = p0 / p2,  v = p1 / p2.
+ *   3. x = floor(u), y = floor(v): pixel x covers [x, x + 1), its centre is x + 0.5 (the convention of the fused points).
+ *      Skip the view unless 0 <= u < w and 0 <= v < h (false for NaN).
+ *   4. d = depths[view][y][x].  Skip if masks[view][y][x] == 0, or d is not finite, or d <= 0.
+ *   5. sdf = (double)d - z.  Skip if sdf < -T.  tv = (float)min(1.0, sdf / T).
+ *   6. sum = sum + tv, one fp32 add per view, in view order;  n += 1.
+ *   7. If sdf <= T: rgb += images[view][y][x][0..2] (uint8) and nc += 1.
+ *   Every observation weighs 1.  A view is skipped for a whole block only when no point of the block could pass steps 1, 3 and 5
+ *   (bounding sphere against the frustum planes and entry 21); that never changes a result.
+ *
+ * Extraction, with min_weight >= 1.
+ *   A point is valid iff it exists and n >= min_weight; it is inside iff sum < 0 (no division enters a decision).
+ *   A cube (lower corner L, corners L + {0,1}^3) is processed iff its 8 corners are valid.  It is split into the six tetrahedra
+ *   000 -> e_a -> e_a + e_b -> 111 over the axis orders (a, b, c) in lexicographic order: (x,y,z) (x,z,y) (y,x,z) (y,z,x) (z,x,y)
+ *   (z,y,x); tetrahedron corners v0..v3 along the path.  Every tetrahedron edge joins nested corners, so it is a lattice edge
+ *   with a lower point A and an offset of one of seven kinds, in this order: x, y, z, xy, xz, yz, xyz.
+ *   Vertices.  Edge (A, kind) carries a vertex iff exactly one of its ends is inside and some processed cube has it as an edge
+ *   (the cubes with lower corner A - o, o a corner offset that shares no axis with the kind).  Da = (double)sum_A / (double)n_A,
+ *   Db likewise for the upper end B;  tt = Da / (Da - Db);  P[a] = (float)(XA[a] + tt * (XB[a] - XA[a])).
+ *   Colour per channel: c_A = (2 rgb_A + nc_A) / (2 nc_A) in integers when nc_A > 0, else c_B; c_B likewise;
+ *   colour = clamp(floor(((double)c_A + tt * (double)(c_B - c_A)) + 0.5), 0, 255); 128 when nc_A = nc_B = 0.
+ *   Triangles of a tetrahedron, case = the set of inside corners:
+ *     one corner i inside or one corner i outside, the others j < k < l: (ij, ik, il);
+ *     i < j inside and k < l outside: the quadrilateral q = (ik, il, jl, jk) as (q0, q1, q2), (q0, q2, q3), in this order.
+ *   Each triangle is wound so that its normal points to the outside (the positive, camera-facing side); the other winding
+ *   swaps the second and third vertex.  The winding is a function of the case and of the parity of the axis order alone.
+ *   A point with sum == 0 is outside; its edges' vertices coincide with it and give zero-area triangles, which are kept.
+ *   Order.  Vertices by (block key, local index of A, kind); faces by (block key, local index of L, tetrahedron, triangle).
+ *
+ * cds_tsdf_integrate_f32: depths [n_views][h][w] fp32, masks uint8, images [n_views][h][w][3] uint8; frame_host: 4 doubles on the
+ *   HOST (origin, s); dims_host: 3 ints on the HOST (nb).  Adds n_views views to the accumulators.
+ *   CDS_EINVAL: a null frame_host / dims_host, a frame that is not finite, s <= 0, nb < 1 or more than CDS_TSDF_MAX_CELLS cells;
+ *   n_blocks < 0 or > CDS_TSDF_MAX_CELLS; n_views outside 1..CDS_TSDF_MAX_CHUNK; h or w < 1; n_views h w >= 2^31; T outside [s, 8 s];
+ *   a null device pointer (n_blocks == 0 returns 0 first).
+ * cds_tsdf_classify: vmask [n_blocks][512] uint8 (bit k: the point's edge of kind k carries a vertex), tcount [n_blocks][512]
+ *   uint8 (triangles of the point's cube), block_vertices / block_faces [n_blocks] int32 (their sums per block).
+ *   CDS_EINVAL: the frame cases above; min_weight < 1; a null pointer.
+ * cds_tsdf_emit: block_vstart / block_tstart [n_blocks] int32: the exclusive prefix sums of block_vertices / block_faces;
+ *   n_vertices / n_faces their totals; vstart [n_blocks][512] int32 scratch (the first vertex of every point);
+ *   vertices [n_vertices][3] fp32, colors [n_vertices][3] uint8, faces [n_faces][3] int32.
+ *   CDS_EINVAL: the frame cases above; a total < 0 or >= 2^31; a null pointer (outputs may be null when their total is 0).
+ */
+#define CDS_TSDF_MAX_CHUNK 32
+#define CDS_TSDF_MAX_CELLS (1 << 26)
+int cds_tsdf_integrate_f32(const int* keys, long long n_blocks, const double* frame_host, const int* dims_host, double trunc,
+                           const float* depths, const unsigned char* masks, const unsigned char* images, const double* cams,
+                           int n_views, int h, int w, float* sum, int* n, int* nc, int* rgb, void* stream);
+int cds_tsdf_classify(const int* keys, const int* table, long long n_blocks, const double* frame_host, const int* dims_host,
+                      const float* sum, const int* n, int min_weight, unsigned char* vmask, unsigned char* tcount,
+                      int* block_vertices, int* block_faces, void* stream);
+int cds_tsdf_emit(const int* keys, const int* table, long long n_blocks, const double* frame_host, const int* dims_host,
+                  const float* sum, const int* n, const int* nc, const int* rgb, const unsigned char* vmask,
+                  const unsigned char* tcount, const int* block_vstart, const int* block_tstart, long long n_vertices,
+                  long long n_faces, int* vstart, float* vertices, unsigned char* colors, int* faces, void* stream);
+
+/*
  * Norm-curvature bookkeeping of one FeatureNet level (module.py:250-251,257-258,264-265) in one launch:
  *   nc_sum[i] = (a[i]^2 + b[i]^2 + c[i]^2) / 3,  nc_abs[i] = |c[i]|   for the three DynamicConv curvature maps of the level
  */

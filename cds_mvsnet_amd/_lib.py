@@ -150,6 +150,10 @@ SIGNATURES = {
     "cds_tsdf_integrate_f32": [P, L, P, P, DB, P, P, P, P, I, I, I, P, P, P, P, P],
     "cds_tsdf_classify": [P, P, L, P, P, P, P, I, P, P, P, P, P],
     "cds_tsdf_emit": [P, P, L, P, P, P, P, P, P, P, P, P, P, L, L, P, P, P, P, P],
+    "cds_raster_project": [P, L, P, I, P, P, P],
+    "cds_raster_faces": [P, L, L, P, I, P, P, I, I, L, P, P, P],
+    "cds_raster_large": [P, L, P, L, L, P, I, P, P, I, I, P, P],
+    "cds_raster_resolve": [P, P, L, L, P, I, P, P, I, I, P, P, P, P, P, P],
     "cds_grid_hash_log2_slots": [L],
     "cds_grid_keys_f32": [P, L, P, P, P],
     "cds_grid_hash_build": [P, L, L, P, P, I, P],

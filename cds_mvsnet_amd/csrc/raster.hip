@@ -1,0 +1,306 @@
+// Rendering a mesh into the views of a scan (the rule is stated in include/cds_mvsnet_hip.h): depth, face index,
+// facing and colour per pixel, as a function of the input alone.
+//
+//   cds_raster_project   one thread per (view, vertex): rule 1, the snapped coordinates and the camera-space point
+//   cds_raster_faces     one thread per (view, face): rules 2-5 for the faces of at most `large_px` candidate pixels; a larger
+//                        face is only marked
+//   cds_raster_large     one wave per listed (view, face): its 64 lanes stride the candidate pixels
+//   cds_raster_resolve   one thread per pixel: rule 6 from the winning key
+//
+// Every decision is made in int64 or fp64, with the bracketing of the rule (the library is built with -ffp-contract=off).  The
+// visibility reduction is a 64-bit unsigned minimum over keys (depth bits, face index): it does not depend on the order in which
+// fragments arrive, so it is done with the vector memory atomic that atomicMin compiles to (global_atomic_umin_x2, no
+// compare-and-swap loop), the only atomic of this file.  Every loop has its bound fixed before it starts: the candidate count of the face.
+#include "cds_common.hpp"
+
+namespace {
+
+constexpr int kCam = CDS_RASTER_CAM;           // doubles per camera: R 0..8, t 9..11, fx 12, s 13, cx 14, fy 15, cy 16
+constexpr int kUnusable = INT_MIN;             // X of a vertex that rule 1 rejects
+constexpr long long kSnapLimit = 1ll << 28;
+constexpr int kThreads = 256;
+
+// Rules 2 and 3 up to the candidate box of one face in one view.
+struct FaceSetup {
+  long long X[3], Y[3];
+  int g;                                       // sign of A
+  int px0, py0, bw, bh;                        // candidate pixels: px0 .. px0 + bw - 1, py0 .. py0 + bh - 1
+  long long count;                             // bw bh, 0 when the face is not drawn or no pixel centre lies in its box
+};
+
+// Rule 4: the face's plane in camera space.
+struct FacePlane {
+  double n[3], d;
+};
+
+__device__ __forceinline__ long long floor_div256(long long a) { return a >> 8; }   // arithmetic shift: floor for negatives too
+
+__device__ __forceinline__ bool face_setup(const int* __restrict__ faces, const int* __restrict__ xy, long long face,
+                                           long long n_vertices, int h, int w, int idx[3], FaceSetup& s) {
+  s.count = 0;
+  for (int k = 0; k < 3; ++k) {
+    idx[k] = faces[3 * face + k];
+    if ((unsigned long long)(long long)idx[k] >= (unsigned long long)n_vertices) return false;   // never read outside the mesh
+    const int2 p = *reinterpret_cast<const int2*>(xy + 2 * (long long)idx[k]);
+    if (p.x == kUnusable) return false;
+    s.X[k] = p.x;
+    s.Y[k] = p.y;
+  }
+  const long long A = (s.X[1] - s.X[0]) * (s.Y[2] - s.Y[0]) - (s.Y[1] - s.Y[0]) * (s.X[2] - s.X[0]);
+  if (A == 0) return false;
+  s.g = A > 0 ? 1 : -1;
+  const long long xl = min(s.X[0], min(s.X[1], s.X[2])), xh = max(s.X[0], max(s.X[1], s.X[2]));
+  const long long yl = min(s.Y[0], min(s.Y[1], s.Y[2])), yh = max(s.Y[0], max(s.Y[1], s.Y[2]));
+  // the centre 256 p + 128 lies in [lo, hi]  iff  ceil((lo - 128) / 256) <= p <= floor((hi - 128) / 256)
+  const long long px0 = max(0ll, floor_div256(xl - 128 + 255)), px1 = min((long long)w - 1, floor_div256(xh - 128));
+  const long long py0 = max(0ll, floor_div256(yl - 128 + 255)), py1 = min((long long)h - 1, floor_div256(yh - 128));
+  if (px1 < px0 || py1 < py0) return false;
+  s.px0 = (int)px0; s.py0 = (int)py0;
+  s.bw = (int)(px1 - px0 + 1); s.bh = (int)(py1 - py0 + 1);
+  s.count = (long long)s.bw * s.bh;
+  return true;
+}
+
+// Rule 3 for the pixel (px, py).
+__device__ __forceinline__ bool covered(const FaceSetup& s, int px, int py) {
+  const long long Qx = 256ll * px + 128, Qy = 256ll * py + 128;
+  bool in = true;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    const int j = i == 2 ? 0 : i + 1;
+    const long long dx = s.g * (s.X[j] - s.X[i]), dy = s.g * (s.Y[j] - s.Y[i]);
+    const long long E = dx * (Qy - s.Y[i]) - dy * (Qx - s.X[i]);
+    in = in && (E > 0 || (E == 0 && (dy < 0 || (dy == 0 && dx > 0))));
+  }
+  return in;
+}
+
+__device__ __forceinline__ void load_point(const double* __restrict__ xc, int v, double p[3]) {
+  p[0] = xc[3 * (long long)v]; p[1] = xc[3 * (long long)v + 1]; p[2] = xc[3 * (long long)v + 2];
+}
+
+__device__ __forceinline__ FacePlane face_plane(const double a[3], const double b[3], const double c[3]) {
+  const double e1[3] = {b[0] - a[0], b[1] - a[1], b[2] - a[2]}, e2[3] = {c[0] - a[0], c[1] - a[1], c[2] - a[2]};
+  FacePlane f;
+  f.n[0] = e1[1] * e2[2] - e1[2] * e2[1];
+  f.n[1] = e1[2] * e2[0] - e1[0] * e2[2];
+  f.n[2] = e1[0] * e2[1] - e1[1] * e2[0];
+  f.d = (f.n[0] * a[0] + f.n[1] * a[1]) + f.n[2] * a[2];
+  return f;
+}
+
+// Rule 4 for one pixel: the ray (rx, ry, 1) and the depth along it.  The fragment exists iff the result is finite and > 0.
+__device__ __forceinline__ double fragment_depth(const FacePlane& f, const double* __restrict__ cam, int px, int py, double& rx,
+                                                 double& ry) {
+  ry = (((double)py + 0.5) - cam[16]) / cam[15];
+  rx = ((((double)px + 0.5) - cam[14]) - cam[13] * ry) / cam[12];
+  const double den = (f.n[0] * rx + f.n[1] * ry) + f.n[2];
+  return f.d / den;
+}
+
+__device__ __forceinline__ bool fragment_exists(double zf) { return zf > 0.0 && zf <= 1.7976931348623157e308; }
+
+// Rules 3-5 for candidate i of the face.
+__device__ __forceinline__ void draw_candidate(const FaceSetup& s, const FacePlane& f, const double* __restrict__ cam, long long i,
+                                               unsigned face, int w, unsigned long long* __restrict__ keys) {
+  const int px = s.px0 + (int)(i % s.bw), py = s.py0 + (int)(i / s.bw);
+  if (!covered(s, px, py)) return;
+  double rx, ry;
+  const double zf = fragment_depth(f, cam, px, py, rx, ry);
+  if (!fragment_exists(zf)) return;
+  const unsigned long long key = ((unsigned long long)__float_as_uint((float)zf) << 32) | face;
+  atomicMin(keys + (size_t)py * w + px, key);
+}
+
+// ------------------------------------------------------------------------------------------------------------------ project
+__global__ __launch_bounds__(kThreads) void raster_project_kernel(const float* __restrict__ vertices, long long n_vertices,
+                                                                  const double* __restrict__ cams, int* __restrict__ xy,
+                                                                  double* __restrict__ xc) {
+  const long long i = (long long)blockIdx.x * kThreads + threadIdx.x;
+  if (i >= n_vertices) return;
+  const int view = blockIdx.y;
+  const double* c = cams + (long long)view * kCam;
+  const double X0 = vertices[3 * i], X1 = vertices[3 * i + 1], X2 = vertices[3 * i + 2];
+  const double xc0 = ((c[0] * X0 + c[1] * X1) + c[2] * X2) + c[9];
+  const double xc1 = ((c[3] * X0 + c[4] * X1) + c[5] * X2) + c[10];
+  const double z = ((c[6] * X0 + c[7] * X1) + c[8] * X2) + c[11];
+  const double u = ((c[12] * xc0 + c[13] * xc1) + c[14] * z) / z;
+  const double v = (c[15] * xc1 + c[16] * z) / z;
+  const double sx = floor(u * 256.0 + 0.5), sy = floor(v * 256.0 + 0.5);
+  // an infinite or NaN u fails |X| < 2^28 as well: u 256 + 0.5 keeps it
+  const bool usable = z > 0.0 && fabs(u) <= 1.7976931348623157e308 && fabs(v) <= 1.7976931348623157e308 &&
+                      fabs(sx) < (double)kSnapLimit && fabs(sy) < (double)kSnapLimit;
+  const long long o = (long long)view * n_vertices + i;
+  xy[2 * o] = usable ? (int)sx : kUnusable;
+  xy[2 * o + 1] = usable ? (int)sy : kUnusable;
+  xc[3 * o] = xc0; xc[3 * o + 1] = xc1; xc[3 * o + 2] = z;
+}
+
+// -------------------------------------------------------------------------------------------------------------------- faces
+__global__ __launch_bounds__(kThreads) void raster_faces_kernel(const int* __restrict__ faces, long long n_faces,
+                                                                long long n_vertices, const double* __restrict__ cams,
+                                                                const int* __restrict__ xy, const double* __restrict__ xc, int h,
+                                                                int w, long long large_px, unsigned long long* __restrict__ keys,
+                                                                unsigned char* __restrict__ large) {
+  const long long face = (long long)blockIdx.x * kThreads + threadIdx.x;
+  if (face >= n_faces) return;
+  const int view = blockIdx.y;
+  int idx[3];
+  FaceSetup s;
+  const bool drawn = face_setup(faces, xy + 2 * (long long)view * n_vertices, face, n_vertices, h, w, idx, s);
+  const bool is_large = drawn && s.count > large_px;
+  large[(long long)view * n_faces + face] = is_large ? 1 : 0;
+  if (!drawn || is_large) return;
+  const double* xcv = xc + 3 * (long long)view * n_vertices;
+  double a[3], b[3], c[3];
+  load_point(xcv, idx[0], a); load_point(xcv, idx[1], b); load_point(xcv, idx[2], c);
+  const FacePlane f = face_plane(a, b, c);
+  const double* cam = cams + (long long)view * kCam;
+  unsigned long long* kv = keys + (size_t)view * h * w;
+  const long long count = s.count;                                     // <= large_px
+  for (long long i = 0; i < count; ++i) draw_candidate(s, f, cam, i, (unsigned)face, w, kv);
+}
+
+// One wave per entry of `list` (view n_faces + face); its lanes take the candidates lane, lane + 64, ...
+__global__ __launch_bounds__(kThreads) void raster_large_kernel(const long long* __restrict__ list, long long n_list,
+                                                                const int* __restrict__ faces, long long n_faces,
+                                                                long long n_vertices, int n_views,
+                                                                const double* __restrict__ cams, const int* __restrict__ xy,
+                                                                const double* __restrict__ xc, int h, int w,
+                                                                unsigned long long* __restrict__ keys) {
+  const long long item = (long long)blockIdx.x * (kThreads / 64) + (threadIdx.x >> 6);
+  if (item >= n_list) return;
+  const long long e = list[item];
+  if (e < 0 || e >= (long long)n_views * n_faces) return;              // an entry that does not belong to this chunk
+  const int view = (int)(e / n_faces);
+  const long long face = e % n_faces;
+  int idx[3];
+  FaceSetup s;
+  if (!face_setup(faces, xy + 2 * (long long)view * n_vertices, face, n_vertices, h, w, idx, s)) return;
+  const double* xcv = xc + 3 * (long long)view * n_vertices;
+  double a[3], b[3], c[3];
+  load_point(xcv, idx[0], a); load_point(xcv, idx[1], b); load_point(xcv, idx[2], c);
+  const FacePlane f = face_plane(a, b, c);
+  const double* cam = cams + (long long)view * kCam;
+  unsigned long long* kv = keys + (size_t)view * h * w;
+  const long long count = s.count;                                     // <= h w
+  for (long long i = threadIdx.x & 63; i < count; i += 64) draw_candidate(s, f, cam, i, (unsigned)face, w, kv);
+}
+
+// ------------------------------------------------------------------------------------------------------------------ resolve
+__global__ __launch_bounds__(kThreads) void raster_resolve_kernel(const unsigned long long* __restrict__ keys,
+                                                                  const int* __restrict__ faces, long long n_faces,
+                                                                  long long n_vertices, const double* __restrict__ cams,
+                                                                  const double* __restrict__ xc,
+                                                                  const unsigned char* __restrict__ colors, int h, int w,
+                                                                  float* __restrict__ depth, int* __restrict__ face_out,
+                                                                  unsigned char* __restrict__ front,
+                                                                  unsigned char* __restrict__ valid,
+                                                                  unsigned char* __restrict__ image) {
+  const long long p = (long long)blockIdx.x * kThreads + threadIdx.x, hw = (long long)h * w;
+  if (p >= hw) return;
+  const int view = blockIdx.y;
+  const size_t o = (size_t)view * hw + p;
+  const unsigned long long key = keys[o];
+  const long long face = (long long)(key & 0xffffffffull);
+  float z = 0.f;
+  int fo = -1;
+  unsigned char fr = 0, rgb[3] = {0, 0, 0};
+  int idx[3] = {0, 0, 0};
+  bool hit = key != ~0ull && face < n_faces;
+  if (hit)
+    for (int k = 0; k < 3; ++k) {
+      idx[k] = faces[3 * face + k];
+      hit = hit && (unsigned long long)(long long)idx[k] < (unsigned long long)n_vertices;
+    }
+  if (hit) {
+    z = __uint_as_float((unsigned)(key >> 32));
+    fo = (int)face;
+    const double* xcv = xc + 3 * (long long)view * n_vertices;
+    double a[3], b[3], c[3];
+    load_point(xcv, idx[0], a); load_point(xcv, idx[1], b); load_point(xcv, idx[2], c);
+    const FacePlane f = face_plane(a, b, c);
+    fr = f.d < 0.0 ? 1 : 0;
+    if (colors && image) {
+      double rx, ry;
+      const double zf = fragment_depth(f, cams + (long long)view * kCam, (int)(p % w), (int)(p / w), rx, ry);
+      const double P[3] = {zf * rx, zf * ry, zf};
+      const double pa[3] = {a[0] - P[0], a[1] - P[1], a[2] - P[2]}, pb[3] = {b[0] - P[0], b[1] - P[1], b[2] - P[2]},
+                   pc[3] = {c[0] - P[0], c[1] - P[1], c[2] - P[2]};
+      const double nn = (f.n[0] * f.n[0] + f.n[1] * f.n[1]) + f.n[2] * f.n[2];
+      const double* q[4] = {pb, pc, pa, pb};                           // w_a from (b, c), w_b from (c, a), w_c from (a, b)
+      double wt[3];
+      for (int k = 0; k < 3; ++k) {
+        const double* s = q[k];
+        const double* t = q[k + 1];
+        const double c0 = s[1] * t[2] - s[2] * t[1], c1 = s[2] * t[0] - s[0] * t[2], c2 = s[0] * t[1] - s[1] * t[0];
+        wt[k] = ((f.n[0] * c0 + f.n[1] * c1) + f.n[2] * c2) / nn;
+      }
+      for (int ch = 0; ch < 3; ++ch) {
+        const double ca = colors[3 * (long long)idx[0] + ch], cb = colors[3 * (long long)idx[1] + ch],
+                     cc = colors[3 * (long long)idx[2] + ch];
+        const double val = (wt[0] * ca + wt[1] * cb) + wt[2] * cc;
+        const double cl = val > 0.0 ? (val < 255.0 ? val : 255.0) : 0.0;       // NaN -> 0
+        rgb[ch] = (unsigned char)(int)floor(cl + 0.5);
+      }
+    }
+  }
+  depth[o] = z;
+  face_out[o] = fo;
+  front[o] = fr;
+  valid[o] = fr;                                                         // hit and front
+  if (image) { image[3 * o] = rgb[0]; image[3 * o + 1] = rgb[1]; image[3 * o + 2] = rgb[2]; }
+}
+
+bool sizes_ok(long long n_vertices, long long n_faces, int n_views, int h, int w) {
+  return n_vertices >= 0 && n_vertices <= 0x7fffffffLL && n_faces >= 0 && n_faces <= 0x7fffffffLL && n_views >= 1 &&
+         n_views <= CDS_RASTER_MAX_CHUNK && h >= 1 && w >= 1 && (long long)h * w <= 0x7fffffffLL;
+}
+
+unsigned blocks_for(long long n) { return (unsigned)((n + kThreads - 1) / kThreads); }
+
+}  // namespace
+
+extern "C" int cds_raster_project(const float* vertices, long long n_vertices, const double* cams, int n_views, int* xy, double* xc,
+                                  void* stream) {
+  if (!sizes_ok(n_vertices, 0, n_views, 1, 1)) return CDS_EINVAL;
+  if (n_vertices == 0) return 0;
+  if (!vertices || !cams || !xy || !xc) return CDS_EINVAL;
+  hipLaunchKernelGGL(raster_project_kernel, dim3(blocks_for(n_vertices), (unsigned)n_views), dim3(kThreads), 0, (hipStream_t)stream,
+                     vertices, n_vertices, cams, xy, xc);
+  return cds_launch_status();
+}
+
+extern "C" int cds_raster_faces(const int* faces, long long n_faces, long long n_vertices, const double* cams, int n_views,
+                                const int* xy, const double* xc, int h, int w, long long large_px, unsigned long long* keys,
+                                unsigned char* large, void* stream) {
+  if (!sizes_ok(n_vertices, n_faces, n_views, h, w) || large_px < 1) return CDS_EINVAL;
+  if (n_faces == 0) return 0;
+  if (!faces || !cams || !xy || !xc || !keys || !large) return CDS_EINVAL;
+  hipLaunchKernelGGL(raster_faces_kernel, dim3(blocks_for(n_faces), (unsigned)n_views), dim3(kThreads), 0, (hipStream_t)stream, faces,
+                     n_faces, n_vertices, cams, xy, xc, h, w, large_px, keys, large);
+  return cds_launch_status();
+}
+
+extern "C" int cds_raster_large(const long long* list, long long n_list, const int* faces, long long n_faces, long long n_vertices,
+                                const double* cams, int n_views, const int* xy, const double* xc, int h, int w,
+                                unsigned long long* keys, void* stream) {
+  if (!sizes_ok(n_vertices, n_faces, n_views, h, w) || n_list < 0 || n_list > CDS_RASTER_MAX_LIST) return CDS_EINVAL;
+  if (n_list == 0 || n_faces == 0) return 0;
+  if (!list || !faces || !cams || !xy || !xc || !keys) return CDS_EINVAL;
+  const unsigned blocks = (unsigned)((n_list + kThreads / 64 - 1) / (kThreads / 64));
+  hipLaunchKernelGGL(raster_large_kernel, dim3(blocks), dim3(kThreads), 0, (hipStream_t)stream, list, n_list, faces, n_faces,
+                     n_vertices, n_views, cams, xy, xc, h, w, keys);
+  return cds_launch_status();
+}
+
+extern "C" int cds_raster_resolve(const unsigned long long* keys, const int* faces, long long n_faces, long long n_vertices,
+                                  const double* cams, int n_views, const double* xc, const unsigned char* colors, int h, int w,
+                                  float* depth, int* face, unsigned char* front, unsigned char* valid, unsigned char* image,
+                                  void* stream) {
+  if (!sizes_ok(n_vertices, n_faces, n_views, h, w)) return CDS_EINVAL;
+  if (!keys || !cams || !depth || !face || !front || !valid || (n_faces > 0 && (!faces || !xc))) return CDS_EINVAL;
+  hipLaunchKernelGGL(raster_resolve_kernel, dim3(blocks_for((long long)h * w), (unsigned)n_views), dim3(kThreads), 0,
+                     (hipStream_t)stream, keys, faces, n_faces, n_vertices, cams, xc, colors, h, w, depth, face, front, valid, image);
+  return cds_launch_status();
+}

@@ -176,6 +176,9 @@ def parse_args(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
                                                             "loaders pass num_srcs as nviews)")
     ap.add_argument("--num_depths", type=int, default=192)
     ap.add_argument("--interval_scale", type=float, default=1.06)
+    ap.add_argument("--crop", default=None, metavar="H,W",
+                    help="centre crop of images and ground truth, for every dataset (default: the layout's own, 512,640 for dtu and "
+                         "576,768 for blended); a tree of render --export_blended needs the size of its maps or less")
     ap.add_argument("--batch_size", type=int, default=2)
     ap.add_argument("--val_batch_size", type=int, default=1)
     ap.add_argument("--epochs", type=int, default=10)
@@ -207,6 +210,10 @@ def parse_args(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
         ap.error("--pretrained and --resume exclude each other")
     try:
         args.dlossw = [float(x) for x in args.dlossw.split(",")]
+        if args.crop is not None:
+            args.crop = [int(x) for x in args.crop.split(",")]
+            if len(args.crop) != 2 or min(args.crop) < 1:
+                raise ValueError(f"--crop {args.crop}: expected H,W, both positive")
         parse_monitor(args.monitor)
     except ValueError as e:
         ap.error(str(e))
@@ -233,10 +240,10 @@ def main(argv: Optional[Sequence[str]] = None) -> List[Dict[str, object]]:
     train_sets, val_sets = [], []
     for i, name in enumerate(args.dataset):
         train_sets.append(DATASETS[name](args.datapath[i], args.trainlist[i], "train", args.num_srcs, args.num_depths, args.interval_scale,
-                                         seed=args.seed))
+                                         crop=args.crop, seed=args.seed))
         if args.vallist:
             val_sets.append(DATASETS[name](args.datapath[i], args.vallist[i], "val", VAL_VIEWS, args.num_depths, args.interval_scale,
-                                           seed=args.seed))
+                                           crop=args.crop, seed=args.seed))
     config = {"arch": {"type": "CDSMVSNet", "args": arch}, "args": {k: v for k, v in vars(args).items()}}
     try:
         return fit(model, train_sets, val_sets, args.epochs, batch_size=args.batch_size, val_batch_size=args.val_batch_size, lr=args.lr,

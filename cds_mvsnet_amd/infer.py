@@ -13,7 +13,9 @@ or, with `--filter_method dynamic`, the dynamic consistency check (fusion.py; `-
 `--dyn_views`).  `--normals` (`--normal_radius`, `--normal_jump`, `--normal_min_pts`; not for gipuma) adds each point's oriented
 normal and `--merge_voxel SIZE` (`--merge_min_points K`) merges the scan to one point per occupied voxel.
 `--mesh_voxel SIZE` (`--mesh_trunc T`, `--mesh_min_weight N`; not for gipuma) also writes `<out>/<scan>_mesh.ply`, a triangle mesh
-from the same fusion pass (mesh.py).
+from the same fusion pass (mesh.py).  With it, `--render_mesh` (`--back`, `--max_rel_diff R`, `--save_image`) renders
+that mesh into every view, `<out>/<scan>/depth_mesh/%08d.pfm`, and `--export_blended DIR` writes the tree `fit --dataset blended`
+trains from (render.py).
 `--save_stages` also writes the three stages' own depth maps, `<out>/<scan>/depth_stage{1,2,3}/%08d.pfm`, at their resolutions
 (what evaluations/precision.py scores stage by stage; `python -m cds_mvsnet_amd.depth_eval --folders ...`).
 
@@ -234,6 +236,13 @@ def run(args) -> float:
                              os.path.join(args.outdir, f"{scan}_mesh.ply"), args.mesh_voxel, args.mesh_trunc, args.mesh_min_weight,
                              cloud_ply=ply, **kw)
             print(f"[{rank}] {scan}_mesh.ply: {format_mesh(info)}", flush=True)
+            if args.render_mesh:
+                # the mesh just written, from the device tensors, into every view of the scan
+                from .render import export_blended, render_scan
+                render_scan(os.path.join(args.outdir, scan), info["mesh"], os.path.join(args.testpath, scan), back=args.back,
+                            max_rel_diff=args.max_rel_diff, save_image=args.save_image, device=kw.get("device", "cuda"))
+                if args.export_blended:
+                    export_blended(scan, args.testpath, args.outdir, args.export_blended)
             return info["cloud"]
 
         if world > 1:  # every rank's depth maps must be on disk before any scan is fused
@@ -314,7 +323,18 @@ def parse_args(argv=None) -> argparse.Namespace:
     add_cloud_args(ap)
     from .mesh import add_mesh_args, check_voxel
     add_mesh_args(ap)
+    from .render import add_render_args
+    ap.add_argument("--render_mesh", action="store_true",
+                    help="--mesh_voxel: render the mesh into every view and write <outdir>/<scan>/depth_mesh/%%08d.pfm (render.py, "
+                         "DESIGN §1.10)")
+    add_render_args(ap)
     args = ap.parse_args(argv)
+    if args.render_mesh and args.mesh_voxel is None:
+        ap.error("--render_mesh renders the mesh of --mesh_voxel: give --fuse --mesh_voxel SIZE as well")
+    if not args.render_mesh and (args.export_blended or args.save_image or args.max_rel_diff is not None or args.back != "mask"):
+        ap.error("--export_blended, --save_image, --max_rel_diff and --back belong to --render_mesh")
+    if args.max_rel_diff is not None and not args.max_rel_diff >= 0:
+        ap.error(f"--max_rel_diff must be >= 0, got {args.max_rel_diff}")
     if args.mesh_voxel is not None:
         if args.filter_method == "gipuma":
             ap.error("--mesh_voxel is not implemented for --filter_method gipuma (its fused point has no single depth map); "

@@ -286,7 +286,8 @@ def mesh_scan(pair_folder: str, scan_folder: str, plyfilename: str, voxel: float
     """One scan from saved depth maps to a mesh at ``plyfilename``: the fusion pass of :func:`fusion.filter_depth` (``method``
     "normal" or "dynamic" and its ``fusion_options``), then allocation from every view's kept points, integration of the fused
     depth maps in ``pair.txt`` order and extraction.  ``cloud_ply``: also write the fused cloud there, from the same pass and byte
-    for byte what ``filter_depth`` writes alone.  -> {"vertices", "faces", "blocks": counts, "cloud": filter_depth's result}."""
+    for byte what ``filter_depth`` writes alone.  -> {"vertices", "faces", "blocks": counts, "cloud": filter_depth's result,
+    "mesh": the mesh dict of :meth:`TsdfVolume.extract`, still on the device (render.render_scan takes it)}."""
     from .fusion import filter_depth
     if method == "gipuma":
         raise ValueError("mesh_scan: gipuma fusion is not supported (its fused point has no single depth map); use normal or dynamic")
@@ -297,7 +298,8 @@ def mesh_scan(pair_folder: str, scan_folder: str, plyfilename: str, voxel: float
     cloud = filter_depth(pair_folder, scan_folder, cloud_ply, device=device, method=method, collect=views, **fusion_options)
     mesh, vol = mesh_views(views, voxel, trunc, min_weight, device)
     write_mesh_ply(plyfilename, mesh["vertices"].cpu().numpy(), mesh["colors"].cpu().numpy(), mesh["faces"].cpu().numpy())
-    return {"vertices": int(mesh["vertices"].shape[0]), "faces": int(mesh["faces"].shape[0]), "blocks": vol.n_blocks, "cloud": cloud}
+    return {"vertices": int(mesh["vertices"].shape[0]), "faces": int(mesh["faces"].shape[0]), "blocks": vol.n_blocks, "cloud": cloud,
+            "mesh": mesh}
 
 
 def format_mesh(info: Dict[str, object]) -> str:

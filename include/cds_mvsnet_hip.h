@@ -671,6 +671,62 @@ int cds_tsdf_emit(const int* keys, const int* table, long long n_blocks, const d
                   long long n_faces, int* vstart, float* vertices, unsigned char* colors, int* faces, void* stream);
 
 /*
+ * Rendering a triangle mesh into the views of a scan: depth, face, facing and colour per pixel (csrc/raster.hip).
+ *
+ * Inputs.  vertices fp32 [n_vertices][3], faces int32 [n_faces][3], optional colours uint8 [n_vertices][3]; per view
+ *   cams [CDS_RASTER_CAM] doubles: R 0..8 and t 9..11 the rows of E = [R | t] world -> camera, then fx 12, s 13, cx 14, fy 15,
+ *   cy 16 of K = [[fx, s, cx], [0, fy, cy], [0, 0, 1]] (the host refuses another K); 17.. unused.  A map of h x w pixels.
+ *   All arithmetic is fp64 from the fp32 entries, bracketed as written; decisions on snapped coordinates are exact in int64.
+ * 1. Vertex.  Xc[r] = ((R[r][0] X0 + R[r][1] X1) + R[r][2] X2) + t[r];  z = Xc[2].
+ *      u = ((fx Xc0 + s Xc1) + cx z) / z,  v = (fy Xc1 + cy z) / z.  Pixel x covers [x, x + 1), its centre is x + 0.5.
+ *      X = floor(u * 256 + 0.5), Y = floor(v * 256 + 0.5) as int64.
+ *      The vertex is usable iff z > 0, u and v are finite, |X| < 2^28 and |Y| < 2^28.
+ * 2. Face (a, b, c) with snapped corners 0, 1, 2.  Drawn iff its three vertices are usable and
+ *      A = (X1 - X0)(Y2 - Y0) - (Y1 - Y0)(X2 - X0) != 0.  No clipping: a face with an unusable vertex is dropped whole.
+ * 3. Coverage.  Q = (256 px + 128, 256 py + 128), g = sign(A).  For every edge i -> j, j = (i + 1) mod 3:
+ *      dx = g (Xj - Xi), dy = g (Yj - Yi), E = dx (Qy - Yi) - dy (Qx - Xi).
+ *      The pixel is covered iff for all three edges E > 0, or E == 0 and (dy < 0 or (dy == 0 and dx > 0)) (top-left).
+ *      Candidates: the pixels of the map with min X <= Qx <= max X and min Y <= Qy <= max Y.
+ * 4. Depth, from the face's plane in camera space.  n = (Xc_b - Xc_a) x (Xc_c - Xc_a), each component as p q - r s
+ *      (n0 = e1[1] e2[2] - e1[2] e2[1], cyclic);  d = (n0 Xa0 + n1 Xa1) + n2 Xa2.
+ *      ry = ((py + 0.5) - cy) / fy,  rx = (((px + 0.5) - cx) - s ry) / fx,  den = (n0 rx + n1 ry) + n2,  zf = d / den.
+ *      The fragment exists iff zf is finite and zf > 0.  front = d < 0: the face's own winding looks at the camera.
+ * 5. Visibility.  key = ((uint64)bits((float)zf) << 32) | face index; the pixel takes the minimum key over its fragments: the
+ *      nearest depth, the lowest face index on a tie.  The minimum does not depend on any order.
+ * 6. Outputs per view: depth fp32 (the key's upper word; 0 without a hit), face int32 (-1 without a hit), front uint8,
+ *      valid uint8 = hit and front, and, with colours, image uint8 [h][w][3] (0 without a hit):  P = zf (rx, ry, 1) with the zf
+ *      of rule 4 for the winning face,  w_a = n . ((Xc_b - P) x (Xc_c - P)) / (n . n), w_b from (c, a), w_c from (a, b), the
+ *      cross products as in 4 and every dot product as (x0 y0 + x1 y1) + x2 y2;
+ *      channel = floor(clamp((w_a c_a + w_b c_b) + w_c c_c, 0, 255) + 0.5), with clamp(NaN) = 0.
+ *
+ * cds_raster_project: xy [n_views][n_vertices][2] int32 (X, Y; both INT_MIN for an unusable vertex), xc [n_views][n_vertices][3]
+ *   doubles (Xc).
+ * cds_raster_faces: keys [n_views][h][w] uint64, filled with all ones by the caller before the first launch; rules 2-5 for every
+ *   face with at most large_px candidates; large [n_views][n_faces] uint8 is written for EVERY (view, face): 1 for a drawn face
+ *   with more candidates, which is NOT drawn here, else 0.
+ * cds_raster_large: list [n_list] int64 of entries view * n_faces + face; one wave draws one entry, whatever its size.
+ *   The result of faces + large over the marked entries does not depend on large_px.
+ * cds_raster_resolve: rule 6; colors and image may both be null.
+ *   CDS_EINVAL: n_vertices or n_faces < 0 or >= 2^31; n_views outside 1..CDS_RASTER_MAX_CHUNK; h or w < 1; h w >= 2^31;
+ *   large_px < 1; n_list < 0 or > CDS_RASTER_MAX_LIST; a null required pointer (an empty mesh or list returns 0 first, except in
+ *   resolve, which then writes the all-miss outputs).  A face index outside the vertices drops the face; nothing is read there.
+ */
+#define CDS_RASTER_CAM 24
+#define CDS_RASTER_MAX_CHUNK 32
+#define CDS_RASTER_MAX_LIST (1ll << 30)
+int cds_raster_project(const float* vertices, long long n_vertices, const double* cams, int n_views, int* xy, double* xc,
+                       void* stream);
+int cds_raster_faces(const int* faces, long long n_faces, long long n_vertices, const double* cams, int n_views, const int* xy,
+                     const double* xc, int h, int w, long long large_px, unsigned long long* keys, unsigned char* large,
+                     void* stream);
+int cds_raster_large(const long long* list, long long n_list, const int* faces, long long n_faces, long long n_vertices,
+                     const double* cams, int n_views, const int* xy, const double* xc, int h, int w, unsigned long long* keys,
+                     void* stream);
+int cds_raster_resolve(const unsigned long long* keys, const int* faces, long long n_faces, long long n_vertices,
+                       const double* cams, int n_views, const double* xc, const unsigned char* colors, int h, int w, float* depth,
+                       int* face, unsigned char* front, unsigned char* valid, unsigned char* image, void* stream);
+
+/*
  * Norm-curvature bookkeeping of one FeatureNet level (module.py:250-251,257-258,264-265) in one launch:
  *   nc_sum[i] = (a[i]^2 + b[i]^2 + c[i]^2) / 3,  nc_abs[i] = |c[i]|   for the three DynamicConv curvature maps of the level
  */

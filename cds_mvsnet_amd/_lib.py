@@ -154,6 +154,12 @@ SIGNATURES = {
     "cds_raster_faces": [P, L, L, P, I, P, P, I, I, L, P, P, P],
     "cds_raster_large": [P, L, P, L, L, P, I, P, P, I, I, P, P],
     "cds_raster_resolve": [P, P, L, L, P, I, P, P, I, I, P, P, P, P, P, P],
+    "cds_mesh_cc_init": [P, L, P],
+    "cds_mesh_cc_hook": [P, L, L, P, P, P],
+    "cds_mesh_cc_jump": [P, L, P],
+    "cds_mesh_cc_count": [P, L, L, P, P, P],
+    "cds_mesh_cc_mark": [P, L, L, P, P, P, P, P],
+    "cds_mesh_cc_gather": [P, P, P, L, L, P, P, P, P, L, L, P, P, P, P],
     "cds_grid_hash_log2_slots": [L],
     "cds_grid_keys_f32": [P, L, P, P, P],
     "cds_grid_hash_build": [P, L, L, P, P, I, P],

@@ -13,7 +13,8 @@ or, with `--filter_method dynamic`, the dynamic consistency check (fusion.py; `-
 `--dyn_views`).  `--normals` (`--normal_radius`, `--normal_jump`, `--normal_min_pts`; not for gipuma) adds each point's oriented
 normal and `--merge_voxel SIZE` (`--merge_min_points K`) merges the scan to one point per occupied voxel.
 `--mesh_voxel SIZE` (`--mesh_trunc T`, `--mesh_min_weight N`; not for gipuma) also writes `<out>/<scan>_mesh.ply`, a triangle mesh
-from the same fusion pass (mesh.py).  With it, `--render_mesh` (`--back`, `--max_rel_diff R`, `--save_image`) renders
+from the same fusion pass (mesh.py); `--mesh_min_component N` / `--mesh_keep_largest K` drop its small connected
+components first.  With it, `--render_mesh` (`--back`, `--max_rel_diff R`, `--save_image`) renders
 that mesh into every view, `<out>/<scan>/depth_mesh/%08d.pfm`, and `--export_blended DIR` writes the tree `fit --dataset blended`
 trains from (render.py).
 `--save_stages` also writes the three stages' own depth maps, `<out>/<scan>/depth_stage{1,2,3}/%08d.pfm`, at their resolutions
@@ -234,7 +235,7 @@ def run(args) -> float:
                 return filter_depth(os.path.join(args.testpath, scan), os.path.join(args.outdir, scan), ply, **kw)
             info = mesh_scan(os.path.join(args.testpath, scan), os.path.join(args.outdir, scan),
                              os.path.join(args.outdir, f"{scan}_mesh.ply"), args.mesh_voxel, args.mesh_trunc, args.mesh_min_weight,
-                             cloud_ply=ply, **kw)
+                             cloud_ply=ply, min_component=args.mesh_min_component, keep_largest=args.mesh_keep_largest, **kw)
             print(f"[{rank}] {scan}_mesh.ply: {format_mesh(info)}", flush=True)
             if args.render_mesh:
                 # the mesh just written, from the device tensors, into every view of the scan
@@ -321,7 +322,7 @@ def parse_args(argv=None) -> argparse.Namespace:
                     help="dynamic: a pixel is kept when n views agree at level n for some n in this range")
     from .fusion import add_cloud_args
     add_cloud_args(ap)
-    from .mesh import add_mesh_args, check_voxel
+    from .mesh import add_mesh_args, check_clean_args, check_voxel
     add_mesh_args(ap)
     from .render import add_render_args
     ap.add_argument("--render_mesh", action="store_true",
@@ -335,6 +336,7 @@ def parse_args(argv=None) -> argparse.Namespace:
         ap.error("--export_blended, --save_image, --max_rel_diff and --back belong to --render_mesh")
     if args.max_rel_diff is not None and not args.max_rel_diff >= 0:
         ap.error(f"--max_rel_diff must be >= 0, got {args.max_rel_diff}")
+    check_clean_args(ap, args, args.mesh_voxel is not None)
     if args.mesh_voxel is not None:
         if args.filter_method == "gipuma":
             ap.error("--mesh_voxel is not implemented for --filter_method gipuma (its fused point has no single depth map); "

@@ -8,11 +8,19 @@ of every cube: welded vertices, consistent winding, colours, a fixed order.  The
 the blocks out.  There is no CPU path.
 
     python -m cds_mvsnet_amd.mesh --testpath <scenes> --outdir <out> --testlist <list> --mesh_voxel SIZE [--mesh_trunc T]
-        [--mesh_min_weight 2] [--filter_method normal|dynamic] [--conf 0,0,0] [--thres_disp 1.0] [--thres_view 3]
-        [--dyn_dist_base 0.25] [--dyn_rel_base 0.000769] [--dyn_views 2,10]
+        [--mesh_min_weight 2] [--mesh_min_component N] [--mesh_keep_largest K] [--filter_method normal|dynamic] [--conf 0,0,0]
+        [--thres_disp 1.0] [--thres_view 3] [--dyn_dist_base 0.25] [--dyn_rel_base 0.000769] [--dyn_views 2,10]
 
 fuses the saved depth maps of ``<out>/<scan>/`` as ``python -m cds_mvsnet_amd.fusion`` does and writes
 ``<out>/<scan>_mesh.ply``.  ``infer ... --fuse --mesh_voxel SIZE`` writes cloud and mesh from one fusion pass.
+
+``--mesh_min_component N`` / ``--mesh_keep_largest K`` drop the small connected components of the mesh before it is written
+(the kernels of ``csrc/mesh_clean.hip``: a union-find over the vertices, face counts per component, compaction).
+
+    python -m cds_mvsnet_amd.mesh --from_mesh "<out>/{scan}_mesh.ply" --mesh_min_component N [--mesh_keep_largest K]
+        --outdir <out> --testlist <list>
+
+cleans saved meshes in place, without the fusion.
 """
 from __future__ import annotations
 
@@ -32,6 +40,7 @@ Tensor = torch.Tensor
 MAX_CELLS = 1 << 26            # cells of the dense block table (CDS_TSDF_MAX_CELLS): 256 MiB of int32
 MAX_CHUNK = 32                 # views per launch the kernel takes (CDS_TSDF_MAX_CHUNK)
 CHUNK_VIEWS = 32               # views per launch of TsdfVolume.integrate (profiles/tsdf_mesh.md: 3.5 x faster than 1)
+MAX_ROUNDS = 64                # hook passes of the component labelling before it gives up (CDS_MESH_CC_MAX_ROUNDS)
 
 
 def check_voxel(voxel, trunc=None, what: str = "mesh"):
@@ -207,8 +216,140 @@ class TsdfVolume:
         return out
 
 
+# -------------------------------------------------------------------------------------------------------------- components
+def _check_faces(faces, n_vertices, what: str) -> int:
+    """The checks of a face list, in the order of render_mesh: layout (ValueError), device (RuntimeError), index range (ValueError)."""
+    if not isinstance(faces, torch.Tensor) or faces.dim() != 2 or faces.shape[1] != 3 or faces.dtype != torch.int32:
+        raise ValueError(f"{what}: faces must be an int32 [F,3] tensor, got {getattr(faces, 'dtype', type(faces))} "
+                         f"{tuple(getattr(faces, 'shape', ()))}")
+    nv = int(n_vertices)
+    if not (0 <= nv < 2 ** 31):
+        raise ValueError(f"{what}: {n_vertices} vertices, 0 .. 2^31 - 1 expected")
+    if not faces.is_cuda:
+        raise RuntimeError(f"{what}: faces must be a ROCm (cuda) tensor; there is no CPU fallback")
+    if faces.shape[0]:
+        lo, hi = (int(x) for x in torch.aminmax(faces))
+        if lo < 0 or hi >= nv:
+            raise ValueError(f"{what}: faces index outside the {nv} vertices ({lo}..{hi})")
+    return nv
+
+
+def _labels(faces: Tensor, nv: int):
+    """Rules 1-3 of DESIGN §1.11 for a checked, contiguous face list with nv > 0 -> (label int32 [nv], count int32 [nv], rounds)."""
+    dev, nf = faces.device, int(faces.shape[0])
+    if nf == 0:
+        return torch.arange(nv, dtype=torch.int32, device=dev), torch.zeros(nv, dtype=torch.int32, device=dev), 0
+    lib = _lib.load()
+    parent = torch.empty(nv, dtype=torch.int32, device=dev)
+    count = torch.zeros(nv, dtype=torch.int32, device=dev)
+    changed = torch.zeros(MAX_ROUNDS, dtype=torch.int32, device=dev)       # one word per round, zeroed once
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        check(lib.cds_mesh_cc_init(parent.data_ptr(), nv, stream), "cds_mesh_cc_init")
+        rounds = 0
+        while True:
+            if rounds == MAX_ROUNDS:
+                raise RuntimeError(f"mesh_components: the labels of {nv} vertices and {nf} faces did not settle in {MAX_ROUNDS} rounds")
+            check(lib.cds_mesh_cc_hook(faces.data_ptr(), nf, nv, parent.data_ptr(), changed.data_ptr() + 4 * rounds, stream),
+                  "cds_mesh_cc_hook")
+            check(lib.cds_mesh_cc_jump(parent.data_ptr(), nv, stream), "cds_mesh_cc_jump")
+            rounds += 1
+            if int(changed[rounds - 1]) == 0:                               # the one word read per round
+                break
+        check(lib.cds_mesh_cc_count(faces.data_ptr(), nf, nv, parent.data_ptr(), count.data_ptr(), stream), "cds_mesh_cc_count")
+    return parent, count, rounds
+
+
+def mesh_components(faces: Tensor, n_vertices: int) -> Dict[str, object]:
+    """The connected components of a mesh (DESIGN §1.11 rules 1-3): faces int32 [F,3] on a ROCm device, every index in
+    [0, n_vertices) -> {"label" int32 [V]: the smallest vertex of each vertex's component, "components" int32 [C]: the labels,
+    ascending, "faces" int64 [C]: the faces of each (a face counts for its first vertex), "rounds": hook passes made}, on that
+    device.  Two vertices are connected when a face holds both; a vertex in no face is a component with 0 faces."""
+    nv = _check_faces(faces, n_vertices, "mesh_components")
+    dev = faces.device
+    if nv == 0:
+        return {"label": torch.zeros(0, dtype=torch.int32, device=dev), "components": torch.zeros(0, dtype=torch.int32, device=dev),
+                "faces": torch.zeros(0, dtype=torch.int64, device=dev), "rounds": 0}
+    label, count, rounds = _labels(faces.contiguous(), nv)
+    comps = torch.nonzero(label == torch.arange(nv, dtype=torch.int32, device=dev)).reshape(-1)
+    return {"label": label, "components": comps.to(torch.int32), "faces": count[comps].to(torch.int64), "rounds": rounds}
+
+
+def select_components(counts: Tensor, min_faces: int = 0, keep_largest: int = 0) -> Tensor:
+    """Rule 4 of DESIGN §1.11: counts [C] in ascending label order -> bool [C].  A component is kept iff count >= min_faces and,
+    with K = keep_largest > 0, it is among the first K by (count descending, label ascending) of all components."""
+    keep = counts >= int(min_faces)
+    if int(keep_largest) > 0:
+        order = torch.sort(-counts.to(torch.int64), stable=True).indices   # stable: equal counts stay in label order
+        first = torch.zeros_like(keep)
+        first[order[:int(keep_largest)]] = True
+        keep = keep & first
+    return keep
+
+
+def clean_mesh(mesh_dict: Dict[str, Tensor], min_faces: int = 0, keep_largest: int = 0):
+    """Drop the small connected components of a mesh: ``mesh_dict`` as :meth:`TsdfVolume.extract` returns it
+    (vertices float32 [V,3], colors uint8 [V,3], faces int32 [F,3], on one ROCm device).  A component is kept iff it has at least
+    ``min_faces`` faces and, with ``keep_largest = K > 0``, is one of the K largest (ties: the lower label).  -> (mesh dict of
+    the kept faces and the vertices they hold, both in their order, the rows copied bit for bit; info: {"components",
+    "vertices", "faces": (before, after), "largest": faces of the largest component, "rounds"}).  "components" counts every
+    component before, isolated vertices included, and the kept ones that hold a face after."""
+    what = "clean_mesh"
+    min_faces, keep_largest = int(min_faces), int(keep_largest)
+    if min_faces < 0 or keep_largest < 0:
+        raise ValueError(f"{what}: min_faces and keep_largest must be >= 0, got {min_faces} and {keep_largest}")
+    vert, col, faces = mesh_dict["vertices"], mesh_dict["colors"], mesh_dict["faces"]
+    if not isinstance(vert, torch.Tensor) or vert.dim() != 2 or vert.shape[1] != 3 or vert.dtype != torch.float32:
+        raise ValueError(f"{what}: vertices must be a float32 [V,3] tensor, got {getattr(vert, 'dtype', type(vert))} "
+                         f"{tuple(getattr(vert, 'shape', ()))}")
+    nv = int(vert.shape[0])
+    if not isinstance(col, torch.Tensor) or tuple(col.shape) != (nv, 3) or col.dtype != torch.uint8:
+        raise ValueError(f"{what}: colors must be a uint8 [{nv},3] tensor, got {getattr(col, 'dtype', type(col))} "
+                         f"{tuple(getattr(col, 'shape', ()))}")
+    if not vert.is_cuda:
+        raise RuntimeError(f"{what}: vertices must be a ROCm (cuda) tensor; there is no CPU fallback")
+    _check_faces(faces, nv, what)
+    dev = vert.device
+    if col.device != dev or faces.device != dev:
+        raise RuntimeError(f"{what}: colors and faces must be on {dev}; there is no CPU fallback")
+    nf = int(faces.shape[0])
+    empty = {"vertices": torch.zeros((0, 3), dtype=torch.float32, device=dev),
+             "colors": torch.zeros((0, 3), dtype=torch.uint8, device=dev), "faces": torch.zeros((0, 3), dtype=torch.int32, device=dev)}
+    if nv == 0 or nf == 0:                                                   # no face: no vertex is in a kept face
+        return empty, {"components": (nv, 0), "vertices": (nv, 0), "faces": (0, 0), "largest": 0, "rounds": 0}
+    vert, col, faces = vert.contiguous(), col.contiguous(), faces.contiguous()
+    label, count, rounds = _labels(faces, nv)
+    comps = torch.nonzero(label == torch.arange(nv, dtype=torch.int32, device=dev)).reshape(-1)
+    counts = count[comps]
+    kept = select_components(counts, min_faces, keep_largest)
+    keep = torch.zeros(nv, dtype=torch.uint8, device=dev)
+    keep[comps] = kept.to(torch.uint8)
+    fkeep = torch.empty(nf, dtype=torch.uint8, device=dev)
+    vkeep = torch.zeros(nv, dtype=torch.uint8, device=dev)
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        check(lib.cds_mesh_cc_mark(faces.data_ptr(), nf, nv, label.data_ptr(), keep.data_ptr(), fkeep.data_ptr(), vkeep.data_ptr(),
+                                   stream), "cds_mesh_cc_mark")
+        vend, fend = torch.cumsum(vkeep, 0, dtype=torch.int64), torch.cumsum(fkeep, 0, dtype=torch.int64)
+        nv_out, nf_out, n_comp, largest = (int(x) for x in torch.stack(
+            [vend[-1], fend[-1], (kept & (counts > 0)).sum(), counts.max()]).cpu())
+        info = {"components": (int(comps.numel()), n_comp), "vertices": (nv, nv_out), "faces": (nf, nf_out), "largest": largest,
+                "rounds": rounds}
+        if nv_out == 0:
+            return empty, info
+        vnew, fnew = (vend - vkeep).to(torch.int32), (fend - fkeep).to(torch.int32)
+        out = {"vertices": torch.empty((nv_out, 3), dtype=torch.float32, device=dev),
+               "colors": torch.empty((nv_out, 3), dtype=torch.uint8, device=dev),
+               "faces": torch.empty((nf_out, 3), dtype=torch.int32, device=dev)}
+        check(lib.cds_mesh_cc_gather(vert.data_ptr(), col.data_ptr(), faces.data_ptr(), nv, nf, vkeep.data_ptr(), vnew.data_ptr(),
+                                     fkeep.data_ptr(), fnew.data_ptr(), nv_out, nf_out, out["vertices"].data_ptr(),
+                                     out["colors"].data_ptr(), out["faces"].data_ptr(), stream), "cds_mesh_cc_gather")
+    return out, info
+
+
 # --------------------------------------------------------------------------------------------------------------------- PLY
-_VERTEX = [("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1")]
+_VERTEX =[("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1")]
 _FACE = [("k", "u1"), ("v", "<i4", (3,))]
 _HEADER = ("ply\nformat binary_little_endian 1.0\nelement vertex {}\nproperty float x\nproperty float y\nproperty float z\n"
            "property uchar red\nproperty uchar green\nproperty uchar blue\nelement face {}\n"
@@ -282,45 +423,86 @@ def mesh_views(views: Sequence[dict], voxel: float, trunc: Optional[float] = Non
 
 
 def mesh_scan(pair_folder: str, scan_folder: str, plyfilename: str, voxel: float, trunc: Optional[float] = None, min_weight: int = 2,
-              method: str = "normal", cloud_ply: Optional[str] = None, device: str = "cuda", **fusion_options) -> Dict[str, object]:
+              method: str = "normal", cloud_ply: Optional[str] = None, device: str = "cuda", min_component: int = 0,
+              keep_largest: int = 0, **fusion_options) -> Dict[str, object]:
     """One scan from saved depth maps to a mesh at ``plyfilename``: the fusion pass of :func:`fusion.filter_depth` (``method``
     "normal" or "dynamic" and its ``fusion_options``), then allocation from every view's kept points, integration of the fused
     depth maps in ``pair.txt`` order and extraction.  ``cloud_ply``: also write the fused cloud there, from the same pass and byte
-    for byte what ``filter_depth`` writes alone.  -> {"vertices", "faces", "blocks": counts, "cloud": filter_depth's result,
-    "mesh": the mesh dict of :meth:`TsdfVolume.extract`, still on the device (render.render_scan takes it)}."""
+    for byte what ``filter_depth`` writes alone.  ``min_component`` / ``keep_largest``: when either is > 0 the mesh goes through
+    :func:`clean_mesh` before it is written; at 0 nothing of that runs.  -> {"vertices", "faces", "blocks": counts,
+    "cloud": filter_depth's result, "mesh": the mesh dict written, still on the device (render.render_scan takes it)[, "clean":
+    clean_mesh's info]}."""
     from .fusion import filter_depth
     if method == "gipuma":
         raise ValueError("mesh_scan: gipuma fusion is not supported (its fused point has no single depth map); use normal or dynamic")
     voxel, trunc = check_voxel(voxel, trunc, "mesh_scan")
     if int(min_weight) < 1:
         raise ValueError(f"mesh_scan: min_weight must be >= 1, got {min_weight}")
+    if int(min_component) < 0 or int(keep_largest) < 0:
+        raise ValueError(f"mesh_scan: min_component and keep_largest must be >= 0, got {min_component} and {keep_largest}")
     views: list = []
     cloud = filter_depth(pair_folder, scan_folder, cloud_ply, device=device, method=method, collect=views, **fusion_options)
     mesh, vol = mesh_views(views, voxel, trunc, min_weight, device)
+    cleaned = None
+    if int(min_component) > 0 or int(keep_largest) > 0:
+        mesh, cleaned = clean_mesh(mesh, min_component, keep_largest)
     write_mesh_ply(plyfilename, mesh["vertices"].cpu().numpy(), mesh["colors"].cpu().numpy(), mesh["faces"].cpu().numpy())
-    return {"vertices": int(mesh["vertices"].shape[0]), "faces": int(mesh["faces"].shape[0]), "blocks": vol.n_blocks, "cloud": cloud,
-            "mesh": mesh}
+    out = {"vertices": int(mesh["vertices"].shape[0]), "faces": int(mesh["faces"].shape[0]), "blocks": vol.n_blocks, "cloud": cloud,
+           "mesh": mesh}
+    if cleaned is not None:
+        out["clean"] = cleaned
+    return out
+
+
+def clean_file(src_ply: str, dst_ply: str, min_component: int = 0, keep_largest: int = 0, device: str = "cuda") -> Dict[str, object]:
+    """A saved mesh through :func:`clean_mesh` and back into a file (``dst_ply`` may be ``src_ply``): what one runs while tuning
+    the threshold, without the fusion.  -> {"vertices", "faces", "mesh", "clean"} as :func:`mesh_scan`."""
+    dev = torch.device(device)
+    v, c, f = (torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in read_mesh_ply(src_ply))
+    mesh, cleaned = clean_mesh({"vertices": v, "colors": c, "faces": f}, min_component, keep_largest)
+    write_mesh_ply(dst_ply, mesh["vertices"].cpu().numpy(), mesh["colors"].cpu().numpy(), mesh["faces"].cpu().numpy())
+    return {"vertices": int(mesh["vertices"].shape[0]), "faces": int(mesh["faces"].shape[0]), "mesh": mesh, "clean": cleaned}
 
 
 def format_mesh(info: Dict[str, object]) -> str:
-    return f"{info['vertices']} vertices, {info['faces']} faces, {info['blocks']} blocks"
+    text = f"{info['vertices']} vertices, {info['faces']} faces"
+    if "blocks" in info:
+        text += f", {info['blocks']} blocks"
+    if "clean" in info:
+        c = info["clean"]
+        text += (f"; removed {c['components'][0] - c['components'][1]} of {c['components'][0]} components and "
+                 f"{c['faces'][0] - c['faces'][1]} of {c['faces'][0]} faces (the largest has {c['largest']})")
+    return text
 
 
 # ---------------------------------------------------------------------------------------------------------------------- CLI
 def add_mesh_args(ap: argparse.ArgumentParser, required: bool = False) -> None:
-    """The options of DESIGN §1.9, shared with ``infer --fuse``."""
+    """The options of DESIGN §1.9 and §1.11, shared with ``infer --fuse``."""
     ap.add_argument("--mesh_voxel", type=float, default=None, required=required, metavar="SIZE",
                     help="write <outdir>/<scan>_mesh.ply: a triangle mesh from a TSDF volume with this lattice spacing (world units)")
     ap.add_argument("--mesh_trunc", type=float, default=None, metavar="T",
                     help="--mesh_voxel: truncation distance, between 1 and 8 voxels (default 4 voxels)")
     ap.add_argument("--mesh_min_weight", type=int, default=2, metavar="N",
                     help="--mesh_voxel: views a lattice point needs before its cubes are meshed")
+    ap.add_argument("--mesh_min_component", type=int, default=0, metavar="N",
+                    help="--mesh_voxel: drop the connected components of the mesh with fewer than N faces (0: keep all)")
+    ap.add_argument("--mesh_keep_largest", type=int, default=0, metavar="K",
+                    help="--mesh_voxel: keep only the K components with the most faces (0: no limit)")
+
+
+def check_clean_args(ap: argparse.ArgumentParser, args, allowed: bool) -> None:
+    """ap.error for a negative clean-up option, or for one given where no mesh is made (``allowed`` false)."""
+    if args.mesh_min_component < 0 or args.mesh_keep_largest < 0:
+        ap.error(f"--mesh_min_component and --mesh_keep_largest must be >= 0, got {args.mesh_min_component} and "
+                 f"{args.mesh_keep_largest}")
+    if not allowed and (args.mesh_min_component or args.mesh_keep_largest):
+        ap.error("--mesh_min_component and --mesh_keep_largest clean the mesh of --mesh_voxel: give --mesh_voxel SIZE as well")
 
 
 def main(argv=None) -> Dict[str, Dict[str, object]]:
     from .fusion import DYN_DIST_BASE, DYN_REL_BASE, _floats
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--testpath", required=True, help="the scenes: <testpath>/<scan>/pair.txt")
+    ap.add_argument("--testpath", default=None, help="the scenes: <testpath>/<scan>/pair.txt (not needed with --from_mesh)")
     ap.add_argument("--outdir", required=True, help="the infer output folder: <outdir>/<scan>/{depth_est,confidence,cams,images}")
     ap.add_argument("--testlist", required=True, help="text file with one scan name per line")
     ap.add_argument("--filter_method", default="normal", choices=["normal", "dynamic", "gipuma"])
@@ -331,18 +513,33 @@ def main(argv=None) -> Dict[str, Dict[str, object]]:
     ap.add_argument("--dyn_rel_base", type=float, default=DYN_REL_BASE, help="dynamic: relative depth difference per level")
     ap.add_argument("--dyn_views", default="2,10", help="dynamic: n_min,n_max")
     ap.add_argument("--device", default="cuda")
-    add_mesh_args(ap, required=True)
+    add_mesh_args(ap)
+    ap.add_argument("--from_mesh", default=None, metavar="FILE",
+                    help="instead of --mesh_voxel: clean this saved mesh ({scan} is replaced) with --mesh_min_component / "
+                         "--mesh_keep_largest and write <outdir>/<scan>_mesh.ply, without any fusion")
     args = ap.parse_args(argv)
+    if (args.mesh_voxel is None) == (args.from_mesh is None):
+        ap.error("give either --mesh_voxel SIZE (fuse and mesh) or --from_mesh FILE (clean a saved mesh)")
+    check_clean_args(ap, args, True)
+    if args.from_mesh is None and args.testpath is None:
+        ap.error("--testpath is required with --mesh_voxel")
     if args.filter_method == "gipuma":
         ap.error("--mesh_voxel is not implemented for --filter_method gipuma (its fused point has no single depth map); "
                  "use normal or dynamic")
     with open(args.testlist) as f:
         scans = [ln.strip() for ln in f if ln.strip()]
     out = {}
+    if args.from_mesh is not None:
+        for scan in scans:
+            out[scan] = clean_file(args.from_mesh.format(scan=scan), os.path.join(args.outdir, f"{scan}_mesh.ply"),
+                                   args.mesh_min_component, args.mesh_keep_largest, device=args.device)
+            print(f"{scan}_mesh.ply: {format_mesh(out[scan])}", flush=True)
+        return out
     for scan in scans:
         info = mesh_scan(os.path.join(args.testpath, scan), os.path.join(args.outdir, scan),
                          os.path.join(args.outdir, f"{scan}_mesh.ply"), args.mesh_voxel, args.mesh_trunc, args.mesh_min_weight,
-                         method=args.filter_method, device=args.device, conf=_floats(args.conf, 3, "--conf"),
+                         method=args.filter_method, device=args.device, min_component=args.mesh_min_component,
+                         keep_largest=args.mesh_keep_largest, conf=_floats(args.conf, 3, "--conf"),
                          thres_disp=args.thres_disp, thres_view=args.thres_view, dist_base=args.dyn_dist_base,
                          rel_base=args.dyn_rel_base, n_views=tuple(int(v) for v in _floats(args.dyn_views, 2, "--dyn_views")))
         out[scan] = info

@@ -727,6 +727,52 @@ int cds_raster_resolve(const unsigned long long* keys, const int* faces, long lo
                        int* face, unsigned char* front, unsigned char* valid, unsigned char* image, void* stream);
 
 /*
+ * Connected components of a triangle mesh and the removal of the small ones (csrc/mesh_clean.hip).
+ *
+ * Inputs.  faces int32 [n_faces][3] over n_vertices vertices, every index in [0, n_vertices) (the host refuses another mesh; a
+ *   kernel skips such a face and reads nothing there).  Everything below is integer arithmetic; nothing depends on any order.
+ * 1. Connectivity.  Two vertices are connected when some face holds both; a component is a class of the transitive closure.
+ *      Two sheets that share a single vertex are one component (vertex, not edge, adjacency).  A face with a repeated index
+ *      (a, a, b) still connects a and b.  A duplicate face is a face like any other.
+ * 2. Label.  label[v] = the smallest vertex index of v's component.  A vertex in no face is a component of its own, with 0 faces.
+ * 3. Size.  A face belongs to the component of its first vertex; count[c] = the number of faces of the component with label c.
+ *      Nothing else measures a component (no area: no floating-point sum enters a decision).
+ * 4. Selection, with min_faces >= 0 and keep_largest >= 0.  A component is kept iff count >= min_faces and, when
+ *      K = keep_largest > 0, it is among the first K components in the order (count descending, label ascending) of ALL
+ *      components.  keep_largest = 0 sets no limit.
+ * 5. Output.  The kept faces (those of kept components) in their order; the vertices that some kept face holds, in their order,
+ *      numbered 0, 1, ...; the rows of vertices and colors copied bit for bit; the faces rewritten to the new numbers.  A vertex in
+ *      no kept face is dropped.  With min_faces <= 1 and keep_largest = 0 a mesh whose every vertex lies in a face comes back as
+ *      it was.
+ *
+ * The labels come from a union-find over parent int32 [n_vertices] with parent[x] <= x at all times:
+ * cds_mesh_cc_init: parent[v] = v.
+ * cds_mesh_cc_hook: one pass over the faces: the roots of a face's vertices, the larger ones lowered to the smallest by atomicMin;
+ *   *changed (a device word the caller zeroed) is set to 1 when the pass lowered any word.
+ * cds_mesh_cc_jump: parent[v] = the root above v.  The caller repeats hook and jump until a hook leaves *changed at 0, at most
+ *   CDS_MESH_CC_MAX_ROUNDS times; then parent is the label of rule 2.  A caller that reaches the limit must report an error and
+ *   must not use parent.
+ * cds_mesh_cc_count: count [n_vertices] int32, zeroed by the caller: rule 3 (count[c] for c a label, 0 elsewhere).
+ * cds_mesh_cc_mark: keep [n_vertices] uint8 indexed by label (rule 4, made by the caller); face_keep [n_faces] uint8 is written
+ *   for every face; vertex_keep [n_vertices] uint8, zeroed by the caller, is set to 1 for the vertices of kept faces.
+ * cds_mesh_cc_gather: rule 5.  vertex_new / face_new: the exclusive prefix sums of vertex_keep / face_keep, int32; out_vertices /
+ *   out_faces their totals; colors and colors_out may both be null.
+ *   CDS_EINVAL: n_vertices or n_faces < 0 or >= 2^31; a total larger than its input; a null required pointer (an empty input or
+ *   output returns 0 first).
+ */
+#define CDS_MESH_CC_MAX_ROUNDS 64
+int cds_mesh_cc_init(int* parent, long long n_vertices, void* stream);
+int cds_mesh_cc_hook(const int* faces, long long n_faces, long long n_vertices, int* parent, int* changed, void* stream);
+int cds_mesh_cc_jump(int* parent, long long n_vertices, void* stream);
+int cds_mesh_cc_count(const int* faces, long long n_faces, long long n_vertices, const int* label, int* count, void* stream);
+int cds_mesh_cc_mark(const int* faces, long long n_faces, long long n_vertices, const int* label, const unsigned char* keep,
+                     unsigned char* face_keep, unsigned char* vertex_keep, void* stream);
+int cds_mesh_cc_gather(const float* vertices, const unsigned char* colors, const int* faces, long long n_vertices,
+                       long long n_faces, const unsigned char* vertex_keep, const int* vertex_new, const unsigned char* face_keep,
+                       const int* face_new, long long out_vertices, long long out_faces, float* vertices_out,
+                       unsigned char* colors_out, int* faces_out, void* stream);
+
+/*
  * Norm-curvature bookkeeping of one FeatureNet level (module.py:250-251,257-258,264-265) in one launch:
  *   nc_sum[i] = (a[i]^2 + b[i]^2 + c[i]^2) / 3,  nc_abs[i] = |c[i]|   for the three DynamicConv curvature maps of the level
  */

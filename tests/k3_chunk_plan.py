@@ -168,12 +168,14 @@ def k3_launch_views(views, split_env=None):
 A_DEPTHS = (96, 97, 120, 145, 192, 194)
 B_DEPTH = 145
 N_SRC = 7            # source views every input provides (K3 takes up to 7 in two launches)
+W_SHAPE = (3, 40, 40, 130)     # input W: V, D, h, w
 
 
 def local_permutation(hyp, group, seed):
     """hyp [1, D, h, w] with every run of `group` consecutive planes shuffled independently per pixel: non-monotone hypotheses whose
-    range over a chunk stays that of the ordered ones (a full permutation makes every chunk's range the whole sweep: all fallback,
-    which test_warp_lds_fallbacks_wild_geometry already covers)."""
+    range over a chunk stays that of the ordered ones (a full permutation makes every chunk's range the whole sweep: all fallback.
+    That case is input "W" below, run by test_k3_k1_wild_geometry_w_vs_oracle; test_warp_lds_fallbacks_wild_geometry of
+    test_hip_parity.py does NOT cover it: every sample of its input lies outside every source image, so it compares zeros)."""
     g = torch.Generator().manual_seed(seed)
     D = hyp.shape[1]
     key = (torch.arange(D) // group).view(1, D, 1, 1).float() + 0.999 * torch.rand(hyp.shape, generator=g)
@@ -184,8 +186,18 @@ def named_input(name, D=B_DEPTH):
     """(cams [1, 8, 2, 4, 4], hyp [1, D, h, w]) of an input family.
     A / A2: friendly geometry (no chunk is ever halved), a long march; A2's width and height are no tile multiples.
     B: halving geometry (wider baseline, near depths); Bperm: B with locally permuted hypotheses.
-    cfg4 / cfg4near: stage 1 of BASELINE config 4 (480x264, D = 48), default and near hypothesis range."""
+    cfg4 / cfg4near: stage 1 of BASELINE config 4 (480x264, D = 48), default and near hypothesis range.
+    W: wild geometry whose samples still hit the source images (cams [1, 4, 2, 4, 4], 40x130, D = 40): a wide baseline, hypotheses
+    drawn independently per pixel and plane (every chunk spans the whole sweep: nearly all of K3's / K1's chunks take the global-memory
+    path, and most workgroups of the K3 backward overflow their LDS box), and a third view whose z = 0 plane cuts the sweep."""
     from cds_mvsnet_amd import synth
+    if name == "W":
+        assert D == W_SHAPE[1]
+        V, _, h, w = W_SHAPE
+        cams = synth.make_cameras(V + 1, h, w, refine=False, seed=91, baseline=(150., 60., 15.))["stage3"]
+        cams[0, 3, 0, :3, 3] += torch.tensor([0., 0., -600.])      # view 3: its z = 0 plane cuts the sweep (pz < 0 for about half of its samples)
+        hyp = 300. + 600. * torch.rand(1, D, h, w, generator=torch.Generator().manual_seed(91))   # unordered per pixel
+        return cams, hyp
     if name in ("A", "A2"):
         h, w = (24, 136) if name == "A" else (21, 77)
         return synth.stage_cameras(N_SRC + 1, h, w, seed=52), synth.make_hypotheses(D, h, w, seed=53)
@@ -200,6 +212,31 @@ def named_input(name, D=B_DEPTH):
         assert D == 48
         return synth.stage_cameras(7, h, w, seed=62), synth.make_hypotheses(D, h, w, lo=425. if name == "cfg4" else 300., seed=63)
     raise KeyError(name)
+
+
+def w_features(C):
+    """The feature pairs of input W at C channels (synth.make_pair_features layout, one pair per source view)."""
+    from cds_mvsnet_amd import synth
+    V, _, h, w = W_SHAPE
+    return synth.make_pair_features(V, C, h, w, seed=91, sharp=True)
+
+
+def assert_wild_input(name="W"):
+    """The preconditions of the wild-geometry forward tests, as properties of the input: at least 90 % of K3's chunks and 60 % of K1's
+    (C = 8) on the global-memory path, and the samples still inside the source images: all four taps for at least half of the samples
+    of views 1 and 2 and for 5 % of the pole view's."""
+    V, D = W_SHAPE[:2]
+    cams, hyp = named_input(name, D)
+    k = k3_constants()
+    for views in ((1, 2, 3), (1, 2)):
+        p = named_plan(name, D, views, k["dc"], k["cap"])
+        assert p.fallback >= 0.9 * p.total, (name, views, p[:5])
+    k = k1_constants(8)
+    p = merge([named_plan(name, D, [v], k["dc"], k["cap"]) for v in range(1, V + 1)])
+    assert p.fallback >= 0.6 * p.total, (name, "K1", p[:5])
+    frac = [in_image_fraction(cams, hyp, v) for v in range(1, V + 1)]
+    assert frac[0] >= 0.5 and frac[1] >= 0.5 and frac[2] >= 0.05, frac
+    return frac
 
 
 def in_image_fraction(cams, hyp, view):

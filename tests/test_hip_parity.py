@@ -605,7 +605,9 @@ def test_batch_of_two_equals_two_singles(dev, seeded_state):
 @pytest.mark.parametrize("V,C,D,h,w", [(2, 8, 6, 12, 40), (3, 16, 4, 9, 70), (1, 32, 3, 8, 20), (2, 8, 40, 24, 130), (4, 16, 20, 33, 65)])
 def test_warp_aggregate_backward_vs_autograd(V, C, D, h, w, dev, ops):
     """Training step: gradients of the un-normalised warp-aggregate w.r.t. ref / src / vis against
-    torch autograd through the CPU oracle's warp (F.grid_sample)."""
+    torch autograd through the CPU oracle's warp (F.grid_sample).  An fp32 reference and a bound about 1000 x fp32 round-off: the
+    float64 bar, the paths these five shapes never reach (no box over 40 % of the LDS budget) and the direct kernel are in
+    tests/test_warp_bwd_gpu.py."""
     from oracle import cds_oracle as O
     feats, cams, hyp, _, _, mats, hyp_d = _random_stage(ops, dev, V, C, D, h, w, seed=60 + V)
     g = torch.Generator().manual_seed(5)
@@ -761,7 +763,11 @@ def test_warp_lds_fallbacks_wild_geometry(exact, dev, ops):
     """Geometry that defeats the LDS fast path: a wide baseline and near depths give tens of pixels of parallax per plane
     (boxes over the LDS budget even after the chunk is halved to 8 planes -> global-memory path), randomly permuted
     (non-monotone) hypotheses, and a source camera whose principal plane cuts the depth range (projective pole: samples
-    jump across the image).  K1 / K3 must still agree with the CPU oracle."""
+    jump across the image).  K1 / K3 must still agree with the CPU oracle.
+    What this input really is: with this baseline and these depths NOT ONE sample of any view has a tap inside its source image
+    (tests/test_k3_chunk_plan_cpu.py proves it), so the expected volume is identically zero and the entropies are those of a uniform
+    distribution.  It is the test of "everything outside": the kernels must write exact zeros, whatever path a chunk takes.  The values
+    of the global-memory path are tested on input W by tests/test_k3_depth_march_gpu.py::test_k3_k1_wild_geometry_w_vs_oracle."""
     from oracle import cds_oracle as O
     from cds_mvsnet_amd import synth, geometry
     V, C, D, h, w = 3, 8, 40, 24, 136
@@ -788,6 +794,8 @@ def test_warp_lds_fallbacks_wild_geometry(exact, dev, ops):
     fin = torch.isfinite(want)
     assert fin.float().mean() > 0.99
     assert ((vol.cpu() - want).abs()[fin]).max() < 2e-5
+    assert torch.count_nonzero(want) == 0 and fin.all()                     # every sample is outside every source image
+    assert torch.equal(vol.cpu(), torch.zeros(C, D, h, w))
 
 
 @pytest.mark.parametrize("k,stride,cin,cout,H,W", [(3, 1, 8, 11, 37, 70), (1, 1, 24, 8, 20, 33), (5, 1, 16, 19, 18, 40), (3, 2, 16, 32, 21, 50),

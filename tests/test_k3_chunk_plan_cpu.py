@@ -176,6 +176,44 @@ def test_preconditions_of_the_gpu_cases():
     assert all(plan.in_image_fraction(cams, hyp, v) >= 0.60 for v in range(1, 8))
 
 
+def test_input_w_is_wild_and_hits_the_image():
+    """The preconditions of test_k3_k1_wild_geometry_w_vs_oracle, proven without a GPU: (nearly) all chunks on the global-memory path,
+    the samples still inside the source images, and an oracle volume with content."""
+    frac = plan.assert_wild_input()
+    assert 0.70 <= frac[0] <= 0.76 and 0.73 <= frac[1] <= 0.79 and 0.07 <= frac[2] <= 0.11, frac     # the figures the input was chosen by
+    k = plan.k3_constants()
+    D = plan.W_SHAPE[1]
+    p = plan.named_plan("W", D, (1, 2, 3), k["dc"], k["cap"])
+    assert p.fallback == p.total == 150
+    p = plan.named_plan("W", D, (1, 2), k["dc"], k["cap"])
+    assert p.fallback >= 0.9 * p.total and p.total >= 100
+    for C, share in ((8, 0.6), (16, 0.85)):
+        kk = plan.k1_constants(C)
+        p = plan.merge([plan.named_plan("W", D, [v], kk["dc"], kk["cap"]) for v in (1, 2, 3)])
+        assert p.fallback >= share * p.total, (C, p[:5])
+    cams, hyp = plan.named_input("W", D)
+    # unordered per pixel: about half of the neighbouring plane pairs descend
+    assert 0.4 < float((hyp[:, 1:] < hyp[:, :-1]).float().mean()) < 0.6
+    assert gpu_cases.w_oracle_content(8) >= 0.5
+    want, _ = gpu_cases._oracle_volume("W", D, 8, gpu_cases.W_VIEWS, normalize=False)
+    assert float(torch.isfinite(want).float().mean()) >= 0.99
+    assert all(torch.isfinite(gpu_cases._oracle_view("W", D, 8, v)[1]).float().mean() >= 0.99 for v in gpu_cases.W_VIEWS)
+
+
+def test_old_wild_input_has_no_sample_inside_any_image():
+    """What test_warp_lds_fallbacks_wild_geometry (test_hip_parity.py) really is: with its baseline and depths no sample of any view
+    has even one tap inside the source image, so its expected volume is identically zero."""
+    from cds_mvsnet_amd import synth
+    V, D, h, w = 3, 40, 24, 136
+    cams = synth.make_cameras(V + 1, h, w, refine=False, seed=91, baseline=(900.0, 300.0, 40.0))["stage3"]
+    cams[0, 3, 0, :3, 3] += torch.tensor([0.0, 0.0, -260.0])
+    hyp = 120.0 + 600.0 * torch.rand(1, D, h, w, generator=torch.Generator().manual_seed(91))
+    for v in range(1, V + 1):
+        assert plan.in_image_fraction(cams, hyp, v) == 0.0
+        cx, cy = plan.sample_cells(cams, hyp, v)          # a tap inside needs a cell in [-1, n - 1]
+        assert not bool(((cx >= -1) & (cx <= w - 1) & (cy >= -1) & (cy <= h - 1)).any())
+
+
 def test_config4_stage1_meets_halved_chunks():
     k = plan.k3_constants()
     for name in ("cfg4", "cfg4near"):

@@ -59,6 +59,8 @@ ORACLE_SECONDS = [0.0]
 
 def _features(name, C):
     from cds_mvsnet_amd import synth
+    if (name, C) not in _FEATS and name == "W":
+        _FEATS[(name, C)] = plan.w_features(C)
     if (name, C) not in _FEATS:
         cams, hyp = plan.named_input(name, plan.B_DEPTH if name.startswith("B") else 96)
         _, _, h, w = hyp.shape
@@ -242,6 +244,67 @@ def test_k1_multi_chunk_march_vs_oracle(name, D, views, C, exact, dev, ops):
     err = (ent - want).abs().max().item()
     print("entropy max-abs vs oracle", err)
     assert err < (5e-5 if exact else 2e-4)
+
+
+# ------------------------------------------------------------------------------------------------
+# 1b. wild geometry that hits the image: (nearly) every chunk on the global-memory path
+# ------------------------------------------------------------------------------------------------
+W_VIEWS = (1, 2, 3)
+W_D = plan.W_SHAPE[1]
+
+
+def w_oracle_content(C):
+    """Share of the entries of the oracle's un-normalised volume of input W (all three views) that are finite and above 1e-3 in
+    magnitude: the wild-geometry test compares content, not zeros."""
+    want, _ = _oracle_volume("W", W_D, C, W_VIEWS, normalize=False)
+    return float((torch.isfinite(want) & (want.abs() > 1e-3)).float().mean())
+
+
+def _max_err(got, want):
+    ok = torch.isfinite(want)
+    return (got - want).abs()[ok].max().item(), float(ok.float().mean())
+
+
+@pytest.mark.parametrize("C", [8, 16])
+def test_k3_k1_wild_geometry_w_vs_oracle(C, dev, ops):
+    """Input W: hypotheses drawn independently per pixel and plane, a wide baseline and a view whose z = 0 plane cuts the sweep, with the
+    samples still INSIDE the source images (test_warp_lds_fallbacks_wild_geometry of test_hip_parity.py has the same kind of geometry but
+    not one sample inside: it compares zeros).  Every chunk of K3 over three views, 94 % over two, 75 % / 92 % of K1's (C = 8 / 16) take the
+    global-memory path, so this is the test of the values that path produces.  Exact positions, all three views: un-normalised volume
+    2e-5 on the oracle's finite entries (at least 99 % of all), entropy 5e-5 where the oracle's is finite - the bounds of the older wild
+    test.  Fast positions, views 1 - 2 (the pole view's samples are a question of position sensitivity, not of the kernel): normalised
+    volume 5e-5, entropy 2e-4, the bounds of test_warp_kernels_vs_oracle_odd_shapes for fast positions at widths up to 130."""
+    frac = plan.assert_wild_input()
+    content = w_oracle_content(C)
+    print("in-image fractions", frac, "oracle entries finite and > 1e-3: %.3f" % content)
+    assert content >= 0.5
+    ref, src, vis, mats, hyp_d = _device_inputs("W", W_D, C, W_VIEWS, dev, ops)
+    # exact positions, all three views
+    want, _ = _oracle_volume("W", W_D, C, W_VIEWS, normalize=False)
+    out = torch.full((C, W_D) + tuple(ref.shape[2:]), float("nan"), device=dev)
+    vol, _ = ops.warp_aggregate(ref, src, vis, mats, hyp_d, normalize=False, volume=out, exact=True)
+    err, finite = _max_err(vol.cpu(), want)
+    print("exact: un-normalised volume max-abs vs oracle %.3g (oracle finite on %.4f)" % (err, finite))
+    assert finite >= 0.99
+    assert err < 2e-5
+    ent = ops.warp_entropy(ref, src, mats, hyp_d, exact=True).cpu()
+    for i, v in enumerate(W_VIEWS):
+        err, finite = _max_err(ent[i], _oracle_view("W", W_D, C, v)[1])
+        print("exact: entropy of view %d max-abs vs oracle %.3g (oracle finite on %.4f)" % (v, err, finite))
+        assert err < 5e-5
+    # fast positions, views 1 - 2, normalised
+    want, _ = _oracle_volume("W", W_D, C, W_VIEWS[:2], normalize=True)
+    out = torch.full((C, W_D) + tuple(ref.shape[2:]), float("nan"), device=dev)
+    vol, _ = ops.warp_aggregate(ref[:2], src[:2], vis[:2], mats[:2], hyp_d, normalize=True, volume=out, exact=False)
+    err, finite = _max_err(vol.cpu(), want)
+    print("fast: normalised volume of views 1 - 2 max-abs vs oracle %.3g (oracle finite on %.4f)" % (err, finite))
+    assert finite >= 0.99
+    assert err < 5e-5
+    ent = ops.warp_entropy(ref[:2], src[:2], mats[:2], hyp_d, exact=False).cpu()
+    for i, v in enumerate(W_VIEWS[:2]):
+        err, _ = _max_err(ent[i], _oracle_view("W", W_D, C, v)[1])
+        print("fast: entropy of view %d max-abs vs oracle %.3g" % (v, err))
+        assert err < 2e-4
 
 
 # ------------------------------------------------------------------------------------------------

@@ -160,6 +160,10 @@ SIGNATURES = {
     "cds_mesh_cc_count": [P, L, L, P, P, P],
     "cds_mesh_cc_mark": [P, L, L, P, P, P, P, P],
     "cds_mesh_cc_gather": [P, P, P, L, L, P, P, P, P, L, L, P, P, P, P],
+    "cds_mesh_simplify_faces": [P, L, L, P, L, P, P, P, P],
+    "cds_mesh_simplify_quadric_f32": [P, L, P, L, P, P, P, P, L, F, P, P, P],
+    "cds_mesh_simplify_mark": [P, P, L, L, P, P],
+    "cds_mesh_simplify_gather": [P, P, L, P, P, P, L, P, P, L, L, P, P, P, P],
     "cds_grid_hash_log2_slots": [L],
     "cds_grid_keys_f32": [P, L, P, P, P],
     "cds_grid_hash_build": [P, L, L, P, P, I, P],

@@ -8,8 +8,9 @@ of every cube: welded vertices, consistent winding, colours, a fixed order.  The
 the blocks out.  There is no CPU path.
 
     python -m cds_mvsnet_amd.mesh --testpath <scenes> --outdir <out> --testlist <list> --mesh_voxel SIZE [--mesh_trunc T]
-        [--mesh_min_weight 2] [--mesh_min_component N] [--mesh_keep_largest K] [--filter_method normal|dynamic] [--conf 0,0,0]
-        [--thres_disp 1.0] [--thres_view 3] [--dyn_dist_base 0.25] [--dyn_rel_base 0.000769] [--dyn_views 2,10]
+        [--mesh_min_weight 2] [--mesh_min_component N] [--mesh_keep_largest K] [--mesh_simplify CELL]
+        [--mesh_simplify_placement quadric|mean] [--filter_method normal|dynamic] [--conf 0,0,0] [--thres_disp 1.0]
+        [--thres_view 3] [--dyn_dist_base 0.25] [--dyn_rel_base 0.000769] [--dyn_views 2,10]
 
 fuses the saved depth maps of ``<out>/<scan>/`` as ``python -m cds_mvsnet_amd.fusion`` does and writes
 ``<out>/<scan>_mesh.ply``.  ``infer ... --fuse --mesh_voxel SIZE`` writes cloud and mesh from one fusion pass.
@@ -21,6 +22,11 @@ fuses the saved depth maps of ``<out>/<scan>/`` as ``python -m cds_mvsnet_amd.fu
         --outdir <out> --testlist <list>
 
 cleans saved meshes in place, without the fusion.
+
+``--mesh_simplify CELL`` simplifies the mesh before it is written, after the clean-up (the kernels of
+``csrc/mesh_simplify.hip``): the vertices of a cell of side CELL, the cells of ``--merge_voxel``, become one vertex at the
+regularised minimiser of its faces' quadric error (``--mesh_simplify_placement mean``: at their mean), and the faces that
+collapse or repeat are dropped.  ``--from_mesh FILE --mesh_simplify CELL`` does it to a saved mesh.
 """
 from __future__ import annotations
 
@@ -41,6 +47,8 @@ MAX_CELLS = 1 << 26            # cells of the dense block table (CDS_TSDF_MAX_CE
 MAX_CHUNK = 32                 # views per launch the kernel takes (CDS_TSDF_MAX_CHUNK)
 CHUNK_VIEWS = 32               # views per launch of TsdfVolume.integrate (profiles/tsdf_mesh.md: 3.5 x faster than 1)
 MAX_ROUNDS = 64                # hook passes of the component labelling before it gives up (CDS_MESH_CC_MAX_ROUNDS)
+PLACEMENTS = ("quadric", "mean")   # where simplify_mesh puts a cluster's vertex
+PACK_BITS = 21                 # three cluster numbers of at most this many bits make one sort key of a face's identity
 
 
 def check_voxel(voxel, trunc=None, what: str = "mesh"):
@@ -287,17 +295,9 @@ def select_components(counts: Tensor, min_faces: int = 0, keep_largest: int = 0)
     return keep
 
 
-def clean_mesh(mesh_dict: Dict[str, Tensor], min_faces: int = 0, keep_largest: int = 0):
-    """Drop the small connected components of a mesh (DESIGN §1.11): ``mesh_dict`` as :meth:`TsdfVolume.extract` returns it
-    (vertices float32 [V,3], colors uint8 [V,3], faces int32 [F,3], on one ROCm device).  A component is kept iff it has at least
-    ``min_faces`` faces and, with ``keep_largest = K > 0``, is one of the K largest (ties: the lower label).  -> (mesh dict of
-    the kept faces and the vertices they hold, both in their order, the rows copied bit for bit; info: {"components",
-    "vertices", "faces": (before, after), "largest": faces of the largest component, "rounds"}).  "components" counts every
-    component before, isolated vertices included, and the kept ones that hold a face after."""
-    what = "clean_mesh"
-    min_faces, keep_largest = int(min_faces), int(keep_largest)
-    if min_faces < 0 or keep_largest < 0:
-        raise ValueError(f"{what}: min_faces and keep_largest must be >= 0, got {min_faces} and {keep_largest}")
+def _check_mesh(mesh_dict, what: str):
+    """The checks of a mesh dict: layouts (ValueError), device (RuntimeError), index range (ValueError) -> (vertices, colors,
+    faces, V, device)."""
     vert, col, faces = mesh_dict["vertices"], mesh_dict["colors"], mesh_dict["faces"]
     if not isinstance(vert, torch.Tensor) or vert.dim() != 2 or vert.shape[1] != 3 or vert.dtype != torch.float32:
         raise ValueError(f"{what}: vertices must be a float32 [V,3] tensor, got {getattr(vert, 'dtype', type(vert))} "
@@ -312,6 +312,21 @@ def clean_mesh(mesh_dict: Dict[str, Tensor], min_faces: int = 0, keep_largest: i
     dev = vert.device
     if col.device != dev or faces.device != dev:
         raise RuntimeError(f"{what}: colors and faces must be on {dev}; there is no CPU fallback")
+    return vert, col, faces, nv, dev
+
+
+def clean_mesh(mesh_dict: Dict[str, Tensor], min_faces: int = 0, keep_largest: int = 0):
+    """Drop the small connected components of a mesh (DESIGN §1.11): ``mesh_dict`` as :meth:`TsdfVolume.extract` returns it
+    (vertices float32 [V,3], colors uint8 [V,3], faces int32 [F,3], on one ROCm device).  A component is kept iff it has at least
+    ``min_faces`` faces and, with ``keep_largest = K > 0``, is one of the K largest (ties: the lower label).  -> (mesh dict of
+    the kept faces and the vertices they hold, both in their order, the rows copied bit for bit; info: {"components",
+    "vertices", "faces": (before, after), "largest": faces of the largest component, "rounds"}).  "components" counts every
+    component before, isolated vertices included, and the kept ones that hold a face after."""
+    what = "clean_mesh"
+    min_faces, keep_largest = int(min_faces), int(keep_largest)
+    if min_faces < 0 or keep_largest < 0:
+        raise ValueError(f"{what}: min_faces and keep_largest must be >= 0, got {min_faces} and {keep_largest}")
+    vert, col, faces, nv, dev = _check_mesh(mesh_dict, what)
     nf = int(faces.shape[0])
     empty = {"vertices": torch.zeros((0, 3), dtype=torch.float32, device=dev),
              "colors": torch.zeros((0, 3), dtype=torch.uint8, device=dev), "faces": torch.zeros((0, 3), dtype=torch.int32, device=dev)}
@@ -345,6 +360,124 @@ def clean_mesh(mesh_dict: Dict[str, Tensor], min_faces: int = 0, keep_largest: i
         check(lib.cds_mesh_cc_gather(vert.data_ptr(), col.data_ptr(), faces.data_ptr(), nv, nf, vkeep.data_ptr(), vnew.data_ptr(),
                                      fkeep.data_ptr(), fnew.data_ptr(), nv_out, nf_out, out["vertices"].data_ptr(),
                                      out["colors"].data_ptr(), out["faces"].data_ptr(), stream), "cds_mesh_cc_gather")
+    return out, info
+
+
+# ---------------------------------------------------------------------------------------------------------- simplification
+def check_cell(cell, what: str = "simplify_mesh") -> float:
+    """-> cell as a float; ValueError unless it is finite and > 0."""
+    try:
+        size = float(cell)
+    except (TypeError, ValueError):
+        size = math.nan
+    if not (size > 0 and math.isfinite(size)):
+        raise ValueError(f"{what}: cell must be positive, got {cell}")
+    return size
+
+
+def _first_of_identity(ident: Tensor, n_clusters: int) -> Tensor:
+    """ident int64 [N,3] in ascending face order -> bool [N]: the row is the first with its triple (rule 5's lowest index).
+    Stable sorts keep equal triples in face order, so the first of a run is the lowest face: one sort of a packed key while a
+    cluster fits PACK_BITS bits, else one per column, last column first."""
+    n = int(ident.shape[0])
+    if int(n_clusters) <= 1 << PACK_BITS:
+        key = (ident[:, 0] << (2 * PACK_BITS)) | (ident[:, 1] << PACK_BITS) | ident[:, 2]
+        order = torch.sort(key, stable=True).indices
+        key = key[order]
+        new = key[1:] != key[:-1]
+    else:
+        order = torch.sort(ident[:, 2], stable=True).indices
+        order = order[torch.sort(ident[order, 1], stable=True).indices]
+        order = order[torch.sort(ident[order, 0], stable=True).indices]
+        rows = ident[order]
+        new = (rows[1:] != rows[:-1]).any(1)
+    first = torch.zeros(n, dtype=torch.bool, device=ident.device)
+    first[order[:1]] = True
+    first[order[1:][new]] = True
+    return first
+
+
+def _clusters(vert: Tensor, col: Tensor, faces: Tensor, cell: float, placement: str):
+    """Rules 1-4 and the face pass of rule 5 for checked, contiguous tensors with V > 0 and F > 0, on the current device
+    -> (C, positions float32 [C,3], packed colours int32 [C], fallback uint8 [C] or None for "mean", face clusters int32 [F,3],
+    collapsed uint8 [F], identities int32 [F,3])."""
+    from .pointcloud import pack_colors, voxel_groups
+    dev, nv, nf = vert.device, int(vert.shape[0]), int(faces.shape[0])
+    lib = _lib.load()
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    perm, start, ukeys, counts = voxel_groups(vert, cell, "simplify_mesh")   # ValueError for a vertex that is not finite
+    nc = int(ukeys.numel())
+    cluster = torch.empty(nv, dtype=torch.int32, device=dev)
+    cluster[perm] = torch.repeat_interleave(torch.arange(nc, dtype=torch.int32, device=dev), counts, output_size=nv)
+    mean = torch.empty((nc, 3), dtype=torch.float32, device=dev)
+    packed = torch.empty(nc, dtype=torch.int32, device=dev)
+    members = torch.empty(nc, dtype=torch.int32, device=dev)
+    check(lib.cds_voxel_merge_f32(vert.data_ptr(), pack_colors(col).data_ptr(), None, nv, perm.data_ptr(), start.data_ptr(), nc,
+                                  mean.data_ptr(), packed.data_ptr(), None, members.data_ptr(), stream), "cds_voxel_merge_f32")
+    fclus = torch.empty((nf, 3), dtype=torch.int32, device=dev)
+    ident = torch.empty((nf, 3), dtype=torch.int32, device=dev)
+    gone = torch.empty(nf, dtype=torch.uint8, device=dev)
+    check(lib.cds_mesh_simplify_faces(faces.data_ptr(), nf, nv, cluster.data_ptr(), nc, fclus.data_ptr(), gone.data_ptr(),
+                                      ident.data_ptr(), stream), "cds_mesh_simplify_faces")
+    if placement != "quadric":
+        return nc, mean, packed, None, fclus, gone, ident
+    owner, inc = torch.sort(fclus.reshape(-1), stable=True)                  # the corners 3 f + j of every cluster, ascending
+    inc_start = torch.searchsorted(owner, torch.arange(nc + 1, dtype=torch.int32, device=dev)).to(torch.int32)
+    pos = torch.empty((nc, 3), dtype=torch.float32, device=dev)
+    fell = torch.empty(nc, dtype=torch.uint8, device=dev)
+    check(lib.cds_mesh_simplify_quadric_f32(vert.data_ptr(), nv, faces.data_ptr(), nf, perm.data_ptr(), start.data_ptr(),
+                                            inc.data_ptr(), inc_start.data_ptr(), nc, cell, pos.data_ptr(), fell.data_ptr(),
+                                            stream), "cds_mesh_simplify_quadric_f32")
+    return nc, pos, packed, fell, fclus, gone, ident
+
+
+def simplify_mesh(mesh_dict: Dict[str, Tensor], cell: float, placement: str = "quadric"):
+    """Vertex clustering with quadric placement: ``mesh_dict`` as :meth:`TsdfVolume.extract` returns it (vertices
+    float32 [V,3], all finite, colors uint8 [V,3], faces int32 [F,3], on one ROCm device).  The vertices of a cell of side ``cell``
+    (world units; the cells of ``--merge_voxel``: :func:`pointcloud.voxel_groups`) become one vertex: at the regularised minimiser
+    of its faces' quadric error (``placement="quadric"``; it falls back to the mean where that is undetermined or leaves the
+    neighbourhood) or at their mean (``"mean"``, the bits of ``cds_voxel_merge_f32``), with the rounded mean colour.  Faces with two
+    corners in one cluster and repeats of an earlier face are dropped, as are clusters no surviving face holds.  -> (mesh dict: the
+    surviving faces in their order, the clusters they hold in ascending cell-key order; info: {"vertices", "faces": (before,
+    after), "clusters", "collapsed", "duplicates", "fallback": clusters, kept or not, that fell back (0 for "mean")})."""
+    what = "simplify_mesh"
+    cell = check_cell(cell, what)
+    if placement not in PLACEMENTS:
+        raise ValueError(f"{what}: placement must be one of {PLACEMENTS}, got {placement!r}")
+    vert, col, faces, nv, dev = _check_mesh(mesh_dict, what)
+    nf = int(faces.shape[0])
+    empty = {"vertices": torch.zeros((0, 3), dtype=torch.float32, device=dev),
+             "colors": torch.zeros((0, 3), dtype=torch.uint8, device=dev), "faces": torch.zeros((0, 3), dtype=torch.int32, device=dev)}
+    if nv == 0 or nf == 0:                                                   # no face: no cluster is in a surviving face
+        return empty, {"vertices": (nv, 0), "faces": (0, 0), "clusters": 0, "collapsed": 0, "duplicates": 0, "fallback": 0}
+    if 3 * nf >= 2 ** 31:
+        raise ValueError(f"{what}: {nf} faces, at most {(2 ** 31 - 1) // 3}")
+    vert, col, faces = vert.contiguous(), col.contiguous(), faces.contiguous()
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        nc, pos, packed, fell, fclus, gone, ident = _clusters(vert, col, faces, cell, placement)
+        n_fell = fell.sum() if fell is not None else torch.zeros((), dtype=torch.int64, device=dev)
+        alive = torch.nonzero(gone == 0).reshape(-1)
+        fkeep = torch.zeros(nf, dtype=torch.uint8, device=dev)
+        if alive.numel():
+            fkeep[alive[_first_of_identity(ident[alive].long(), nc)]] = 1
+        ckeep = torch.zeros(nc, dtype=torch.uint8, device=dev)
+        check(lib.cds_mesh_simplify_mark(fclus.data_ptr(), fkeep.data_ptr(), nf, nc, ckeep.data_ptr(), stream),
+              "cds_mesh_simplify_mark")
+        cend, fend = torch.cumsum(ckeep, 0, dtype=torch.int64), torch.cumsum(fkeep, 0, dtype=torch.int64)
+        nv_out, nf_out, n_gone, n_fell = (int(x) for x in torch.stack([cend[-1], fend[-1], gone.sum(), n_fell]).cpu())
+        info = {"vertices": (nv, nv_out), "faces": (nf, nf_out), "clusters": nc, "collapsed": n_gone,
+                "duplicates": nf - n_gone - nf_out, "fallback": n_fell}
+        if nv_out == 0:
+            return empty, info
+        cnew, fnew = (cend - ckeep).to(torch.int32), (fend - fkeep).to(torch.int32)
+        out = {"vertices": torch.empty((nv_out, 3), dtype=torch.float32, device=dev),
+               "colors": torch.empty((nv_out, 3), dtype=torch.uint8, device=dev),
+               "faces": torch.empty((nf_out, 3), dtype=torch.int32, device=dev)}
+        check(lib.cds_mesh_simplify_gather(pos.data_ptr(), packed.data_ptr(), nc, ckeep.data_ptr(), cnew.data_ptr(), fclus.data_ptr(),
+                                           nf, fkeep.data_ptr(), fnew.data_ptr(), nv_out, nf_out, out["vertices"].data_ptr(),
+                                           out["colors"].data_ptr(), out["faces"].data_ptr(), stream), "cds_mesh_simplify_gather")
     return out, info
 
 
@@ -422,16 +555,26 @@ def mesh_views(views: Sequence[dict], voxel: float, trunc: Optional[float] = Non
     return vol.extract(min_weight), vol
 
 
+def _check_simplify(simplify, placement, what: str) -> float:
+    """-> simplify as a float, 0.0 for "off"; ValueError for a negative or non-finite cell or an unknown placement."""
+    if placement not in PLACEMENTS:
+        raise ValueError(f"{what}: placement must be one of {PLACEMENTS}, got {placement!r}")
+    if simplify is None or simplify == 0:
+        return 0.0
+    return check_cell(simplify, what)
+
+
 def mesh_scan(pair_folder: str, scan_folder: str, plyfilename: str, voxel: float, trunc: Optional[float] = None, min_weight: int = 2,
               method: str = "normal", cloud_ply: Optional[str] = None, device: str = "cuda", min_component: int = 0,
-              keep_largest: int = 0, **fusion_options) -> Dict[str, object]:
+              keep_largest: int = 0, simplify: float = 0.0, placement: str = "quadric", **fusion_options) -> Dict[str, object]:
     """One scan from saved depth maps to a mesh at ``plyfilename``: the fusion pass of :func:`fusion.filter_depth` (``method``
     "normal" or "dynamic" and its ``fusion_options``), then allocation from every view's kept points, integration of the fused
     depth maps in ``pair.txt`` order and extraction.  ``cloud_ply``: also write the fused cloud there, from the same pass and byte
     for byte what ``filter_depth`` writes alone.  ``min_component`` / ``keep_largest``: when either is > 0 the mesh goes through
-    :func:`clean_mesh` before it is written; at 0 nothing of that runs.  -> {"vertices", "faces", "blocks": counts,
-    "cloud": filter_depth's result, "mesh": the mesh dict written, still on the device (render.render_scan takes it)[, "clean":
-    clean_mesh's info]}."""
+    :func:`clean_mesh` before it is written; at 0 nothing of that runs.  ``simplify``: a cell side > 0 sends the
+    mesh, after the clean-up, through :func:`simplify_mesh` with ``placement``; at 0 nothing of that runs.
+    -> {"vertices", "faces", "blocks": counts, "cloud": filter_depth's result, "mesh": the mesh dict written, still on the device
+    (render.render_scan takes it)[, "clean": clean_mesh's info][, "simplify": simplify_mesh's info]}."""
     from .fusion import filter_depth
     if method == "gipuma":
         raise ValueError("mesh_scan: gipuma fusion is not supported (its fused point has no single depth map); use normal or dynamic")
@@ -440,28 +583,41 @@ def mesh_scan(pair_folder: str, scan_folder: str, plyfilename: str, voxel: float
         raise ValueError(f"mesh_scan: min_weight must be >= 1, got {min_weight}")
     if int(min_component) < 0 or int(keep_largest) < 0:
         raise ValueError(f"mesh_scan: min_component and keep_largest must be >= 0, got {min_component} and {keep_largest}")
+    simplify = _check_simplify(simplify, placement, "mesh_scan")
     views: list = []
     cloud = filter_depth(pair_folder, scan_folder, cloud_ply, device=device, method=method, collect=views, **fusion_options)
     mesh, vol = mesh_views(views, voxel, trunc, min_weight, device)
-    cleaned = None
+    cleaned = simplified = None
     if int(min_component) > 0 or int(keep_largest) > 0:
         mesh, cleaned = clean_mesh(mesh, min_component, keep_largest)
+    if simplify > 0:
+        mesh, simplified = simplify_mesh(mesh, simplify, placement)
     write_mesh_ply(plyfilename, mesh["vertices"].cpu().numpy(), mesh["colors"].cpu().numpy(), mesh["faces"].cpu().numpy())
     out = {"vertices": int(mesh["vertices"].shape[0]), "faces": int(mesh["faces"].shape[0]), "blocks": vol.n_blocks, "cloud": cloud,
            "mesh": mesh}
     if cleaned is not None:
         out["clean"] = cleaned
+    if simplified is not None:
+        out["simplify"] = simplified
     return out
 
 
-def clean_file(src_ply: str, dst_ply: str, min_component: int = 0, keep_largest: int = 0, device: str = "cuda") -> Dict[str, object]:
-    """A saved mesh through :func:`clean_mesh` and back into a file (``dst_ply`` may be ``src_ply``): what one runs while tuning
-    the threshold, without the fusion.  -> {"vertices", "faces", "mesh", "clean"} as :func:`mesh_scan`."""
+def clean_file(src_ply: str, dst_ply: str, min_component: int = 0, keep_largest: int = 0, device: str = "cuda",
+               simplify: float = 0.0, placement: str = "quadric") -> Dict[str, object]:
+    """A saved mesh through :func:`clean_mesh`, then, with ``simplify`` > 0, through :func:`simplify_mesh`, and back into a file
+    (``dst_ply`` may be ``src_ply``): what one runs while tuning the threshold or the cell, without the fusion.  With ``simplify``
+    alone (both clean-up options at 0) the file goes through :func:`simplify_mesh` only, as in :func:`mesh_scan`.
+    -> {"vertices", "faces", "mesh"[, "clean"][, "simplify"]} as :func:`mesh_scan`."""
+    simplify = _check_simplify(simplify, placement, "clean_file")
     dev = torch.device(device)
     v, c, f = (torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in read_mesh_ply(src_ply))
-    mesh, cleaned = clean_mesh({"vertices": v, "colors": c, "faces": f}, min_component, keep_largest)
+    mesh, out = {"vertices": v, "colors": c, "faces": f}, {}
+    if simplify == 0 or int(min_component) > 0 or int(keep_largest) > 0:
+        mesh, out["clean"] = clean_mesh(mesh, min_component, keep_largest)
+    if simplify > 0:
+        mesh, out["simplify"] = simplify_mesh(mesh, simplify, placement)
     write_mesh_ply(dst_ply, mesh["vertices"].cpu().numpy(), mesh["colors"].cpu().numpy(), mesh["faces"].cpu().numpy())
-    return {"vertices": int(mesh["vertices"].shape[0]), "faces": int(mesh["faces"].shape[0]), "mesh": mesh, "clean": cleaned}
+    return dict(out, vertices=int(mesh["vertices"].shape[0]), faces=int(mesh["faces"].shape[0]), mesh=mesh)
 
 
 def format_mesh(info: Dict[str, object]) -> str:
@@ -472,12 +628,16 @@ def format_mesh(info: Dict[str, object]) -> str:
         c = info["clean"]
         text += (f"; removed {c['components'][0] - c['components'][1]} of {c['components'][0]} components and "
                  f"{c['faces'][0] - c['faces'][1]} of {c['faces'][0]} faces (the largest has {c['largest']})")
+    if "simplify" in info:
+        s = info["simplify"]
+        text += (f"; simplified {s['vertices'][0]} -> {s['vertices'][1]} vertices and {s['faces'][0]} -> {s['faces'][1]} faces "
+                 f"({s['clusters']} clusters, {s['collapsed']} faces collapsed, {s['duplicates']} duplicates, {s['fallback']} fallbacks)")
     return text
 
 
 # ---------------------------------------------------------------------------------------------------------------------- CLI
 def add_mesh_args(ap: argparse.ArgumentParser, required: bool = False) -> None:
-    """The options of DESIGN §1.9 and §1.11, shared with ``infer --fuse``."""
+    """The options of DESIGN §1.9, §1.11 and §1.12, shared with ``infer --fuse``."""
     ap.add_argument("--mesh_voxel", type=float, default=None, required=required, metavar="SIZE",
                     help="write <outdir>/<scan>_mesh.ply: a triangle mesh from a TSDF volume with this lattice spacing (world units)")
     ap.add_argument("--mesh_trunc", type=float, default=None, metavar="T",
@@ -488,15 +648,28 @@ def add_mesh_args(ap: argparse.ArgumentParser, required: bool = False) -> None:
                     help="--mesh_voxel: drop the connected components of the mesh with fewer than N faces (0: keep all)")
     ap.add_argument("--mesh_keep_largest", type=int, default=0, metavar="K",
                     help="--mesh_voxel: keep only the K components with the most faces (0: no limit)")
+    ap.add_argument("--mesh_simplify", type=float, default=None, metavar="CELL",
+                    help="--mesh_voxel: simplify the mesh before it is written: one vertex per cell of this side (world units, the "
+                         "cells of --merge_voxel), faces that collapse or repeat dropped")
+    ap.add_argument("--mesh_simplify_placement", default="quadric", choices=list(PLACEMENTS),
+                    help="--mesh_simplify: a cell's vertex at the minimiser of its faces' quadric error (edges and corners "
+                         "survive) or at the mean of its vertices")
 
 
 def check_clean_args(ap: argparse.ArgumentParser, args, allowed: bool) -> None:
-    """ap.error for a negative clean-up option, or for one given where no mesh is made (``allowed`` false)."""
+    """ap.error for a negative clean-up option or a non-positive --mesh_simplify, or for one given where no mesh is made
+    (``allowed`` false)."""
     if args.mesh_min_component < 0 or args.mesh_keep_largest < 0:
         ap.error(f"--mesh_min_component and --mesh_keep_largest must be >= 0, got {args.mesh_min_component} and "
                  f"{args.mesh_keep_largest}")
     if not allowed and (args.mesh_min_component or args.mesh_keep_largest):
         ap.error("--mesh_min_component and --mesh_keep_largest clean the mesh of --mesh_voxel: give --mesh_voxel SIZE as well")
+    if args.mesh_simplify is not None:
+        if not (args.mesh_simplify > 0 and math.isfinite(args.mesh_simplify)):
+            ap.error(f"--mesh_simplify must be positive, got {args.mesh_simplify}")
+        if not allowed:
+            ap.error("--mesh_simplify simplifies the mesh of --mesh_voxel: give --mesh_voxel SIZE (or, in mesh, --from_mesh FILE) "
+                     "as well")
 
 
 def main(argv=None) -> Dict[str, Dict[str, object]]:
@@ -516,7 +689,8 @@ def main(argv=None) -> Dict[str, Dict[str, object]]:
     add_mesh_args(ap)
     ap.add_argument("--from_mesh", default=None, metavar="FILE",
                     help="instead of --mesh_voxel: clean this saved mesh ({scan} is replaced) with --mesh_min_component / "
-                         "--mesh_keep_largest and write <outdir>/<scan>_mesh.ply, without any fusion")
+                         "--mesh_keep_largest, simplify it with --mesh_simplify, and write <outdir>/<scan>_mesh.ply, without any "
+                         "fusion")
     args = ap.parse_args(argv)
     if (args.mesh_voxel is None) == (args.from_mesh is None):
         ap.error("give either --mesh_voxel SIZE (fuse and mesh) or --from_mesh FILE (clean a saved mesh)")
@@ -532,14 +706,16 @@ def main(argv=None) -> Dict[str, Dict[str, object]]:
     if args.from_mesh is not None:
         for scan in scans:
             out[scan] = clean_file(args.from_mesh.format(scan=scan), os.path.join(args.outdir, f"{scan}_mesh.ply"),
-                                   args.mesh_min_component, args.mesh_keep_largest, device=args.device)
+                                   args.mesh_min_component, args.mesh_keep_largest, device=args.device,
+                                   simplify=args.mesh_simplify or 0.0, placement=args.mesh_simplify_placement)
             print(f"{scan}_mesh.ply: {format_mesh(out[scan])}", flush=True)
         return out
     for scan in scans:
         info = mesh_scan(os.path.join(args.testpath, scan), os.path.join(args.outdir, scan),
                          os.path.join(args.outdir, f"{scan}_mesh.ply"), args.mesh_voxel, args.mesh_trunc, args.mesh_min_weight,
                          method=args.filter_method, device=args.device, min_component=args.mesh_min_component,
-                         keep_largest=args.mesh_keep_largest, conf=_floats(args.conf, 3, "--conf"),
+                         keep_largest=args.mesh_keep_largest, simplify=args.mesh_simplify or 0.0,
+                         placement=args.mesh_simplify_placement, conf=_floats(args.conf, 3, "--conf"),
                          thres_disp=args.thres_disp, thres_view=args.thres_view, dist_base=args.dyn_dist_base,
                          rel_base=args.dyn_rel_base, n_views=tuple(int(v) for v in _floats(args.dyn_views, 2, "--dyn_views")))
         out[scan] = info

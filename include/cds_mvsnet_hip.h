@@ -773,6 +773,64 @@ int cds_mesh_cc_gather(const float* vertices, const unsigned char* colors, const
                        unsigned char* colors_out, int* faces_out, void* stream);
 
 /*
+ * Simplification of a triangle mesh: vertex clustering with quadric placement (csrc/mesh_simplify.hip).
+ *
+ * Inputs.  vertices float32 [V][3], all finite; colors uint8 [V][3]; faces int32 [F][3], every index in [0, V) (the host refuses
+ *   another mesh; a kernel skips such a face and reads nothing there); cell > 0, finite; placement "quadric" or "mean".
+ * 1. Cells.  The cells of cds_voxel_merge_f32 as pointcloud.voxel_groups(vertices, cell) lays them out: origin
+ *      float32(min - cell / 2), index floorf((p - o) / cell) in fp32, the grid's key packing.  Cluster c is the c-th occupied cell
+ *      in ascending key order; its members perm[start[c] .. start[c + 1]) are ascending vertex indices; k_c is their number.
+ * 2. Mean and colour.  S_c: the fp64 sum of the members' positions in member order; m_c = S_c / k_c in fp64.  The colour is
+ *      (2 sum + k) / (2 k) per channel in integers.  fp32(m_c) and the colour are what cds_voxel_merge_f32 returns; with
+ *      placement "mean" the position is fp32(m_c), that kernel's bits.
+ * 3. Quadric.  The incidences of cluster c are the pairs (f, j) with cluster(faces[f][j]) == c in ascending (f, j); a face with
+ *      two corners in c appears twice.  Per face, with p_i = (double)vertices[faces[f][i]]: e1 = p1 - p0, e2 = p2 - p0,
+ *      n = (e1y e2z - e1z e2y, e1z e2x - e1x e2z, e1x e2y - e1y e2x), w2 = (nx nx + ny ny) + nz nz; a face whose w2 is zero or
+ *      not finite contributes nothing.  Per incidence: q = p0 - m_c, d = (nx qx + ny qy) + nz qz; A00 += nx nx, A01 += nx ny,
+ *      A02 += nx nz, A11 += ny ny, A12 += ny nz, A22 += nz nz, b += n d per component; nine sequential fp64 sums in incidence
+ *      order.  The weight is the squared area: no square root and no division enters a sum.
+ * 4. Solve, regularised towards the mean.  tr = (A00 + A11) + A22; lam = tr 2^-10; M = A + lam I.  Cofactors, each one
+ *      difference of two products: c00 = M11 M22 - A12 A12, c01 = A02 A12 - A01 M22, c02 = A01 A12 - A02 M11,
+ *      c11 = M00 M22 - A02 A02, c12 = A01 A02 - M00 A12, c22 = M00 M11 - A01 A01.  det = (M00 c00 + A01 c01) + A02 c02.
+ *      y_i = ((C_i0 b0 + C_i1 b1) + C_i2 b2) / det.  The position is fp32(m_c + y), per component.  The cluster FALLS BACK to
+ *      fp32(m_c) unless tr is finite and > 0, det is finite and > 0, y is finite and max |y_i| <= (double)cell, with cell the
+ *      fp32 value the cells were made with.  All fp64, no contraction (-ffp-contract=off).
+ * 5. Faces.  A face is mapped corner by corner to clusters.  It is COLLAPSED, and dropped, when two corners share a cluster.
+ *      The identity of another face is its triple rotated so that the smallest cluster comes first (unique: the clusters are
+ *      distinct; the winding is kept).  A face is a DUPLICATE, and dropped, when a face with a lower index has the same identity.
+ *      Two faces over the same clusters with opposite winding both stay.
+ * 6. Output.  The surviving faces in their order, corners in their original order; the clusters some surviving face holds in
+ *      ascending key order, numbered densely, with positions and colours.  A cluster in no surviving face is dropped.
+ *
+ * cds_mesh_simplify_faces: rule 5 per face.  cluster int32 [n_vertices]: the cluster of every vertex.  Writes face_clusters
+ *   int32 [n_faces][3], collapsed uint8 [n_faces] and identity int32 [n_faces][3].  A face with an index outside the vertices, or
+ *   a cluster outside [0, n_clusters), is written as collapsed with the clusters -1.  The caller finds the duplicates (a stable
+ *   sort of the identities on the device: the first of a run is the lowest index).
+ * cds_mesh_simplify_quadric_f32: rules 2-4.  perm int64 [n_vertices] and start int32 [n_clusters + 1] as voxel_groups returns
+ *   them; inc int64 [3 n_faces]: the corners 3 f + j sorted by their cluster, stable; inc_start int32 [n_clusters + 1].  Writes
+ *   out_positions float32 [n_clusters][3] and out_fallback uint8 [n_clusters].  An offset or index outside its array is skipped.
+ * cds_mesh_simplify_mark: cluster_keep uint8 [n_clusters], zeroed by the caller, is set to 1 for the clusters of the faces with
+ *   face_keep != 0.
+ * cds_mesh_simplify_gather: rule 6.  positions float32 [n_clusters][3]; colors: the packed words of cds_voxel_merge_f32, or null
+ *   (then colors_out is not written); cluster_new / face_new: the exclusive prefix sums of cluster_keep / face_keep, int32;
+ *   out_vertices / out_faces their totals.
+ *   CDS_EINVAL: a count < 0 or >= 2^31; 3 n_faces >= 2^31 (quadric); n_clusters > n_vertices; cell not finite or <= 0; a total
+ *   larger than its input; a null required pointer (an empty input or output returns 0 first).
+ */
+int cds_mesh_simplify_faces(const int* faces, long long n_faces, long long n_vertices, const int* cluster, long long n_clusters,
+                            int* face_clusters, unsigned char* collapsed, int* identity, void* stream);
+int cds_mesh_simplify_quadric_f32(const float* vertices, long long n_vertices, const int* faces, long long n_faces,
+                                  const long long* perm, const int* start, const long long* inc, const int* inc_start,
+                                  long long n_clusters, float cell, float* out_positions, unsigned char* out_fallback,
+                                  void* stream);
+int cds_mesh_simplify_mark(const int* face_clusters, const unsigned char* face_keep, long long n_faces, long long n_clusters,
+                           unsigned char* cluster_keep, void* stream);
+int cds_mesh_simplify_gather(const float* positions, const unsigned* colors, long long n_clusters,
+                             const unsigned char* cluster_keep, const int* cluster_new, const int* face_clusters, long long n_faces,
+                             const unsigned char* face_keep, const int* face_new, long long out_vertices, long long out_faces,
+                             float* vertices_out, unsigned char* colors_out, int* faces_out, void* stream);
+
+/*
  * Norm-curvature bookkeeping of one FeatureNet level (module.py:250-251,257-258,264-265) in one launch:
  *   nc_sum[i] = (a[i]^2 + b[i]^2 + c[i]^2) / 3,  nc_abs[i] = |c[i]|   for the three DynamicConv curvature maps of the level
  */

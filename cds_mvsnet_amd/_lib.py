@@ -164,6 +164,9 @@ SIGNATURES = {
     "cds_mesh_simplify_quadric_f32": [P, L, P, L, P, P, P, P, L, F, P, P, P],
     "cds_mesh_simplify_mark": [P, P, L, L, P, P],
     "cds_mesh_simplify_gather": [P, P, L, P, P, P, L, P, P, L, L, P, P, P, P],
+    "cds_mesh_sample_max_n": [],
+    "cds_mesh_sample_count": [P, L, P, L, DB, P, P, P],
+    "cds_mesh_sample_emit": [P, P, L, P, L, P, P, L, P, P, P, P],
     "cds_grid_hash_log2_slots": [L],
     "cds_grid_keys_f32": [P, L, P, P, P],
     "cds_grid_hash_build": [P, L, L, P, P, I, P],

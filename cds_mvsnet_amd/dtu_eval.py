@@ -15,6 +15,10 @@ reducePts_haa.m, MaxDistCP.m, ComputeStat_web.m) for the fused clouds that ``inf
 
 ``python -m cds_mvsnet_amd.dtu_eval --datapath <MVS Data> --plydir <outdir> --scans 1,4,9`` scores a directory of fused
 clouds.  The inputs must be float32 ROCm tensors; there is no CPU path.
+
+``--sample_faces [SPACING]`` scores a mesh by its surface: the file is read with ``mesh.read_mesh_ply`` and the samples of its
+faces (``mesh.sample_mesh``; SPACING defaults to ``--dst``, a covering radius of 2/3 dst) take the place of its
+vertices, which are not added.  Without it a mesh file is scored as the cloud of its vertices, as before.
 """
 from __future__ import annotations
 
@@ -326,11 +330,19 @@ def main(argv: Optional[Sequence[str]] = None) -> Dict[str, object]:
     ap.add_argument("--seed", type=int, default=0, help="seed of the thinning order")
     ap.add_argument("--json", help="write the per-scan and mean results here")
     ap.add_argument("--device", default="cuda")
+    ap.add_argument("--sample_faces", nargs="?", type=float, const=0.0, default=None, metavar="SPACING",
+                    help="the files are meshes: score the samples of their faces (sub-triangle centroids, edges of at most "
+                         "SPACING, default --dst) instead of their vertices")
     args = ap.parse_args(argv)
 
     dev = torch.device(args.device)
     if dev.type != "cuda":
         raise SystemExit("dtu_eval runs on the GPU only (--device cuda[:N])")
+    spacing = None
+    if args.sample_faces is not None:
+        spacing = args.sample_faces if args.sample_faces != 0.0 else args.dst
+        if not (spacing > 0 and math.isfinite(spacing)):
+            ap.error(f"--sample_faces must be positive, got {spacing}")
     names = scan_names(args.testlist, args.scans)
     jobs = []
     for name in names:                                       # resolve every file before the first scan is scored
@@ -346,16 +358,29 @@ def main(argv: Optional[Sequence[str]] = None) -> Dict[str, object]:
         for name, n, ply in jobs:
             t0 = time.time()
             gt = load_dtu_scan(args.datapath, n)
-            pred = torch.from_numpy(read_ply_points(ply)).to(dev)
+            if spacing is None:
+                pred, sampled = torch.from_numpy(read_ply_points(ply)).to(dev), None
+            else:
+                from .mesh import sample_file
+                try:
+                    out, sampled = sample_file(ply, spacing, dev)
+                except ValueError as e:                          # a cloud, or a spacing too fine for the mesh
+                    raise SystemExit(f"{name}: --sample_faces: {e}") from None
+                pred = out["points"]
             r = evaluate(pred, gt, dst=args.dst, max_dist=args.max_dist, seed=args.seed)
+            if sampled is not None:
+                r.update(n_faces=sampled["faces"], n_sampled=sampled["points"])
             per_scan[name] = r
             print(f"{name}: acc {r['acc']:.4f}  comp {r['comp']:.4f}  overall {r['overall']:.4f}  "
-                  f"({r['acc_n']} / {r['comp_n']} points, {time.time() - t0:.1f} s)", flush=True)
+                  f"({r['acc_n']} / {r['comp_n']} points, {time.time() - t0:.1f} s)"
+                  + (f"  [{r['n_sampled']} samples of {r['n_faces']} faces]" if sampled is not None else ""), flush=True)
     acc = _mean([r["acc"] for r in per_scan.values()])
     comp = _mean([r["comp"] for r in per_scan.values()])
     mean = {"acc": acc, "comp": comp, "overall": (acc + comp) / 2.0}
     print(f"mean over {len(per_scan)} scans: acc {acc:.4f}  comp {comp:.4f}  overall {mean['overall']:.4f}")
     out = {"scans": per_scan, "mean": mean, "settings": {"dst": args.dst, "max_dist": args.max_dist, "seed": args.seed}}
+    if spacing is not None:                                      # without the flag the output stays as it was
+        out["settings"]["sample_faces"] = spacing
     if args.json:
         with open(args.json, "w") as f:
             json.dump(out, f, indent=1)

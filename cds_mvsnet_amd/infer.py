@@ -15,7 +15,8 @@ normal and `--merge_voxel SIZE` (`--merge_min_points K`) merges the scan to one 
 `--mesh_voxel SIZE` (`--mesh_trunc T`, `--mesh_min_weight N`; not for gipuma) also writes `<out>/<scan>_mesh.ply`, a triangle mesh
 from the same fusion pass (mesh.py); `--mesh_min_component N` / `--mesh_keep_largest K` drop its small connected
 components first and `--mesh_simplify CELL` (`--mesh_simplify_placement quadric|mean`) then merges the vertices
-of every cell of that side into one.  With it, `--render_mesh` (`--back`, `--max_rel_diff R`, `--save_image`) renders
+of every cell of that side into one; `--mesh_sample SPACING` also writes `<out>/<scan>_surface.ply`, the surface
+of that mesh as a cloud.  With `--mesh_voxel`, `--render_mesh` (`--back`, `--max_rel_diff R`, `--save_image`) renders
 that mesh into every view, `<out>/<scan>/depth_mesh/%08d.pfm`, and `--export_blended DIR` writes the tree `fit --dataset blended`
 trains from (render.py).
 `--save_stages` also writes the three stages' own depth maps, `<out>/<scan>/depth_stage{1,2,3}/%08d.pfm`, at their resolutions
@@ -237,7 +238,8 @@ def run(args) -> float:
             info = mesh_scan(os.path.join(args.testpath, scan), os.path.join(args.outdir, scan),
                              os.path.join(args.outdir, f"{scan}_mesh.ply"), args.mesh_voxel, args.mesh_trunc, args.mesh_min_weight,
                              cloud_ply=ply, min_component=args.mesh_min_component, keep_largest=args.mesh_keep_largest,
-                             simplify=args.mesh_simplify or 0.0, placement=args.mesh_simplify_placement, **kw)
+                             simplify=args.mesh_simplify or 0.0, placement=args.mesh_simplify_placement,
+                             sample=args.mesh_sample or 0.0, surface_ply=os.path.join(args.outdir, f"{scan}_surface.ply"), **kw)
             print(f"[{rank}] {scan}_mesh.ply: {format_mesh(info)}", flush=True)
             if args.render_mesh:
                 # the mesh just written, from the device tensors, into every view of the scan

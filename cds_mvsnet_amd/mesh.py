@@ -9,7 +9,7 @@ the blocks out.  There is no CPU path.
 
     python -m cds_mvsnet_amd.mesh --testpath <scenes> --outdir <out> --testlist <list> --mesh_voxel SIZE [--mesh_trunc T]
         [--mesh_min_weight 2] [--mesh_min_component N] [--mesh_keep_largest K] [--mesh_simplify CELL]
-        [--mesh_simplify_placement quadric|mean] [--filter_method normal|dynamic] [--conf 0,0,0] [--thres_disp 1.0]
+        [--mesh_simplify_placement quadric|mean] [--mesh_sample SPACING] [--filter_method normal|dynamic] [--conf 0,0,0] [--thres_disp 1.0]
         [--thres_view 3] [--dyn_dist_base 0.25] [--dyn_rel_base 0.000769] [--dyn_views 2,10]
 
 fuses the saved depth maps of ``<out>/<scan>/`` as ``python -m cds_mvsnet_amd.fusion`` does and writes
@@ -27,6 +27,11 @@ cleans saved meshes in place, without the fusion.
 ``csrc/mesh_simplify.hip``): the vertices of a cell of side CELL, the cells of ``--merge_voxel``, become one vertex at the
 regularised minimiser of its faces' quadric error (``--mesh_simplify_placement mean``: at their mean), and the faces that
 collapse or repeat are dropped.  ``--from_mesh FILE --mesh_simplify CELL`` does it to a saved mesh.
+
+``--mesh_sample SPACING`` also writes ``<out>/<scan>_surface.ply``, the surface of the mesh written as a cloud (the
+kernels of ``csrc/mesh_sample.hip``): every face is cut into n^2 congruent sub-triangles with edges of at most SPACING and the
+centroid of each becomes a point, so that every point of the surface lies within 2/3 SPACING of one.  It is what
+``dtu_eval --sample_faces`` and ``tt_eval --sample_faces`` score instead of a mesh's vertices (:func:`sample_mesh`).
 """
 from __future__ import annotations
 
@@ -48,6 +53,8 @@ MAX_CHUNK = 32                 # views per launch the kernel takes (CDS_TSDF_MAX
 CHUNK_VIEWS = 32               # views per launch of TsdfVolume.integrate (profiles/tsdf_mesh.md: 3.5 x faster than 1)
 MAX_ROUNDS = 64                # hook passes of the component labelling before it gives up (CDS_MESH_CC_MAX_ROUNDS)
 PLACEMENTS = ("quadric", "mean")   # where simplify_mesh puts a cluster's vertex
+MAX_SAMPLE_N = 1 << 15         # subdivisions per edge sample_mesh takes (CDS_MESH_SAMPLE_MAX_N): n^2 and the weights fit an int32
+MAX_SAMPLES = 1 << 28          # points sample_mesh makes unless told otherwise: 19 bytes each, 4.75 GiB
 PACK_BITS = 21                 # three cluster numbers of at most this many bits make one sort key of a face's identity
 
 
@@ -481,6 +488,89 @@ def simplify_mesh(mesh_dict: Dict[str, Tensor], cell: float, placement: str = "q
     return out, info
 
 
+# ---------------------------------------------------------------------------------------------------------------- sampling
+def check_spacing(spacing, what: str = "sample_mesh") -> float:
+    """-> spacing as a float; ValueError unless it is finite and > 0."""
+    try:
+        size = float(spacing)
+    except (TypeError, ValueError):
+        size = math.nan
+    if not (size > 0 and math.isfinite(size)):
+        raise ValueError(f"{what}: spacing must be positive, got {spacing}")
+    return size
+
+
+def sample_mesh(mesh_dict: Dict[str, Tensor], spacing: float, max_points: int = MAX_SAMPLES):
+    """A dense, deterministic point set from the faces of a mesh: ``mesh_dict`` as :meth:`TsdfVolume.extract`
+    returns it (vertices float32 [V,3], colors uint8 [V,3], faces int32 [F,3], on one ROCm device).  Every face is cut into n^2
+    congruent sub-triangles, n the smallest count for which the face's longest edge is at most n ``spacing`` (world units), and
+    the centroid of each becomes a point with the interpolated colour: every point of the surface lies within 2/3 ``spacing`` of
+    a sample of its face, and no sample lies on an edge.  A face with a corner that is not finite gives nothing.  -> ({"points"
+    float32 [N,3], "colors" uint8 [N,3], "face" int32 [N]: the face of each sample}, in face order; info: {"faces", "points",
+    "max_n": the largest n, "skipped": faces that gave nothing}).  ValueError, before the samples are allocated, for a face that
+    needs n > 2^15 and for more than ``max_points`` samples."""
+    what = "sample_mesh"
+    spacing = check_spacing(spacing, what)
+    vert, col, faces, nv, dev = _check_mesh(mesh_dict, what)
+    nf = int(faces.shape[0])
+    empty = {"points": torch.zeros((0, 3), dtype=torch.float32, device=dev), "colors": torch.zeros((0, 3), dtype=torch.uint8, device=dev),
+             "face": torch.zeros(0, dtype=torch.int32, device=dev)}
+    if nf == 0:
+        return empty, {"faces": 0, "points": 0, "max_n": 0, "skipped": 0}
+    vert, col, faces = vert.contiguous(), col.contiguous(), faces.contiguous()
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        n = torch.empty(nf, dtype=torch.int32, device=dev)
+        n2 = torch.empty(nf, dtype=torch.int64, device=dev)
+        check(lib.cds_mesh_sample_count(vert.data_ptr(), nv, faces.data_ptr(), nf, spacing, n.data_ptr(), n2.data_ptr(), stream),
+              "cds_mesh_sample_count")
+        ends = torch.cumsum(n2, 0)
+        total, max_n, skipped = (int(x) for x in torch.stack([ends[-1], n.max().long(), (n == 0).sum()]).cpu())   # the one read
+        if max_n > MAX_SAMPLE_N:
+            raise ValueError(f"{what}: a face needs more than {MAX_SAMPLE_N} subdivisions at a spacing of {spacing}: raise the "
+                             "spacing")
+        if total > int(max_points) or total >= 2 ** 31:
+            raise ValueError(f"{what}: a spacing of {spacing} gives {total} points, at most {min(int(max_points), 2 ** 31 - 1)}: "
+                             "raise the spacing or simplify the mesh first")
+        info = {"faces": nf, "points": total, "max_n": max_n, "skipped": skipped}
+        if total == 0:
+            return empty, info
+        offsets = ends - n2
+        out = {"points": torch.empty((total, 3), dtype=torch.float32, device=dev),
+               "colors": torch.empty((total, 3), dtype=torch.uint8, device=dev),
+               "face": torch.empty(total, dtype=torch.int32, device=dev)}
+        check(lib.cds_mesh_sample_emit(vert.data_ptr(), col.data_ptr(), nv, faces.data_ptr(), nf, n.data_ptr(), offsets.data_ptr(),
+                                       total, out["points"].data_ptr(), out["colors"].data_ptr(), out["face"].data_ptr(), stream),
+              "cds_mesh_sample_emit")
+    return out, info
+
+
+def sample_file(path: str, spacing: float, device="cuda", max_points: int = MAX_SAMPLES):
+    """The faces of a mesh file of :func:`write_mesh_ply` through :func:`sample_mesh` -> (its result, its info).  ValueError
+    that names the file when it holds no face (a cloud: there is no surface to sample)."""
+    spacing = check_spacing(spacing, "sample_file")
+    try:
+        v, c, f = read_mesh_ply(path)
+    except ValueError as e:
+        raise ValueError(f"{path}: the faces of a mesh are needed to sample its surface, and this is not a mesh file of "
+                         f"write_mesh_ply ({e})") from None
+    if len(f) == 0:
+        raise ValueError(f"{path}: no faces: there is no surface to sample")
+    dev = torch.device(device)
+    return sample_mesh({"vertices": torch.from_numpy(np.ascontiguousarray(v)).to(dev), "colors": torch.from_numpy(
+        np.ascontiguousarray(c)).to(dev), "faces": torch.from_numpy(np.ascontiguousarray(f)).to(dev)}, spacing, max_points)
+
+
+def write_surface_ply(path: str, mesh_dict: Dict[str, Tensor], spacing: float) -> Dict[str, object]:
+    """The sampled surface of a mesh on the device as an ``x y z red green blue`` cloud (:func:`fusion.write_ply`)
+    -> sample_mesh's info."""
+    from .fusion import write_ply
+    out, info = sample_mesh(mesh_dict, spacing)
+    write_ply(path, out["points"].cpu().numpy(), out["colors"].cpu().numpy())
+    return info
+
+
 # --------------------------------------------------------------------------------------------------------------------- PLY
 _VERTEX =[("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1")]
 _FACE = [("k", "u1"), ("v", "<i4", (3,))]
@@ -555,6 +645,15 @@ def mesh_views(views: Sequence[dict], voxel: float, trunc: Optional[float] = Non
     return vol.extract(min_weight), vol
 
 
+def _check_sample(sample, surface_ply, what: str) -> float:
+    """-> sample as a float, 0.0 for "off"; ValueError for a negative or non-finite spacing or one without a file to write."""
+    if sample is None or sample == 0:
+        return 0.0
+    if surface_ply is None:
+        raise ValueError(f"{what}: sample needs surface_ply, the file of the sampled surface")
+    return check_spacing(sample, what)
+
+
 def _check_simplify(simplify, placement, what: str) -> float:
     """-> simplify as a float, 0.0 for "off"; ValueError for a negative or non-finite cell or an unknown placement."""
     if placement not in PLACEMENTS:
@@ -566,15 +665,19 @@ def _check_simplify(simplify, placement, what: str) -> float:
 
 def mesh_scan(pair_folder: str, scan_folder: str, plyfilename: str, voxel: float, trunc: Optional[float] = None, min_weight: int = 2,
               method: str = "normal", cloud_ply: Optional[str] = None, device: str = "cuda", min_component: int = 0,
-              keep_largest: int = 0, simplify: float = 0.0, placement: str = "quadric", **fusion_options) -> Dict[str, object]:
+              keep_largest: int = 0, simplify: float = 0.0, placement: str = "quadric", sample: float = 0.0,
+              surface_ply: Optional[str] = None, **fusion_options) -> Dict[str, object]:
     """One scan from saved depth maps to a mesh at ``plyfilename``: the fusion pass of :func:`fusion.filter_depth` (``method``
     "normal" or "dynamic" and its ``fusion_options``), then allocation from every view's kept points, integration of the fused
     depth maps in ``pair.txt`` order and extraction.  ``cloud_ply``: also write the fused cloud there, from the same pass and byte
     for byte what ``filter_depth`` writes alone.  ``min_component`` / ``keep_largest``: when either is > 0 the mesh goes through
     :func:`clean_mesh` before it is written; at 0 nothing of that runs.  ``simplify``: a cell side > 0 sends the
     mesh, after the clean-up, through :func:`simplify_mesh` with ``placement``; at 0 nothing of that runs.
+    ``sample``: a spacing > 0 also writes the sampled surface of the mesh written (:func:`sample_mesh`) as a cloud
+    at ``surface_ply``; at 0 nothing of that runs.
     -> {"vertices", "faces", "blocks": counts, "cloud": filter_depth's result, "mesh": the mesh dict written, still on the device
-    (render.render_scan takes it)[, "clean": clean_mesh's info][, "simplify": simplify_mesh's info]}."""
+    (render.render_scan takes it)[, "clean": clean_mesh's info][, "simplify": simplify_mesh's info][, "sample": sample_mesh's
+    info and the spacing]}."""
     from .fusion import filter_depth
     if method == "gipuma":
         raise ValueError("mesh_scan: gipuma fusion is not supported (its fused point has no single depth map); use normal or dynamic")
@@ -584,6 +687,7 @@ def mesh_scan(pair_folder: str, scan_folder: str, plyfilename: str, voxel: float
     if int(min_component) < 0 or int(keep_largest) < 0:
         raise ValueError(f"mesh_scan: min_component and keep_largest must be >= 0, got {min_component} and {keep_largest}")
     simplify = _check_simplify(simplify, placement, "mesh_scan")
+    sample = _check_sample(sample, surface_ply, "mesh_scan")
     views: list = []
     cloud = filter_depth(pair_folder, scan_folder, cloud_ply, device=device, method=method, collect=views, **fusion_options)
     mesh, vol = mesh_views(views, voxel, trunc, min_weight, device)
@@ -599,16 +703,21 @@ def mesh_scan(pair_folder: str, scan_folder: str, plyfilename: str, voxel: float
         out["clean"] = cleaned
     if simplified is not None:
         out["simplify"] = simplified
+    if sample > 0:
+        out["sample"] = dict(write_surface_ply(surface_ply, mesh, sample), spacing=sample)
     return out
 
 
 def clean_file(src_ply: str, dst_ply: str, min_component: int = 0, keep_largest: int = 0, device: str = "cuda",
-               simplify: float = 0.0, placement: str = "quadric") -> Dict[str, object]:
+               simplify: float = 0.0, placement: str = "quadric", sample: float = 0.0,
+               surface_ply: Optional[str] = None) -> Dict[str, object]:
     """A saved mesh through :func:`clean_mesh`, then, with ``simplify`` > 0, through :func:`simplify_mesh`, and back into a file
     (``dst_ply`` may be ``src_ply``): what one runs while tuning the threshold or the cell, without the fusion.  With ``simplify``
-    alone (both clean-up options at 0) the file goes through :func:`simplify_mesh` only, as in :func:`mesh_scan`.
-    -> {"vertices", "faces", "mesh"[, "clean"][, "simplify"]} as :func:`mesh_scan`."""
+    alone (both clean-up options at 0) the file goes through :func:`simplify_mesh` only, as in :func:`mesh_scan`.  ``sample`` > 0
+    also writes the sampled surface of the mesh written to ``surface_ply``, as :func:`mesh_scan` does.
+    -> {"vertices", "faces", "mesh"[, "clean"][, "simplify"][, "sample"]} as :func:`mesh_scan`."""
     simplify = _check_simplify(simplify, placement, "clean_file")
+    sample = _check_sample(sample, surface_ply, "clean_file")
     dev = torch.device(device)
     v, c, f = (torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in read_mesh_ply(src_ply))
     mesh, out = {"vertices": v, "colors": c, "faces": f}, {}
@@ -617,6 +726,8 @@ def clean_file(src_ply: str, dst_ply: str, min_component: int = 0, keep_largest:
     if simplify > 0:
         mesh, out["simplify"] = simplify_mesh(mesh, simplify, placement)
     write_mesh_ply(dst_ply, mesh["vertices"].cpu().numpy(), mesh["colors"].cpu().numpy(), mesh["faces"].cpu().numpy())
+    if sample > 0:
+        out["sample"] = dict(write_surface_ply(surface_ply, mesh, sample), spacing=sample)
     return dict(out, vertices=int(mesh["vertices"].shape[0]), faces=int(mesh["faces"].shape[0]), mesh=mesh)
 
 
@@ -632,12 +743,15 @@ def format_mesh(info: Dict[str, object]) -> str:
         s = info["simplify"]
         text += (f"; simplified {s['vertices'][0]} -> {s['vertices'][1]} vertices and {s['faces'][0]} -> {s['faces'][1]} faces "
                  f"({s['clusters']} clusters, {s['collapsed']} faces collapsed, {s['duplicates']} duplicates, {s['fallback']} fallbacks)")
+    if "sample" in info:
+        s = info["sample"]
+        text += f"; surface sampled at {s['spacing']:g}: {s['points']} points (n up to {s['max_n']}, {s['skipped']} faces skipped)"
     return text
 
 
 # ---------------------------------------------------------------------------------------------------------------------- CLI
 def add_mesh_args(ap: argparse.ArgumentParser, required: bool = False) -> None:
-    """The options of DESIGN §1.9, §1.11 and §1.12, shared with ``infer --fuse``."""
+    """The options of DESIGN §1.9, §1.11, §1.12 and §1.13, shared with ``infer --fuse``."""
     ap.add_argument("--mesh_voxel", type=float, default=None, required=required, metavar="SIZE",
                     help="write <outdir>/<scan>_mesh.ply: a triangle mesh from a TSDF volume with this lattice spacing (world units)")
     ap.add_argument("--mesh_trunc", type=float, default=None, metavar="T",
@@ -654,11 +768,14 @@ def add_mesh_args(ap: argparse.ArgumentParser, required: bool = False) -> None:
     ap.add_argument("--mesh_simplify_placement", default="quadric", choices=list(PLACEMENTS),
                     help="--mesh_simplify: a cell's vertex at the minimiser of its faces' quadric error (edges and corners "
                          "survive) or at the mean of its vertices")
+    ap.add_argument("--mesh_sample", type=float, default=None, metavar="SPACING",
+                    help="--mesh_voxel: also write <outdir>/<scan>_surface.ply, the surface of the mesh written as a cloud: the "
+                         "centroids of every face's sub-triangles with edges of at most SPACING (world units)")
 
 
 def check_clean_args(ap: argparse.ArgumentParser, args, allowed: bool) -> None:
-    """ap.error for a negative clean-up option or a non-positive --mesh_simplify, or for one given where no mesh is made
-    (``allowed`` false)."""
+    """ap.error for a negative clean-up option, a non-positive --mesh_simplify or --mesh_sample, or for one given where no mesh is
+    made (``allowed`` false)."""
     if args.mesh_min_component < 0 or args.mesh_keep_largest < 0:
         ap.error(f"--mesh_min_component and --mesh_keep_largest must be >= 0, got {args.mesh_min_component} and "
                  f"{args.mesh_keep_largest}")
@@ -670,6 +787,11 @@ def check_clean_args(ap: argparse.ArgumentParser, args, allowed: bool) -> None:
         if not allowed:
             ap.error("--mesh_simplify simplifies the mesh of --mesh_voxel: give --mesh_voxel SIZE (or, in mesh, --from_mesh FILE) "
                      "as well")
+    if args.mesh_sample is not None:
+        if not (args.mesh_sample > 0 and math.isfinite(args.mesh_sample)):
+            ap.error(f"--mesh_sample must be positive, got {args.mesh_sample}")
+        if not allowed:
+            ap.error("--mesh_sample samples the mesh of --mesh_voxel: give --mesh_voxel SIZE (or, in mesh, --from_mesh FILE) as well")
 
 
 def main(argv=None) -> Dict[str, Dict[str, object]]:
@@ -692,6 +814,8 @@ def main(argv=None) -> Dict[str, Dict[str, object]]:
                          "--mesh_keep_largest, simplify it with --mesh_simplify, and write <outdir>/<scan>_mesh.ply, without any "
                          "fusion")
     args = ap.parse_args(argv)
+    if args.mesh_voxel is None and args.from_mesh is None and args.mesh_sample is not None:
+        ap.error("--mesh_sample samples the mesh of --mesh_voxel: give --mesh_voxel SIZE or --from_mesh FILE as well")
     if (args.mesh_voxel is None) == (args.from_mesh is None):
         ap.error("give either --mesh_voxel SIZE (fuse and mesh) or --from_mesh FILE (clean a saved mesh)")
     check_clean_args(ap, args, True)
@@ -707,7 +831,8 @@ def main(argv=None) -> Dict[str, Dict[str, object]]:
         for scan in scans:
             out[scan] = clean_file(args.from_mesh.format(scan=scan), os.path.join(args.outdir, f"{scan}_mesh.ply"),
                                    args.mesh_min_component, args.mesh_keep_largest, device=args.device,
-                                   simplify=args.mesh_simplify or 0.0, placement=args.mesh_simplify_placement)
+                                   simplify=args.mesh_simplify or 0.0, placement=args.mesh_simplify_placement,
+                                   sample=args.mesh_sample or 0.0, surface_ply=os.path.join(args.outdir, f"{scan}_surface.ply"))
             print(f"{scan}_mesh.ply: {format_mesh(out[scan])}", flush=True)
         return out
     for scan in scans:
@@ -715,7 +840,8 @@ def main(argv=None) -> Dict[str, Dict[str, object]]:
                          os.path.join(args.outdir, f"{scan}_mesh.ply"), args.mesh_voxel, args.mesh_trunc, args.mesh_min_weight,
                          method=args.filter_method, device=args.device, min_component=args.mesh_min_component,
                          keep_largest=args.mesh_keep_largest, simplify=args.mesh_simplify or 0.0,
-                         placement=args.mesh_simplify_placement, conf=_floats(args.conf, 3, "--conf"),
+                         placement=args.mesh_simplify_placement, sample=args.mesh_sample or 0.0,
+                         surface_ply=os.path.join(args.outdir, f"{scan}_surface.ply"), conf=_floats(args.conf, 3, "--conf"),
                          thres_disp=args.thres_disp, thres_view=args.thres_view, dist_base=args.dyn_dist_base,
                          rel_base=args.dyn_rel_base, n_views=tuple(int(v) for v in _floats(args.dyn_views, 2, "--dyn_views")))
         out[scan] = info

@@ -23,6 +23,10 @@ the ``.ply``; the resulting transform replaces ``<Scene>_trans.txt @ init`` as t
 mapping file for video-rate logs is out of scope: both trajectories must list the same cameras in the same order.  The hot
 paths are the HIP kernels of ``csrc/registration.hip``, ``csrc/ransac.hip`` and ``csrc/pointcloud.hip``; clouds must be
 float32 ROCm tensors (correspondences float64), there is no CPU path.
+
+``--sample_faces [SPACING]`` scores a mesh by its surface: the file is read with ``mesh.read_mesh_ply`` and the samples of its
+faces (``mesh.sample_mesh``; SPACING defaults to tau / 2, the voxel of step 2) take the place of its vertices,
+which are not added.  Without it a mesh file is scored as the cloud of its vertices, as before.
 """
 from __future__ import annotations
 
@@ -518,7 +522,12 @@ def main(argv: Optional[Sequence[str]] = None) -> Dict[str, object]:
     ap.add_argument("--no-register", action="store_true", help="score at the initial transform, without the ICP rounds")
     ap.add_argument("--json", help="write the per-scene and mean results here")
     ap.add_argument("--device", default="cuda")
+    ap.add_argument("--sample_faces", nargs="?", type=float, const=0.0, default=None, metavar="SPACING",
+                    help="the files are meshes: score the samples of their faces (sub-triangle centroids, edges of at most "
+                         "SPACING, default tau / 2, the voxel the toolbox samples at) instead of their vertices")
     args = ap.parse_args(argv)
+    if args.sample_faces is not None and not (args.sample_faces >= 0 and math.isfinite(args.sample_faces)):
+        ap.error(f"--sample_faces must be positive, got {args.sample_faces}")
 
     dev = torch.device(args.device)
     if dev.type != "cuda":
@@ -554,7 +563,17 @@ def main(argv: Optional[Sequence[str]] = None) -> Dict[str, object]:
         for scene, tau, ply, paths in jobs:
             t0 = time.time()
             gt = torch.from_numpy(read_ply_points(paths["ply"])).to(dev)
-            pred = torch.from_numpy(read_ply_points(ply)).to(dev)
+            sampled = None
+            if args.sample_faces is None:
+                pred = torch.from_numpy(read_ply_points(ply)).to(dev)
+            else:
+                from .mesh import sample_file
+                spacing = args.sample_faces if args.sample_faces != 0.0 else tau / 2.0
+                try:
+                    out, sampled = sample_file(ply, spacing, dev)
+                except ValueError as e:                          # a cloud, or a spacing too fine for the mesh
+                    raise SystemExit(f"{scene}: --sample_faces: {e}") from None
+                pred = out["points"]
             start, traj = read_trans(paths["trans"]) @ init, None
             if aligned:
                 est = camera_poses_from_cams(paths["cams"]) if args.cams else read_log_trajectory(paths["traj"])
@@ -566,15 +585,20 @@ def main(argv: Optional[Sequence[str]] = None) -> Dict[str, object]:
             r = evaluate(pred, gt, read_crop(paths["crop"]), start, tau, register=not args.no_register)
             if traj is not None:
                 r["trajectory"] = traj
+            if sampled is not None:
+                r.update(n_faces=sampled["faces"], n_sampled=sampled["points"], sample_spacing=spacing)
             per_scene[scene] = r
             print(f"{scene}: precision {r['precision']:.4f}  recall {r['recall']:.4f}  f-score {r['fscore']:.4f}  "
-                  f"(tau {tau:g}, {r['n_pred_sampled']} / {r['n_gt_sampled']} points, {time.time() - t0:.1f} s)", flush=True)
+                  f"(tau {tau:g}, {r['n_pred_sampled']} / {r['n_gt_sampled']} points, {time.time() - t0:.1f} s)"
+                  + (f"  [{r['n_sampled']} samples of {r['n_faces']} faces]" if sampled is not None else ""), flush=True)
     mean = {k: _mean([r[k] for r in per_scene.values()]) for k in ("precision", "recall", "fscore")}
     print(f"mean over {len(per_scene)} scenes: precision {mean['precision']:.4f}  recall {mean['recall']:.4f}  "
           f"f-score {mean['fscore']:.4f}")
     out = {"scenes": per_scene, "mean": mean, "settings": {"tau": args.tau, "register": not args.no_register}}
     if aligned:                                                      # without the alignment the output stays as it was
         out["settings"]["seed"] = args.seed
+    if args.sample_faces is not None:                                # likewise; 0: tau / 2 of each scene
+        out["settings"]["sample_faces"] = args.sample_faces if args.sample_faces != 0.0 else "tau / 2"
     if args.json:
         with open(args.json, "w") as f:
             json.dump(out, f, indent=1)

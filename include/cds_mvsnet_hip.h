@@ -831,6 +831,44 @@ int cds_mesh_simplify_gather(const float* positions, const unsigned* colors, lon
                              float* vertices_out, unsigned char* colors_out, int* faces_out, void* stream);
 
 /*
+ * Surface samples of a triangle mesh: a dense, deterministic point set from the faces (csrc/mesh_sample.hip).
+ *
+ * Inputs.  vertices float32 [V][3]; colors uint8 [V][3]; faces int32 [F][3], every index in [0, V) (the host refuses another
+ *   mesh; a kernel skips such a face and reads nothing there); spacing > 0, finite, a double.
+ * 1. Subdivision count per face.  A, B, C: the corners as doubles.  L2: the largest of the three squared edge lengths, each
+ *      ((dx dx + dy dy) + dz dz) in fp64.  n is the smallest integer >= 1 with ((double)n spacing) ((double)n spacing) >= L2,
+ *      evaluated in fp64.  The kernel starts from ceil(sqrt(L2) / spacing) and corrects downwards and upwards with that test, so
+ *      n does not depend on how sqrt or the division round.  A face with a corner coordinate that is not finite has n = 0 and
+ *      emits nothing; a face with L2 == 0 has n = 1.  n > CDS_MESH_SAMPLE_MAX_N = 2^15 is refused by the host.
+ * 2. Samples.  The barycentric lattice cuts the face into n^2 congruent sub-triangles; sample k in [0, n^2) is the centroid of
+ *      sub-triangle k.  r = isqrt(k) exactly (an integer correction after any floating-point guess), c = k - r r, j = c >> 1.
+ *      Even c (upright): p = 3 r + 2, q = 3 j + 1; odd c: p = 3 r + 1, q = 3 j + 2.  Integer weights wa = 3 n - p, wb = p - q,
+ *      wc = q: all > 0, their sum 3 n.  Position per component: ((wa A + wb B) + wc C) / (double)(3 n) in fp64, no contraction
+ *      (-ffp-contract=off), rounded once to fp32.  Colour per channel, in integers: (2 (wa ca + wb cb + wc cc) + 3 n) / (6 n),
+ *      which rounds half up.
+ * 3. Order.  Face order, then k ascending.  Outputs: points float32 [N][3], colors uint8 [N][3], face int32 [N], N = sum n^2.
+ *
+ * cds_mesh_sample_max_n: CDS_MESH_SAMPLE_MAX_N.
+ * cds_mesh_sample_count: rule 1, one thread per face.  Writes out_n int32 [n_faces], clamped to CDS_MESH_SAMPLE_MAX_N + 1 so that
+ *   the host sees an overflow, and out_n2 int64 [n_faces] = n n.  A face with an index outside the vertices gets 0.
+ * cds_mesh_sample_emit: rules 2 and 3, by sample: a workgroup owns a run of consecutive output indices, finds the run's faces by
+ *   a binary search in offsets and its threads resolve their face inside that range.  n int32 [n_faces] as the count kernel wrote
+ *   it; offsets int64 [n_faces]: the exclusive prefix sum of n n (faces without samples repeat the next offset; the sample
+ *   belongs to the last face whose offset is <= its index); n_points the total.  out_points, out_colors and out_face 16-byte
+ *   aligned.  A sample whose face has an index outside the vertices, an n outside 1 .. CDS_MESH_SAMPLE_MAX_N
+ *   or offsets that do not fit n n is not written.
+ *   CDS_EINVAL: a count < 0 or >= 2^31; spacing not finite or <= 0; a null required pointer or a misaligned output (an empty
+ *   input or output returns 0 first).
+ */
+#define CDS_MESH_SAMPLE_MAX_N 32768
+int cds_mesh_sample_max_n(void);
+int cds_mesh_sample_count(const float* vertices, long long n_vertices, const int* faces, long long n_faces, double spacing,
+                          int* out_n, long long* out_n2, void* stream);
+int cds_mesh_sample_emit(const float* vertices, const unsigned char* colors, long long n_vertices, const int* faces,
+                         long long n_faces, const int* n, const long long* offsets, long long n_points, float* out_points,
+                         unsigned char* out_colors, int* out_face, void* stream);
+
+/*
  * Norm-curvature bookkeeping of one FeatureNet level (module.py:250-251,257-258,264-265) in one launch:
  *   nc_sum[i] = (a[i]^2 + b[i]^2 + c[i]^2) / 3,  nc_abs[i] = |c[i]|   for the three DynamicConv curvature maps of the level
  */

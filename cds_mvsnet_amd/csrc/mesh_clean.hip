@@ -7,6 +7,8 @@
 //   cds_mesh_cc_count    one wave per 1024 faces: count[label of a face's first vertex] += 1, aggregated inside the wave first
 //   cds_mesh_cc_mark     one thread per face: the keep flag of the face, and of its three vertices when it is kept
 //   cds_mesh_cc_gather   one thread per vertex and per face: the kept rows at their new places, the faces renumbered
+// The last one is cds_mesh_compact_dispatch (mesh_common.hpp), defined here: the same kernel, with packed colours, is
+// cds_mesh_simplify_gather.  The face loader and the launch shape are those of mesh_common.hpp.
 //
 // The union-find keeps parent[x] <= x at every moment: init writes x, hook only lowers a word (atomicMin) and jump replaces
 // a word by an ancestor of its vertex, which is not larger.  Three things follow.
@@ -23,11 +25,11 @@
 // (the link is found again in the next pass, and whoever lowered parent[r] raised `changed`, so there is a next pass), or moves
 // r's subtree from its parent m to the smaller root; the face that tied r to m is still in the list and ties the two trees again
 // in the next pass, and this thread raised `changed`.  Either way the cost is a pass, never a wrong label.
-#include "cds_common.hpp"
+#include "mesh_common.hpp"
 
 namespace {
 
-constexpr int kThreads = 256;
+using namespace cds_mesh;
 
 __device__ __forceinline__ int load_parent(const int* parent, long long x) {
   return __hip_atomic_load(parent + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -40,17 +42,6 @@ __device__ __forceinline__ int find_root(const int* parent, int x) {
     if (p >= x || p < 0) return x;
     x = p;
   }
-}
-
-// The three indices of a face; false for a face with an index outside the vertices, which every kernel skips.
-__device__ __forceinline__ bool load_face(const int* __restrict__ faces, long long face, long long n_vertices, int idx[3]) {
-  bool ok = true;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    idx[k] = faces[3 * face + k];
-    ok = ok && (unsigned long long)(long long)idx[k] < (unsigned long long)n_vertices;
-  }
-  return ok;
 }
 
 __global__ __launch_bounds__(kThreads) void cc_init_kernel(int* __restrict__ parent, long long n_vertices) {
@@ -134,16 +125,17 @@ __global__ __launch_bounds__(kThreads) void cc_mark_kernel(const int* __restrict
   if (kept) { vertex_keep[idx[0]] = 1; vertex_keep[idx[1]] = 1; vertex_keep[idx[2]] = 1; }   // every writer stores the same byte
 }
 
-// Items 0 .. n_vertices - 1 are vertices, the rest faces.  *_new: the exclusive prefix sums of the keep flags.
-__global__ __launch_bounds__(kThreads) void cc_gather_kernel(const unsigned* __restrict__ vertices,
-                                                             const unsigned char* __restrict__ colors,
-                                                             const int* __restrict__ faces, long long n_vertices, long long n_faces,
-                                                             const unsigned char* __restrict__ vertex_keep,
-                                                             const int* __restrict__ vertex_new,
-                                                             const unsigned char* __restrict__ face_keep,
-                                                             const int* __restrict__ face_new, long long out_vertices,
-                                                             long long out_faces, unsigned* __restrict__ vertices_out,
-                                                             unsigned char* __restrict__ colors_out, int* __restrict__ faces_out) {
+// Items 0 .. n_vertices - 1 are vertices, the rest faces.  *_new: the exclusive prefix sums of the keep flags.  Color: unsigned
+// char for three bytes per row, unsigned for the packed word of cds_voxel_merge_f32.
+template <typename Color>
+__global__ __launch_bounds__(kThreads) void compact_kernel(const unsigned* __restrict__ vertices, const Color* __restrict__ colors,
+                                                           const int* __restrict__ faces, long long n_vertices, long long n_faces,
+                                                           const unsigned char* __restrict__ vertex_keep,
+                                                           const int* __restrict__ vertex_new,
+                                                           const unsigned char* __restrict__ face_keep,
+                                                           const int* __restrict__ face_new, long long out_vertices,
+                                                           long long out_faces, unsigned* __restrict__ vertices_out,
+                                                           unsigned char* __restrict__ colors_out, int* __restrict__ faces_out) {
   const long long i = (long long)blockIdx.x * kThreads + threadIdx.x;
   if (i < n_vertices) {
     if (!vertex_keep[i]) return;
@@ -151,9 +143,15 @@ __global__ __launch_bounds__(kThreads) void cc_gather_kernel(const unsigned* __r
     if (j < 0 || j >= out_vertices) return;
 #pragma unroll
     for (int k = 0; k < 3; ++k) vertices_out[3 * j + k] = vertices[3 * i + k];       // the bits, not the value
-    if (colors)
+    if (!colors) return;
+    if constexpr (sizeof(Color) == 1) {
 #pragma unroll
       for (int k = 0; k < 3; ++k) colors_out[3 * j + k] = colors[3 * i + k];
+    } else {
+      const unsigned w = colors[i];
+#pragma unroll
+      for (int k = 0; k < 3; ++k) colors_out[3 * j + k] = (unsigned char)((w >> (8 * k)) & 255u);
+    }
     return;
   }
   const long long face = i - n_vertices;
@@ -164,12 +162,6 @@ __global__ __launch_bounds__(kThreads) void cc_gather_kernel(const unsigned* __r
 #pragma unroll
   for (int k = 0; k < 3; ++k) faces_out[3 * j + k] = vertex_new[idx[k]];
 }
-
-bool sizes_ok(long long n_vertices, long long n_faces) {
-  return n_vertices >= 0 && n_vertices <= 0x7fffffffLL && n_faces >= 0 && n_faces <= 0x7fffffffLL;
-}
-
-unsigned blocks_for(long long n) { return (unsigned)((n + kThreads - 1) / kThreads); }
 
 }  // namespace
 
@@ -220,19 +212,30 @@ extern "C" int cds_mesh_cc_mark(const int* faces, long long n_faces, long long n
   return cds_launch_status();
 }
 
-extern "C" int cds_mesh_cc_gather(const float* vertices, const unsigned char* colors, const int* faces, long long n_vertices,
-                                  long long n_faces, const unsigned char* vertex_keep, const int* vertex_new,
-                                  const unsigned char* face_keep, const int* face_new, long long out_vertices, long long out_faces,
-                                  float* vertices_out, unsigned char* colors_out, int* faces_out, void* stream) {
+int cds_mesh_compact_dispatch(const float* vertices, const void* colors, bool packed, const int* faces, long long n_vertices,
+                              long long n_faces, const unsigned char* vertex_keep, const int* vertex_new,
+                              const unsigned char* face_keep, const int* face_new, long long out_vertices, long long out_faces,
+                              float* vertices_out, unsigned char* colors_out, int* faces_out, void* stream) {
   if (!sizes_ok(n_vertices, n_faces) || !sizes_ok(out_vertices, out_faces) || out_vertices > n_vertices || out_faces > n_faces)
     return CDS_EINVAL;
   if (out_vertices == 0) return 0;                                       // no kept vertex: no kept face either
   if (!vertices || !vertex_keep || !vertex_new || !vertices_out || (colors && !colors_out)) return CDS_EINVAL;
   if (out_faces > 0 && (!faces || !face_keep || !face_new || !faces_out)) return CDS_EINVAL;
-  const long long items = n_vertices + (out_faces > 0 ? n_faces : 0);
-  hipLaunchKernelGGL(cc_gather_kernel, dim3(blocks_for(items)), dim3(kThreads), 0, (hipStream_t)stream,
-                     reinterpret_cast<const unsigned*>(vertices), colors, faces, n_vertices, out_faces > 0 ? n_faces : 0, vertex_keep,
-                     vertex_new, face_keep, face_new, out_vertices, out_faces, reinterpret_cast<unsigned*>(vertices_out), colors_out,
-                     faces_out);
+  if (out_faces == 0) n_faces = 0;                                       // vertex items only
+  const auto launch = [&](auto kernel, auto* typed_colors) {
+    hipLaunchKernelGGL(kernel, dim3(blocks_for(n_vertices + n_faces)), dim3(kThreads), 0, (hipStream_t)stream,
+                       reinterpret_cast<const unsigned*>(vertices), typed_colors, faces, n_vertices, n_faces, vertex_keep, vertex_new,
+                       face_keep, face_new, out_vertices, out_faces, reinterpret_cast<unsigned*>(vertices_out), colors_out, faces_out);
+  };
+  if (packed) launch(compact_kernel<unsigned>, static_cast<const unsigned*>(colors));
+  else launch(compact_kernel<unsigned char>, static_cast<const unsigned char*>(colors));
   return cds_launch_status();
+}
+
+extern "C" int cds_mesh_cc_gather(const float* vertices, const unsigned char* colors, const int* faces, long long n_vertices,
+                                  long long n_faces, const unsigned char* vertex_keep, const int* vertex_new,
+                                  const unsigned char* face_keep, const int* face_new, long long out_vertices, long long out_faces,
+                                  float* vertices_out, unsigned char* colors_out, int* faces_out, void* stream) {
+  return cds_mesh_compact_dispatch(vertices, colors, false, faces, n_vertices, n_faces, vertex_keep, vertex_new, face_keep, face_new,
+                                   out_vertices, out_faces, vertices_out, colors_out, faces_out, stream);
 }

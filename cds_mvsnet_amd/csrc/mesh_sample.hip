@@ -8,30 +8,18 @@
 //
 // Nothing here depends on an order the hardware chooses: every output word is written once, by the thread its index names.  No
 // atomics.  The only floating-point decision is rule 1's test; the enumeration and the weights are integers.  The library is built
-// with -ffp-contract=off, so every fp64 product, sum and quotient below is rounded as written.
-#include "cds_common.hpp"
+// with -ffp-contract=off, so every fp64 product, sum and quotient below is rounded as written.  The face loader, the finiteness
+// test and the launch shape are those of mesh_common.hpp.
+#include "mesh_common.hpp"
 
 namespace {
 
-constexpr int kThreads = 256;
+using namespace cds_mesh;
+
 constexpr int kPerThread = 4;                                            // consecutive samples of one thread: 16-byte stores
 constexpr int kRun = kThreads * kPerThread;                              // consecutive samples of one pass of a workgroup
 constexpr int kRunsPerBlock = 8;                                         // consecutive runs of one workgroup
 constexpr int kMaxN = CDS_MESH_SAMPLE_MAX_N;
-constexpr double kHuge = 1.7976931348623157e308;
-
-__device__ __forceinline__ bool is_finite(double x) { return fabs(x) <= kHuge; }              // false for a NaN
-
-// The three indices of a face; false for a face with an index outside the vertices, which both kernels skip.
-__device__ __forceinline__ bool load_face(const int* __restrict__ faces, long long face, long long n_vertices, int idx[3]) {
-  bool ok = true;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    idx[k] = faces[3 * face + k];
-    ok = ok && (unsigned long long)(long long)idx[k] < (unsigned long long)n_vertices;
-  }
-  return ok;
-}
 
 __device__ __forceinline__ double edge2(const double a[3], const double b[3]) {
   const double dx = a[0] - b[0], dy = a[1] - b[1], dz = a[2] - b[2];
@@ -271,21 +259,17 @@ __global__ __launch_bounds__(kThreads) void emit_kernel(const float* __restrict_
   }
 }
 
-bool sizes_ok(long long n_a, long long n_b) { return n_a >= 0 && n_a <= 0x7fffffffLL && n_b >= 0 && n_b <= 0x7fffffffLL; }
-
-bool spacing_ok(double spacing) { return spacing > 0.0 && spacing <= kHuge; }                 // false for a NaN
-
 }  // namespace
 
 extern "C" int cds_mesh_sample_max_n(void) { return kMaxN; }
 
 extern "C" int cds_mesh_sample_count(const float* vertices, long long n_vertices, const int* faces, long long n_faces,
                                      double spacing, int* out_n, long long* out_n2, void* stream) {
-  if (!sizes_ok(n_vertices, n_faces) || !spacing_ok(spacing)) return CDS_EINVAL;
+  if (!sizes_ok(n_vertices, n_faces) || !finite_pos(spacing)) return CDS_EINVAL;
   if (n_faces == 0) return 0;
   if (!faces || !out_n || !out_n2 || (n_vertices > 0 && !vertices)) return CDS_EINVAL;
-  hipLaunchKernelGGL(count_kernel, dim3((unsigned)((n_faces + kThreads - 1) / kThreads)), dim3(kThreads), 0, (hipStream_t)stream,
-                     vertices, n_vertices, faces, n_faces, spacing, out_n, out_n2);
+  hipLaunchKernelGGL(count_kernel, dim3(blocks_for(n_faces)), dim3(kThreads), 0, (hipStream_t)stream, vertices, n_vertices, faces,
+                     n_faces, spacing, out_n, out_n2);
   return cds_launch_status();
 }
 

@@ -8,31 +8,18 @@
 //   cds_mesh_simplify_quadric_f32  one thread per cluster: the fp64 mean of its members, the nine sums of rule 3 over its incidences
 //                                  in ascending (face, corner) order, the regularised solve of rule 4
 //   cds_mesh_simplify_mark         one thread per face: the keep flag of the three clusters of a surviving face
-//   cds_mesh_simplify_gather       one thread per cluster and per face: the kept clusters' rows and the renumbered faces
+//   cds_mesh_simplify_gather       one thread per cluster and per face: the kept clusters' rows and the renumbered faces; it is
+//                                  the compaction of cds_mesh_cc_gather (cds_mesh_compact_dispatch, mesh_common.hpp) with the
+//                                  clusters as vertices and packed colours, and has no kernel here
 //
 // Nothing here depends on an order the hardware chooses: the sums of a cluster are one thread's serial chain in the order the
-// rule gives, mark stores the same byte from every writer, and the other two kernels write each word once.  No float atomics.
+// rule gives, mark stores the same byte from every writer, and the other kernels write each word once.  No float atomics.
 // The library is built with -ffp-contract=off, so every fp64 product and sum below is rounded as written.
-#include "cds_common.hpp"
+#include "mesh_common.hpp"
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr double kHuge = 1.7976931348623157e308;
-
-__device__ __forceinline__ bool finite_pos(double x) { return x > 0.0 && x <= kHuge; }      // false for a NaN
-__device__ __forceinline__ bool is_finite(double x) { return fabs(x) <= kHuge; }              // false for a NaN
-
-// The three indices of a face; false for a face with an index outside the vertices, which every kernel skips.
-__device__ __forceinline__ bool load_face(const int* __restrict__ faces, long long face, long long n_vertices, int idx[3]) {
-  bool ok = true;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    idx[k] = faces[3 * face + k];
-    ok = ok && (unsigned long long)(long long)idx[k] < (unsigned long long)n_vertices;
-  }
-  return ok;
-}
+using namespace cds_mesh;
 
 // A face outside the vertices, or one whose vertex has a cluster outside [0, n_clusters), is written as collapsed with the
 // clusters -1: nothing later reads a row through it.
@@ -141,49 +128,6 @@ __global__ __launch_bounds__(kThreads) void mark_kernel(const int* __restrict__ 
   }
 }
 
-// Items 0 .. n_clusters - 1 are clusters, the rest faces.  *_new: the exclusive prefix sums of the keep flags.  colors: the
-// packed words of cds_voxel_merge_f32 (r | g << 8 | b << 16).
-__global__ __launch_bounds__(kThreads) void gather_kernel(const unsigned* __restrict__ positions, const unsigned* __restrict__ colors,
-                                                          long long n_clusters, const unsigned char* __restrict__ cluster_keep,
-                                                          const int* __restrict__ cluster_new,
-                                                          const int* __restrict__ face_clusters, long long n_faces,
-                                                          const unsigned char* __restrict__ face_keep,
-                                                          const int* __restrict__ face_new, long long out_vertices,
-                                                          long long out_faces, unsigned* __restrict__ vertices_out,
-                                                          unsigned char* __restrict__ colors_out, int* __restrict__ faces_out) {
-  const long long i = (long long)blockIdx.x * kThreads + threadIdx.x;
-  if (i < n_clusters) {
-    if (!cluster_keep[i]) return;
-    const long long j = cluster_new[i];
-    if (j < 0 || j >= out_vertices) return;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) vertices_out[3 * j + k] = positions[3 * i + k];       // the bits, not the value
-    if (colors) {
-      const unsigned w = colors[i];
-      colors_out[3 * j] = (unsigned char)(w & 255u);
-      colors_out[3 * j + 1] = (unsigned char)((w >> 8) & 255u);
-      colors_out[3 * j + 2] = (unsigned char)((w >> 16) & 255u);
-    }
-    return;
-  }
-  const long long face = i - n_clusters;
-  if (face >= n_faces || !face_keep[face]) return;
-  const long long j = face_new[face];
-  if (j < 0 || j >= out_faces) return;
-  int c[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    c[k] = face_clusters[3 * face + k];
-    if ((unsigned long long)(long long)c[k] >= (unsigned long long)n_clusters) return;
-  }
-#pragma unroll
-  for (int k = 0; k < 3; ++k) faces_out[3 * j + k] = cluster_new[c[k]];
-}
-
-bool sizes_ok(long long n_a, long long n_b) { return n_a >= 0 && n_a <= 0x7fffffffLL && n_b >= 0 && n_b <= 0x7fffffffLL; }
-
-unsigned blocks_for(long long n) { return (unsigned)((n + kThreads - 1) / kThreads); }
-
 }  // namespace
 
 extern "C" int cds_mesh_simplify_faces(const int* faces, long long n_faces, long long n_vertices, const int* cluster,
@@ -227,15 +171,6 @@ extern "C" int cds_mesh_simplify_gather(const float* positions, const unsigned* 
                                         long long n_faces, const unsigned char* face_keep, const int* face_new,
                                         long long out_vertices, long long out_faces, float* vertices_out,
                                         unsigned char* colors_out, int* faces_out, void* stream) {
-  if (!sizes_ok(n_clusters, n_faces) || !sizes_ok(out_vertices, out_faces) || out_vertices > n_clusters || out_faces > n_faces)
-    return CDS_EINVAL;
-  if (out_vertices == 0) return 0;                                       // no kept cluster: no kept face either
-  if (!positions || !cluster_keep || !cluster_new || !vertices_out || (colors && !colors_out)) return CDS_EINVAL;
-  if (out_faces > 0 && (!face_clusters || !face_keep || !face_new || !faces_out)) return CDS_EINVAL;
-  const long long items = n_clusters + (out_faces > 0 ? n_faces : 0);
-  hipLaunchKernelGGL(gather_kernel, dim3(blocks_for(items)), dim3(kThreads), 0, (hipStream_t)stream,
-                     reinterpret_cast<const unsigned*>(positions), colors, n_clusters, cluster_keep, cluster_new, face_clusters,
-                     out_faces > 0 ? n_faces : 0, face_keep, face_new, out_vertices, out_faces,
-                     reinterpret_cast<unsigned*>(vertices_out), colors_out, faces_out);
-  return cds_launch_status();
+  return cds_mesh_compact_dispatch(positions, colors, true, face_clusters, n_clusters, n_faces, cluster_keep, cluster_new, face_keep,
+                                   face_new, out_vertices, out_faces, vertices_out, colors_out, faces_out, stream);
 }

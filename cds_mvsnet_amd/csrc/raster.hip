@@ -11,14 +11,18 @@
 // visibility reduction is a 64-bit unsigned minimum over keys (depth bits, face index): it does not depend on the order in which
 // fragments arrive, so it is done with the vector memory atomic that atomicMin compiles to (global_atomic_umin_x2, no
 // compare-and-swap loop), the only atomic of this file.  Every loop has its bound fixed before it starts: the candidate count of the face.
-#include "cds_common.hpp"
+// The workgroup size, blocks_for and resolve's face loader are those of mesh_common.hpp; face_setup keeps its own bounds test, which
+// it interleaves with the loads of xy.
+#include "mesh_common.hpp"
 
 namespace {
+
+using cds_mesh::blocks_for;
+using cds_mesh::kThreads;
 
 constexpr int kCam = CDS_RASTER_CAM;           // doubles per camera: R 0..8, t 9..11, fx 12, s 13, cx 14, fy 15, cy 16
 constexpr int kUnusable = INT_MIN;             // X of a vertex that rule 1 rejects
 constexpr long long kSnapLimit = 1ll << 28;
-constexpr int kThreads = 256;
 
 // Rules 2 and 3 up to the candidate box of one face in one view.
 struct FaceSetup {
@@ -207,12 +211,7 @@ __global__ __launch_bounds__(kThreads) void raster_resolve_kernel(const unsigned
   int fo = -1;
   unsigned char fr = 0, rgb[3] = {0, 0, 0};
   int idx[3] = {0, 0, 0};
-  bool hit = key != ~0ull && face < n_faces;
-  if (hit)
-    for (int k = 0; k < 3; ++k) {
-      idx[k] = faces[3 * face + k];
-      hit = hit && (unsigned long long)(long long)idx[k] < (unsigned long long)n_vertices;
-    }
+  const bool hit = key != ~0ull && face < n_faces && cds_mesh::load_face(faces, face, n_vertices, idx);
   if (hit) {
     z = __uint_as_float((unsigned)(key >> 32));
     fo = (int)face;
@@ -256,8 +255,6 @@ bool sizes_ok(long long n_vertices, long long n_faces, int n_views, int h, int w
   return n_vertices >= 0 && n_vertices <= 0x7fffffffLL && n_faces >= 0 && n_faces <= 0x7fffffffLL && n_views >= 1 &&
          n_views <= CDS_RASTER_MAX_CHUNK && h >= 1 && w >= 1 && (long long)h * w <= 0x7fffffffLL;
 }
-
-unsigned blocks_for(long long n) { return (unsigned)((n + kThreads - 1) / kThreads); }
 
 }  // namespace
 

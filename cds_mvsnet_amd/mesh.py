@@ -58,15 +58,30 @@ MAX_SAMPLES = 1 << 28          # points sample_mesh makes unless told otherwise:
 PACK_BITS = 21                 # three cluster numbers of at most this many bits make one sort key of a face's identity
 
 
-def check_voxel(voxel, trunc=None, what: str = "mesh"):
-    """-> (voxel, trunc) as floats; trunc defaults to 4 voxels.  ValueError unless voxel > 0 and voxel <= trunc <= 8 voxel."""
+def _positive(value, name: str, what: str = "") -> float:
+    """-> value as a float; ValueError "[what: ]name must be positive" unless it is finite and > 0."""
     try:
-        size = float(voxel)
+        size = float(value)
     except (TypeError, ValueError):
         size = math.nan
     if not (size > 0 and math.isfinite(size)):
-        raise ValueError(f"{what}: voxel must be positive, got {voxel}")
-    voxel = size
+        raise ValueError(f"{what + ': ' if what else ''}{name} must be positive, got {value}")
+    return size
+
+
+def _stream(dev) -> int:
+    return torch.cuda.current_stream(dev).cuda_stream
+
+
+def _empty_mesh(dev, nv: int = 0, nf: int = 0) -> Dict[str, Tensor]:
+    """A mesh dict of nv and nf rows to be written; the empty mesh by default."""
+    return {"vertices": torch.empty((nv, 3), dtype=torch.float32, device=dev),
+            "colors": torch.empty((nv, 3), dtype=torch.uint8, device=dev), "faces": torch.empty((nf, 3), dtype=torch.int32, device=dev)}
+
+
+def check_voxel(voxel, trunc=None, what: str = "mesh"):
+    """-> (voxel, trunc) as floats; trunc defaults to 4 voxels.  ValueError unless voxel > 0 and voxel <= trunc <= 8 voxel."""
+    voxel = _positive(voxel, "voxel", what)
     trunc = 4.0 * voxel if trunc is None else float(trunc)
     if not (voxel <= trunc <= 8.0 * voxel):
         raise ValueError(f"{what}: trunc must lie in [voxel, 8 voxel] = [{voxel}, {8.0 * voxel}], got {trunc} (the band of +-trunc "
@@ -151,9 +166,6 @@ class TsdfVolume:
         self._frame = torch.tensor([*origin.tolist(), voxel], dtype=torch.float64)          # host arguments of the kernels
         self._dims = torch.tensor(nb.tolist(), dtype=torch.int32)
 
-    def _stream(self):
-        return torch.cuda.current_stream(self.device).cuda_stream
-
     def integrate(self, depths: Tensor, masks: Tensor, images: Tensor, cams: Tensor, chunk: int = CHUNK_VIEWS) -> None:
         """Add views in the order given: depths [V,h,w] float32, masks [V,h,w] (bool, uint8 or float: non-zero keeps the
         pixel), images [V,h,w,3] uint8, all on the volume's device; cams [V,2,4,4] float32 (extrinsic; intrinsic in [:3,:3]),
@@ -190,7 +202,7 @@ class TsdfVolume:
                                                  self.trunc, depths.data_ptr() + 4 * v0 * hw, masks.data_ptr() + v0 * hw,
                                                  images.data_ptr() + 3 * v0 * hw, tab.data_ptr() + 8 * 24 * v0, nv, h, w,
                                                  self.sum.data_ptr(), self.n.data_ptr(), self.nc.data_ptr(), self.rgb.data_ptr(),
-                                                 self._stream()), "cds_tsdf_integrate_f32")
+                                                 _stream(self.device)), "cds_tsdf_integrate_f32")
 
     def extract(self, min_weight: int = 2) -> Dict[str, Tensor]:
         """The zero level set over the cubes whose eight corners were seen at least ``min_weight`` times
@@ -198,10 +210,8 @@ class TsdfVolume:
         if int(min_weight) < 1:
             raise ValueError(f"TsdfVolume.extract: min_weight must be >= 1, got {min_weight}")
         dev, k = self.device, self.n_blocks
-        empty = {"vertices": torch.zeros((0, 3), dtype=torch.float32, device=dev),
-                 "colors": torch.zeros((0, 3), dtype=torch.uint8, device=dev), "faces": torch.zeros((0, 3), dtype=torch.int32, device=dev)}
         if k == 0:
-            return empty
+            return _empty_mesh(dev)
         lib = _lib.load()
         vmask = torch.empty((k, 512), dtype=torch.uint8, device=dev)
         tcount = torch.empty((k, 512), dtype=torch.uint8, device=dev)
@@ -211,41 +221,48 @@ class TsdfVolume:
         with torch.cuda.device(dev):
             check(lib.cds_tsdf_classify(self.keys.data_ptr(), self.table.data_ptr(), k, *frame, self.sum.data_ptr(), self.n.data_ptr(),
                                         int(min_weight), vmask.data_ptr(), tcount.data_ptr(), bv.data_ptr(), bt.data_ptr(),
-                                        self._stream()), "cds_tsdf_classify")
+                                        _stream(self.device)), "cds_tsdf_classify")
             ends = torch.stack([torch.cumsum(bv, 0, dtype=torch.int64), torch.cumsum(bt, 0, dtype=torch.int64)])
             nv, nf = (int(x) for x in ends[:, -1].cpu())
             if nv >= 2 ** 31 or nf >= 2 ** 31:
                 raise ValueError(f"TsdfVolume.extract: {nv} vertices and {nf} faces, at most 2^31 - 1 each: raise --mesh_voxel")
             if nv == 0:
-                return empty
+                return _empty_mesh(dev)
             vfirst = (ends[0] - bv).to(torch.int32)
             tfirst = (ends[1] - bt).to(torch.int32)
             vstart = torch.empty((k, 512), dtype=torch.int32, device=dev)
-            out = {"vertices": torch.empty((nv, 3), dtype=torch.float32, device=dev),
-                   "colors": torch.empty((nv, 3), dtype=torch.uint8, device=dev),
-                   "faces": torch.empty((nf, 3), dtype=torch.int32, device=dev)}
+            out = _empty_mesh(dev, nv, nf)
             check(lib.cds_tsdf_emit(self.keys.data_ptr(), self.table.data_ptr(), k, *frame, self.sum.data_ptr(), self.n.data_ptr(),
                                     self.nc.data_ptr(), self.rgb.data_ptr(), vmask.data_ptr(), tcount.data_ptr(), vfirst.data_ptr(),
                                     tfirst.data_ptr(), nv, nf, vstart.data_ptr(), out["vertices"].data_ptr(), out["colors"].data_ptr(),
-                                    out["faces"].data_ptr() if nf else None, self._stream()), "cds_tsdf_emit")
+                                    out["faces"].data_ptr() if nf else None, _stream(self.device)), "cds_tsdf_emit")
         return out
 
 
 # -------------------------------------------------------------------------------------------------------------- components
-def _check_faces(faces, n_vertices, what: str) -> int:
-    """The checks of a face list, in the order of render_mesh: layout (ValueError), device (RuntimeError), index range (ValueError)."""
+def _check_faces_layout(faces, what: str) -> None:
     if not isinstance(faces, torch.Tensor) or faces.dim() != 2 or faces.shape[1] != 3 or faces.dtype != torch.int32:
         raise ValueError(f"{what}: faces must be an int32 [F,3] tensor, got {getattr(faces, 'dtype', type(faces))} "
                          f"{tuple(getattr(faces, 'shape', ()))}")
+
+
+def _check_index_range(faces: Tensor, nv: int, what: str) -> None:
+    if faces.shape[0]:
+        lo, hi = (int(x) for x in torch.aminmax(faces))
+        if lo < 0 or hi >= nv:
+            raise ValueError(f"{what}: faces index outside the {nv} vertices ({lo}..{hi})")
+
+
+def _check_faces(faces, n_vertices, what: str) -> int:
+    """The checks of a face list alone, in the order of a mesh's: layout (ValueError), device (RuntimeError), index range
+    (ValueError) -> V."""
+    _check_faces_layout(faces, what)
     nv = int(n_vertices)
     if not (0 <= nv < 2 ** 31):
         raise ValueError(f"{what}: {n_vertices} vertices, 0 .. 2^31 - 1 expected")
     if not faces.is_cuda:
         raise RuntimeError(f"{what}: faces must be a ROCm (cuda) tensor; there is no CPU fallback")
-    if faces.shape[0]:
-        lo, hi = (int(x) for x in torch.aminmax(faces))
-        if lo < 0 or hi >= nv:
-            raise ValueError(f"{what}: faces index outside the {nv} vertices ({lo}..{hi})")
+    _check_index_range(faces, nv, what)
     return nv
 
 
@@ -259,7 +276,7 @@ def _labels(faces: Tensor, nv: int):
     count = torch.zeros(nv, dtype=torch.int32, device=dev)
     changed = torch.zeros(MAX_ROUNDS, dtype=torch.int32, device=dev)       # one word per round, zeroed once
     with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
+        stream = _stream(dev)
         check(lib.cds_mesh_cc_init(parent.data_ptr(), nv, stream), "cds_mesh_cc_init")
         rounds = 0
         while True:
@@ -302,24 +319,48 @@ def select_components(counts: Tensor, min_faces: int = 0, keep_largest: int = 0)
     return keep
 
 
-def _check_mesh(mesh_dict, what: str):
-    """The checks of a mesh dict: layouts (ValueError), device (RuntimeError), index range (ValueError) -> (vertices, colors,
-    faces, V, device)."""
-    vert, col, faces = mesh_dict["vertices"], mesh_dict["colors"], mesh_dict["faces"]
+def check_mesh_layout(vert, col, faces, what: str) -> int:
+    """The first half of a mesh's checks, the layouts (ValueError): vertices float32 [V,3], colors uint8 [V,3] or None, faces int32
+    [F,3] -> V.  render.render_mesh makes its own checks between the two halves."""
     if not isinstance(vert, torch.Tensor) or vert.dim() != 2 or vert.shape[1] != 3 or vert.dtype != torch.float32:
         raise ValueError(f"{what}: vertices must be a float32 [V,3] tensor, got {getattr(vert, 'dtype', type(vert))} "
                          f"{tuple(getattr(vert, 'shape', ()))}")
     nv = int(vert.shape[0])
-    if not isinstance(col, torch.Tensor) or tuple(col.shape) != (nv, 3) or col.dtype != torch.uint8:
+    if col is not None and (not isinstance(col, torch.Tensor) or tuple(col.shape) != (nv, 3) or col.dtype != torch.uint8):
         raise ValueError(f"{what}: colors must be a uint8 [{nv},3] tensor, got {getattr(col, 'dtype', type(col))} "
                          f"{tuple(getattr(col, 'shape', ()))}")
+    _check_faces_layout(faces, what)
+    return nv
+
+
+def check_mesh_device(vert: Tensor, col: Optional[Tensor], faces: Tensor, what: str):
+    """The second half: one ROCm device (RuntimeError), then every index of faces inside the vertices (ValueError) -> device."""
     if not vert.is_cuda:
         raise RuntimeError(f"{what}: vertices must be a ROCm (cuda) tensor; there is no CPU fallback")
-    _check_faces(faces, nv, what)
     dev = vert.device
-    if col.device != dev or faces.device != dev:
-        raise RuntimeError(f"{what}: colors and faces must be on {dev}; there is no CPU fallback")
-    return vert, col, faces, nv, dev
+    for t, name in ((faces, "faces"), (col, "colors")):
+        if t is not None and t.device != dev:
+            raise RuntimeError(f"{what}: {name} must be on {dev}; there is no CPU fallback")
+    _check_index_range(faces, int(vert.shape[0]), what)
+    return dev
+
+
+def _check_mesh(mesh_dict, what: str):
+    """The checks of a mesh dict -> (vertices, colors, faces, V, device)."""
+    vert, col, faces = mesh_dict["vertices"], mesh_dict["colors"], mesh_dict["faces"]
+    nv = check_mesh_layout(vert, col, faces, what)
+    return vert, col, faces, nv, check_mesh_device(vert, col, faces, what)
+
+
+def _kept_rows(vkeep: Tensor, fkeep: Tensor, own):
+    """What follows a mark kernel.  vkeep uint8 [V], fkeep uint8 [F]: the keep flags; own: device scalars of the caller's, read
+    with the two counts in ONE transfer -> ([kept vertices, kept faces, *own] as ints; None when no vertex is kept, else
+    (vertex_new, face_new: the exclusive prefix sums of the flags as int32, the mesh dict to gather into))."""
+    vend, fend = torch.cumsum(vkeep, 0, dtype=torch.int64), torch.cumsum(fkeep, 0, dtype=torch.int64)
+    n = [int(x) for x in torch.stack([vend[-1], fend[-1], *own]).cpu()]
+    if n[0] == 0:
+        return n, None
+    return n, ((vend - vkeep).to(torch.int32), (fend - fkeep).to(torch.int32), _empty_mesh(vkeep.device, n[0], n[1]))
 
 
 def clean_mesh(mesh_dict: Dict[str, Tensor], min_faces: int = 0, keep_largest: int = 0):
@@ -335,10 +376,8 @@ def clean_mesh(mesh_dict: Dict[str, Tensor], min_faces: int = 0, keep_largest: i
         raise ValueError(f"{what}: min_faces and keep_largest must be >= 0, got {min_faces} and {keep_largest}")
     vert, col, faces, nv, dev = _check_mesh(mesh_dict, what)
     nf = int(faces.shape[0])
-    empty = {"vertices": torch.zeros((0, 3), dtype=torch.float32, device=dev),
-             "colors": torch.zeros((0, 3), dtype=torch.uint8, device=dev), "faces": torch.zeros((0, 3), dtype=torch.int32, device=dev)}
     if nv == 0 or nf == 0:                                                   # no face: no vertex is in a kept face
-        return empty, {"components": (nv, 0), "vertices": (nv, 0), "faces": (0, 0), "largest": 0, "rounds": 0}
+        return _empty_mesh(dev), {"components": (nv, 0), "vertices": (nv, 0), "faces": (0, 0), "largest": 0, "rounds": 0}
     vert, col, faces = vert.contiguous(), col.contiguous(), faces.contiguous()
     label, count, rounds = _labels(faces, nv)
     comps = torch.nonzero(label == torch.arange(nv, dtype=torch.int32, device=dev)).reshape(-1)
@@ -350,20 +389,15 @@ def clean_mesh(mesh_dict: Dict[str, Tensor], min_faces: int = 0, keep_largest: i
     vkeep = torch.zeros(nv, dtype=torch.uint8, device=dev)
     lib = _lib.load()
     with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
+        stream = _stream(dev)
         check(lib.cds_mesh_cc_mark(faces.data_ptr(), nf, nv, label.data_ptr(), keep.data_ptr(), fkeep.data_ptr(), vkeep.data_ptr(),
                                    stream), "cds_mesh_cc_mark")
-        vend, fend = torch.cumsum(vkeep, 0, dtype=torch.int64), torch.cumsum(fkeep, 0, dtype=torch.int64)
-        nv_out, nf_out, n_comp, largest = (int(x) for x in torch.stack(
-            [vend[-1], fend[-1], (kept & (counts > 0)).sum(), counts.max()]).cpu())
+        (nv_out, nf_out, n_comp, largest), rows = _kept_rows(vkeep, fkeep, ((kept & (counts > 0)).sum(), counts.max()))
         info = {"components": (int(comps.numel()), n_comp), "vertices": (nv, nv_out), "faces": (nf, nf_out), "largest": largest,
                 "rounds": rounds}
-        if nv_out == 0:
-            return empty, info
-        vnew, fnew = (vend - vkeep).to(torch.int32), (fend - fkeep).to(torch.int32)
-        out = {"vertices": torch.empty((nv_out, 3), dtype=torch.float32, device=dev),
-               "colors": torch.empty((nv_out, 3), dtype=torch.uint8, device=dev),
-               "faces": torch.empty((nf_out, 3), dtype=torch.int32, device=dev)}
+        if rows is None:
+            return _empty_mesh(dev), info
+        vnew, fnew, out = rows
         check(lib.cds_mesh_cc_gather(vert.data_ptr(), col.data_ptr(), faces.data_ptr(), nv, nf, vkeep.data_ptr(), vnew.data_ptr(),
                                      fkeep.data_ptr(), fnew.data_ptr(), nv_out, nf_out, out["vertices"].data_ptr(),
                                      out["colors"].data_ptr(), out["faces"].data_ptr(), stream), "cds_mesh_cc_gather")
@@ -373,13 +407,7 @@ def clean_mesh(mesh_dict: Dict[str, Tensor], min_faces: int = 0, keep_largest: i
 # ---------------------------------------------------------------------------------------------------------- simplification
 def check_cell(cell, what: str = "simplify_mesh") -> float:
     """-> cell as a float; ValueError unless it is finite and > 0."""
-    try:
-        size = float(cell)
-    except (TypeError, ValueError):
-        size = math.nan
-    if not (size > 0 and math.isfinite(size)):
-        raise ValueError(f"{what}: cell must be positive, got {cell}")
-    return size
+    return _positive(cell, "cell", what)
 
 
 def _first_of_identity(ident: Tensor, n_clusters: int) -> Tensor:
@@ -411,7 +439,7 @@ def _clusters(vert: Tensor, col: Tensor, faces: Tensor, cell: float, placement: 
     from .pointcloud import pack_colors, voxel_groups
     dev, nv, nf = vert.device, int(vert.shape[0]), int(faces.shape[0])
     lib = _lib.load()
-    stream = torch.cuda.current_stream(dev).cuda_stream
+    stream = _stream(dev)
     perm, start, ukeys, counts = voxel_groups(vert, cell, "simplify_mesh")   # ValueError for a vertex that is not finite
     nc = int(ukeys.numel())
     cluster = torch.empty(nv, dtype=torch.int32, device=dev)
@@ -453,16 +481,14 @@ def simplify_mesh(mesh_dict: Dict[str, Tensor], cell: float, placement: str = "q
         raise ValueError(f"{what}: placement must be one of {PLACEMENTS}, got {placement!r}")
     vert, col, faces, nv, dev = _check_mesh(mesh_dict, what)
     nf = int(faces.shape[0])
-    empty = {"vertices": torch.zeros((0, 3), dtype=torch.float32, device=dev),
-             "colors": torch.zeros((0, 3), dtype=torch.uint8, device=dev), "faces": torch.zeros((0, 3), dtype=torch.int32, device=dev)}
     if nv == 0 or nf == 0:                                                   # no face: no cluster is in a surviving face
-        return empty, {"vertices": (nv, 0), "faces": (0, 0), "clusters": 0, "collapsed": 0, "duplicates": 0, "fallback": 0}
+        return _empty_mesh(dev), {"vertices": (nv, 0), "faces": (0, 0), "clusters": 0, "collapsed": 0, "duplicates": 0, "fallback": 0}
     if 3 * nf >= 2 ** 31:
         raise ValueError(f"{what}: {nf} faces, at most {(2 ** 31 - 1) // 3}")
     vert, col, faces = vert.contiguous(), col.contiguous(), faces.contiguous()
     lib = _lib.load()
     with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
+        stream = _stream(dev)
         nc, pos, packed, fell, fclus, gone, ident = _clusters(vert, col, faces, cell, placement)
         n_fell = fell.sum() if fell is not None else torch.zeros((), dtype=torch.int64, device=dev)
         alive = torch.nonzero(gone == 0).reshape(-1)
@@ -472,16 +498,12 @@ def simplify_mesh(mesh_dict: Dict[str, Tensor], cell: float, placement: str = "q
         ckeep = torch.zeros(nc, dtype=torch.uint8, device=dev)
         check(lib.cds_mesh_simplify_mark(fclus.data_ptr(), fkeep.data_ptr(), nf, nc, ckeep.data_ptr(), stream),
               "cds_mesh_simplify_mark")
-        cend, fend = torch.cumsum(ckeep, 0, dtype=torch.int64), torch.cumsum(fkeep, 0, dtype=torch.int64)
-        nv_out, nf_out, n_gone, n_fell = (int(x) for x in torch.stack([cend[-1], fend[-1], gone.sum(), n_fell]).cpu())
+        (nv_out, nf_out, n_gone, n_fell), rows = _kept_rows(ckeep, fkeep, (gone.sum(), n_fell))
         info = {"vertices": (nv, nv_out), "faces": (nf, nf_out), "clusters": nc, "collapsed": n_gone,
                 "duplicates": nf - n_gone - nf_out, "fallback": n_fell}
-        if nv_out == 0:
-            return empty, info
-        cnew, fnew = (cend - ckeep).to(torch.int32), (fend - fkeep).to(torch.int32)
-        out = {"vertices": torch.empty((nv_out, 3), dtype=torch.float32, device=dev),
-               "colors": torch.empty((nv_out, 3), dtype=torch.uint8, device=dev),
-               "faces": torch.empty((nf_out, 3), dtype=torch.int32, device=dev)}
+        if rows is None:
+            return _empty_mesh(dev), info
+        cnew, fnew, out = rows
         check(lib.cds_mesh_simplify_gather(pos.data_ptr(), packed.data_ptr(), nc, ckeep.data_ptr(), cnew.data_ptr(), fclus.data_ptr(),
                                            nf, fkeep.data_ptr(), fnew.data_ptr(), nv_out, nf_out, out["vertices"].data_ptr(),
                                            out["colors"].data_ptr(), out["faces"].data_ptr(), stream), "cds_mesh_simplify_gather")
@@ -491,13 +513,7 @@ def simplify_mesh(mesh_dict: Dict[str, Tensor], cell: float, placement: str = "q
 # ---------------------------------------------------------------------------------------------------------------- sampling
 def check_spacing(spacing, what: str = "sample_mesh") -> float:
     """-> spacing as a float; ValueError unless it is finite and > 0."""
-    try:
-        size = float(spacing)
-    except (TypeError, ValueError):
-        size = math.nan
-    if not (size > 0 and math.isfinite(size)):
-        raise ValueError(f"{what}: spacing must be positive, got {spacing}")
-    return size
+    return _positive(spacing, "spacing", what)
 
 
 def sample_mesh(mesh_dict: Dict[str, Tensor], spacing: float, max_points: int = MAX_SAMPLES):
@@ -520,7 +536,7 @@ def sample_mesh(mesh_dict: Dict[str, Tensor], spacing: float, max_points: int = 
     vert, col, faces = vert.contiguous(), col.contiguous(), faces.contiguous()
     lib = _lib.load()
     with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
+        stream = _stream(dev)
         n = torch.empty(nf, dtype=torch.int32, device=dev)
         n2 = torch.empty(nf, dtype=torch.int64, device=dev)
         check(lib.cds_mesh_sample_count(vert.data_ptr(), nv, faces.data_ptr(), nf, spacing, n.data_ptr(), n2.data_ptr(), stream),
@@ -663,6 +679,21 @@ def _check_simplify(simplify, placement, what: str) -> float:
     return check_cell(simplify, what)
 
 
+def _finish(mesh, plyfilename: str, clean, simplify: float, placement: str, sample: float, surface_ply) -> Dict[str, object]:
+    """The way of an extracted or loaded mesh into its files: :func:`clean_mesh` with ``clean`` = (min_component, keep_largest)
+    unless it is None, :func:`simplify_mesh` when ``simplify`` > 0, the mesh PLY, and when ``sample`` > 0 the sampled surface at
+    ``surface_ply`` -> {"vertices", "faces", "mesh": the mesh written, on the device[, "clean"][, "simplify"][, "sample"]}."""
+    out = {}
+    if clean is not None:
+        mesh, out["clean"] = clean_mesh(mesh, *clean)
+    if simplify > 0:
+        mesh, out["simplify"] = simplify_mesh(mesh, simplify, placement)
+    write_mesh_ply(plyfilename, mesh["vertices"].cpu().numpy(), mesh["colors"].cpu().numpy(), mesh["faces"].cpu().numpy())
+    if sample > 0:
+        out["sample"] = dict(write_surface_ply(surface_ply, mesh, sample), spacing=sample)
+    return dict(out, vertices=int(mesh["vertices"].shape[0]), faces=int(mesh["faces"].shape[0]), mesh=mesh)
+
+
 def mesh_scan(pair_folder: str, scan_folder: str, plyfilename: str, voxel: float, trunc: Optional[float] = None, min_weight: int = 2,
               method: str = "normal", cloud_ply: Optional[str] = None, device: str = "cuda", min_component: int = 0,
               keep_largest: int = 0, simplify: float = 0.0, placement: str = "quadric", sample: float = 0.0,
@@ -691,21 +722,8 @@ def mesh_scan(pair_folder: str, scan_folder: str, plyfilename: str, voxel: float
     views: list = []
     cloud = filter_depth(pair_folder, scan_folder, cloud_ply, device=device, method=method, collect=views, **fusion_options)
     mesh, vol = mesh_views(views, voxel, trunc, min_weight, device)
-    cleaned = simplified = None
-    if int(min_component) > 0 or int(keep_largest) > 0:
-        mesh, cleaned = clean_mesh(mesh, min_component, keep_largest)
-    if simplify > 0:
-        mesh, simplified = simplify_mesh(mesh, simplify, placement)
-    write_mesh_ply(plyfilename, mesh["vertices"].cpu().numpy(), mesh["colors"].cpu().numpy(), mesh["faces"].cpu().numpy())
-    out = {"vertices": int(mesh["vertices"].shape[0]), "faces": int(mesh["faces"].shape[0]), "blocks": vol.n_blocks, "cloud": cloud,
-           "mesh": mesh}
-    if cleaned is not None:
-        out["clean"] = cleaned
-    if simplified is not None:
-        out["simplify"] = simplified
-    if sample > 0:
-        out["sample"] = dict(write_surface_ply(surface_ply, mesh, sample), spacing=sample)
-    return out
+    clean = (min_component, keep_largest) if int(min_component) > 0 or int(keep_largest) > 0 else None
+    return dict(_finish(mesh, plyfilename, clean, simplify, placement, sample, surface_ply), blocks=vol.n_blocks, cloud=cloud)
 
 
 def clean_file(src_ply: str, dst_ply: str, min_component: int = 0, keep_largest: int = 0, device: str = "cuda",
@@ -720,15 +738,8 @@ def clean_file(src_ply: str, dst_ply: str, min_component: int = 0, keep_largest:
     sample = _check_sample(sample, surface_ply, "clean_file")
     dev = torch.device(device)
     v, c, f = (torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in read_mesh_ply(src_ply))
-    mesh, out = {"vertices": v, "colors": c, "faces": f}, {}
-    if simplify == 0 or int(min_component) > 0 or int(keep_largest) > 0:
-        mesh, out["clean"] = clean_mesh(mesh, min_component, keep_largest)
-    if simplify > 0:
-        mesh, out["simplify"] = simplify_mesh(mesh, simplify, placement)
-    write_mesh_ply(dst_ply, mesh["vertices"].cpu().numpy(), mesh["colors"].cpu().numpy(), mesh["faces"].cpu().numpy())
-    if sample > 0:
-        out["sample"] = dict(write_surface_ply(surface_ply, mesh, sample), spacing=sample)
-    return dict(out, vertices=int(mesh["vertices"].shape[0]), faces=int(mesh["faces"].shape[0]), mesh=mesh)
+    clean = (min_component, keep_largest) if simplify == 0 or int(min_component) > 0 or int(keep_largest) > 0 else None
+    return _finish({"vertices": v, "colors": c, "faces": f}, dst_ply, clean, simplify, placement, sample, surface_ply)
 
 
 def format_mesh(info: Dict[str, object]) -> str:
@@ -781,17 +792,16 @@ def check_clean_args(ap: argparse.ArgumentParser, args, allowed: bool) -> None:
                  f"{args.mesh_keep_largest}")
     if not allowed and (args.mesh_min_component or args.mesh_keep_largest):
         ap.error("--mesh_min_component and --mesh_keep_largest clean the mesh of --mesh_voxel: give --mesh_voxel SIZE as well")
-    if args.mesh_simplify is not None:
-        if not (args.mesh_simplify > 0 and math.isfinite(args.mesh_simplify)):
-            ap.error(f"--mesh_simplify must be positive, got {args.mesh_simplify}")
+    for option, does in (("mesh_simplify", "simplifies"), ("mesh_sample", "samples")):
+        value = getattr(args, option)
+        if value is None:
+            continue
+        try:
+            _positive(value, "--" + option)
+        except ValueError as e:
+            ap.error(str(e))
         if not allowed:
-            ap.error("--mesh_simplify simplifies the mesh of --mesh_voxel: give --mesh_voxel SIZE (or, in mesh, --from_mesh FILE) "
-                     "as well")
-    if args.mesh_sample is not None:
-        if not (args.mesh_sample > 0 and math.isfinite(args.mesh_sample)):
-            ap.error(f"--mesh_sample must be positive, got {args.mesh_sample}")
-        if not allowed:
-            ap.error("--mesh_sample samples the mesh of --mesh_voxel: give --mesh_voxel SIZE (or, in mesh, --from_mesh FILE) as well")
+            ap.error(f"--{option} {does} the mesh of --mesh_voxel: give --mesh_voxel SIZE (or, in mesh, --from_mesh FILE) as well")
 
 
 def main(argv=None) -> Dict[str, Dict[str, object]]:

@@ -27,6 +27,7 @@ import torch
 
 from . import _lib
 from ._lib import check
+from .mesh import check_mesh_device, check_mesh_layout
 
 Tensor = torch.Tensor
 
@@ -67,19 +68,10 @@ def render_mesh(vertices: Tensor, faces: Tensor, cams: Tensor, h: int, w: int, c
     """vertices float32 [NV,3], faces int32 [NF,3], optional colors uint8 [NV,3], all on one ROCm device; cams [V,2,4,4] on any
     device -> {"depth" float32, "face" int32, "front" uint8, "valid" uint8 [V,h,w][, "image" uint8 [V,h,w,3]]} on that device.
     ``chunk`` views go into one launch (1..32); a face with more than ``large_px`` candidate pixels is drawn by a wave instead of
-    a thread.  The result depends on neither."""
+    a thread.  The result depends on neither.  The mesh is checked as the mesh stage checks it (mesh.check_mesh_layout, then the
+    arguments of this function, then mesh.check_mesh_device)."""
     what = "render_mesh"
-    if not isinstance(vertices, torch.Tensor) or vertices.dim() != 2 or vertices.shape[1] != 3 or vertices.dtype != torch.float32:
-        raise ValueError(f"{what}: vertices must be a float32 [NV,3] tensor, got {getattr(vertices, 'dtype', type(vertices))} "
-                         f"{tuple(getattr(vertices, 'shape', ()))}")
-    if not isinstance(faces, torch.Tensor) or faces.dim() != 2 or faces.shape[1] != 3 or faces.dtype != torch.int32:
-        raise ValueError(f"{what}: faces must be an int32 [NF,3] tensor, got {getattr(faces, 'dtype', type(faces))} "
-                         f"{tuple(getattr(faces, 'shape', ()))}")
-    nv_mesh, nf = int(vertices.shape[0]), int(faces.shape[0])
-    if colors is not None and (not isinstance(colors, torch.Tensor) or tuple(colors.shape) != (nv_mesh, 3) or
-                               colors.dtype != torch.uint8):
-        raise ValueError(f"{what}: colors must be a uint8 [{nv_mesh},3] tensor, got {getattr(colors, 'dtype', type(colors))} "
-                         f"{tuple(getattr(colors, 'shape', ()))}")
+    nv_mesh, nf = check_mesh_layout(vertices, colors, faces, what), int(faces.shape[0])
     if not isinstance(cams, torch.Tensor) or cams.dim() != 4 or tuple(cams.shape[1:]) != (2, 4, 4):
         raise ValueError(f"{what}: cams must be [V,2,4,4], got {tuple(getattr(cams, 'shape', ()))}")
     h, w, chunk, large_px = int(h), int(w), int(chunk), int(large_px)
@@ -89,17 +81,8 @@ def render_mesh(vertices: Tensor, faces: Tensor, cams: Tensor, h: int, w: int, c
         raise ValueError(f"{what}: chunk must lie in 1..{MAX_CHUNK}, got {chunk}")
     if large_px < 1:
         raise ValueError(f"{what}: large_px must be >= 1, got {large_px}")
-    if not vertices.is_cuda:
-        raise RuntimeError(f"{what}: vertices must be a ROCm (cuda) tensor; there is no CPU fallback")
-    dev = vertices.device
-    for t, name in ((faces, "faces"), (colors, "colors")):
-        if t is not None and t.device != dev:
-            raise RuntimeError(f"{what}: {name} must be on {dev}; there is no CPU fallback")
     tab = camera_table(cams)
-    if nf:
-        lo, hi = (int(x) for x in torch.aminmax(faces))
-        if lo < 0 or hi >= nv_mesh:
-            raise ValueError(f"{what}: faces index outside the {nv_mesh} vertices ({lo}..{hi})")
+    dev = check_mesh_device(vertices, colors, faces, what)
     v = int(tab.shape[0])
     out = {name: torch.zeros((v, h, w), dtype=dt, device=dev) for name, dt in OUTPUTS}
     out["face"].fill_(-1)

@@ -813,7 +813,8 @@ int cds_mesh_cc_gather(const float* vertices, const unsigned char* colors, const
  *   face_keep != 0.
  * cds_mesh_simplify_gather: rule 6.  positions float32 [n_clusters][3]; colors: the packed words of cds_voxel_merge_f32, or null
  *   (then colors_out is not written); cluster_new / face_new: the exclusive prefix sums of cluster_keep / face_keep, int32;
- *   out_vertices / out_faces their totals.
+ *   out_vertices / out_faces their totals.  It is cds_mesh_cc_gather's rule 5 with positions as vertices, face_clusters as
+ *   faces and n_clusters as n_vertices: one kernel serves both, and only the colour source differs.
  *   CDS_EINVAL: a count < 0 or >= 2^31; 3 n_faces >= 2^31 (quadric); n_clusters > n_vertices; cell not finite or <= 0; a total
  *   larger than its input; a null required pointer (an empty input or output returns 0 first).
  */

@@ -276,6 +276,92 @@ def test_entry_points_skip_what_the_wrapper_never_sends():
     torch.cuda.synchronize()
 
 
+SENTINEL = 0xA5                                                          # every byte of an output before a gather
+
+
+def _gather_case(case):
+    """-> (vertex bits uint32 [V,3], colours uint8 [V,3], faces int32 [F,3], vertex keep uint8 [V], face keep uint8 [F]).  "a": the
+    8 vertices and six faces of test_entry_points_skip_what_the_wrapper_never_sends, all flagged kept; "b": 257 vertices and 300
+    random faces with three faces outside the vertices put in, random flags: the first face item is thread 1 of the second of
+    three workgroups.  A vertex is kept iff a kept face inside the vertices holds it."""
+    rng = np.random.default_rng(17)
+    if case == "a":
+        nv = 8
+        faces = np.array([[0, 1, 2], [7, 8, 1], [4, 5, 6], [-1, 0, 4], [2, 3, 3], [0, 4, 2 ** 31 - 1]], np.int32)
+        fkeep = np.ones(len(faces), np.uint8)
+    else:
+        nv = 257
+        faces = rng.integers(0, nv, (303, 3)).astype(np.int32)
+        faces[[5, 256, 302]] = [[3, nv, 9], [-1, 0, 4], [0, 4, 2 ** 31 - 1]]
+        fkeep = rng.integers(0, 2, len(faces)).astype(np.uint8)
+        fkeep[[5, 302]] = 1                                                # flagged and outside the vertices: skipped all the same
+    inside = ((faces >= 0) & (faces < nv)).all(1)
+    assert (~inside).sum() == 3
+    vkeep = np.zeros(nv, np.uint8)
+    vkeep[faces[inside & (fkeep != 0)].reshape(-1)] = 1
+    assert 0 < vkeep.sum() < nv and 0 < fkeep.sum()
+    bits = rng.normal(size=(nv, 3)).astype(np.float32).view(np.uint32).copy()
+    bits[np.nonzero(vkeep)[0][0]] = [0x80000000, 0x7f800000, 0xffc12345]   # -0.0, an infinity, a NaN with a payload
+    return bits, rng.integers(0, 256, (nv, 3)).astype(np.uint8), faces, vkeep, fkeep
+
+
+def _numpy_gather(bits, col, faces, vkeep, fkeep):
+    """The compaction in numpy, into arrays of the input's size filled with the sentinel -> (vertex bits, colours, faces, kept
+    vertices, kept flags of faces, vertex_new, face_new)."""
+    nv, nf = len(bits), len(faces)
+    vnew = (np.cumsum(vkeep) - vkeep).astype(np.int32)
+    fnew = (np.cumsum(fkeep) - fkeep).astype(np.int32)
+    want_v = np.full((nv, 3), SENTINEL * 0x01010101, np.uint32)
+    want_c = np.full((nv, 3), SENTINEL, np.uint8)
+    want_f = np.full((nf, 3), SENTINEL, np.uint8).repeat(4, 1).view(np.int32)
+    kept = np.nonzero(vkeep)[0]
+    want_v[:len(kept)], want_c[:len(kept)] = bits[kept], col[kept]
+    for f in np.nonzero(fkeep)[0]:
+        if (faces[f] >= 0).all() and (faces[f] < nv).all():               # else the row of this face keeps the sentinel
+            want_f[fnew[f]] = vnew[faces[f]]
+    return want_v, want_c, want_f, len(kept), int(fkeep.sum()), vnew, fnew
+
+
+@pytest.mark.parametrize("case", ["a", "b"])
+def test_the_two_gathers_are_one_rule(case):
+    """cds_mesh_cc_gather with byte colours and cds_mesh_simplify_gather with the packed words of the same colours (positions =
+    vertices, face_clusters = faces, n_clusters = n_vertices) write the same bytes, those of a numpy gather; the rows of the
+    flagged faces outside the vertices, and everything behind the kept rows, keep the sentinel.  The same without colours."""
+    from cds_mvsnet_amd.pointcloud import pack_colors
+    lib = _lib.load()
+    bits, col, faces, vkeep, fkeep = _gather_case(case)
+    want_v, want_c, want_f, nv_out, nf_out, vnew, fnew = _numpy_gather(bits, col, faces, vkeep, fkeep)
+    nv, nf = len(bits), len(faces)
+    skipped = [int(fnew[f]) for f in np.nonzero(fkeep)[0] if not ((faces[f] >= 0) & (faces[f] < nv)).all()]
+    assert skipped and (want_f[skipped].view(np.uint8) == SENTINEL).all() and (want_f[nf_out:].view(np.uint8) == SENTINEL).all()
+    tv, tc, tf = torch.from_numpy(bits.view(np.float32)).cuda(), torch.from_numpy(col).cuda(), torch.from_numpy(faces).cuda()
+    assert np.array_equal(tv.cpu().numpy().view(np.uint32), bits)        # the upload kept the NaN's payload
+    packed = pack_colors(tc)
+    tvk, tfk = torch.from_numpy(vkeep).cuda(), torch.from_numpy(fkeep).cuda()
+    tvn, tfn = torch.from_numpy(vnew).cuda(), torch.from_numpy(fnew).cuda()
+    for with_colors in (True, False):
+        got = {}
+        for name in ("cc", "simplify"):
+            ov = torch.full((nv, 3), SENTINEL, dtype=torch.uint8, device="cuda").repeat_interleave(4, 1).view(torch.float32)
+            oc = torch.full((nv, 3), SENTINEL, dtype=torch.uint8, device="cuda")
+            of = torch.full((nf, 3), SENTINEL, dtype=torch.uint8, device="cuda").repeat_interleave(4, 1).view(torch.int32)
+            tail = (tvk.data_ptr(), tvn.data_ptr()), (tfk.data_ptr(), tfn.data_ptr(), nv_out, nf_out, ov.data_ptr(),
+                                                      oc.data_ptr() if with_colors else None, of.data_ptr(), None)
+            if name == "cc":
+                rc = lib.cds_mesh_cc_gather(tv.data_ptr(), tc.data_ptr() if with_colors else None, tf.data_ptr(), nv, nf, *tail[0],
+                                            *tail[1])
+            else:
+                rc = lib.cds_mesh_simplify_gather(tv.data_ptr(), packed.data_ptr() if with_colors else None, nv, *tail[0],
+                                                  tf.data_ptr(), nf, *tail[1])
+            assert rc == 0, f"{name}: {rc}"
+            torch.cuda.synchronize()
+            got[name] = (ov.cpu().numpy().view(np.uint32), oc.cpu().numpy(), of.cpu().numpy())
+        for k, (what, want) in enumerate((("vertices", want_v), ("colors", want_c if with_colors else np.full_like(want_c, SENTINEL)),
+                                          ("faces", want_f))):
+            _same(got["cc"][k], got["simplify"][k], f"case {case}, colours {with_colors}: {what} of the two entry points")
+            _same(got["cc"][k], want, f"case {case}, colours {with_colors}: {what} against numpy")
+
+
 def test_two_runs_are_equal():
     f = torch.from_numpy(C.strip(1 << 16, "random", seed=5)).cuda()
     a, b = mesh.mesh_components(f, 1 << 16), mesh.mesh_components(f, 1 << 16)

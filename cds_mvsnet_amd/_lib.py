@@ -148,6 +148,8 @@ SIGNATURES = {
     "cds_depth_normals_f32": [P, P, P, I, I, I, F, I, P, P, P],
     "cds_voxel_merge_f32": [P, P, P, L, P, P, L, P, P, P, P, P],
     "cds_tsdf_integrate_f32": [P, L, P, P, DB, P, P, P, P, I, I, I, P, P, P, P, P],
+    "cds_tsdf_integrate_w_f32": [P, L, P, P, DB, P, P, P, P, I, I, I, P, P, P, P, P, I, F, P, P],
+    "cds_tsdf_view_weights": [P, P, P, P, P, P, I, I, P, P],
     "cds_tsdf_classify": [P, P, L, P, P, P, P, I, P, P, P, P, P],
     "cds_tsdf_emit": [P, P, L, P, P, P, P, P, P, P, P, P, P, L, L, P, P, P, P, P],
     "cds_raster_project": [P, L, P, I, P, P, P],

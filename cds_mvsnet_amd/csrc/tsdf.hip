@@ -2,6 +2,8 @@
 // blocks of 8x8x8 lattice points, and its zero level set as the triangles of the six Freudenthal tetrahedra of every cube.
 //
 //   cds_tsdf_integrate_f32   a chunk of views into the volume
+//   cds_tsdf_integrate_w_f32 the same with a weight per pixel and, optionally, the depth interpolated between pixels (§1.14)
+//   cds_tsdf_view_weights    those weights for one view: viewing angle against the depth map's normals, times a confidence
 //   cds_tsdf_classify        per lattice point: which of its seven edges carry a vertex, how many triangles its cube gives
 //   cds_tsdf_emit            vertices, colours, faces
 //
@@ -131,23 +133,15 @@ __device__ __forceinline__ int block_scan(int v, int* s_wave) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------- integrate
-__global__ __launch_bounds__(512) void tsdf_integrate_kernel(const int* __restrict__ keys, TsdfFrame f, double trunc,
-                                                             const float* __restrict__ depths,
-                                                             const unsigned char* __restrict__ masks,
-                                                             const unsigned char* __restrict__ images,
-                                                             const double* __restrict__ cams, int nv, int h, int w,
-                                                             float* __restrict__ sum, int* __restrict__ n, int* __restrict__ nc,
-                                                             int* __restrict__ rgb, long long n_blocks) {
-  __shared__ double s_cam[kMaxChunk * kCam];
-  __shared__ int s_see[kMaxChunk];
+// The chunk's cameras into LDS, and per view whether it can see block `bp` at all (s_see); ends with a barrier.  Every quantity
+// of the test is linear in the world point, so over the block's bounding sphere it stays within value(centre) +- |gradient| radius.
+// A depth that cds_tsdf_integrate_w_f32 interpolates lies between kept depths of the view, so entry 21 bounds it as well.
+__device__ __forceinline__ void stage_views(const double* __restrict__ cams, int nv, const TsdfFrame& f, BlockPos bp, double trunc,
+                                            int h, int w, double* s_cam, int* s_see) {
   const int tid = threadIdx.x;
-  const long long b = blockIdx.x;
-  const BlockPos bp = block_pos(keys[b], f);
   for (int i = tid; i < nv * kCam; i += kPts) s_cam[i] = cams[i];
   __syncthreads();
   if (tid < nv) {
-    // can view `tid` see the block at all?  Every quantity below is linear in the world point, so over the sphere it stays
-    // within value(centre) +- |gradient| radius.
     const double* c = s_cam + tid * kCam;
     const double C0 = f.origin[0] + ((double)(8 * bp.x) + 3.5) * f.voxel, C1 = f.origin[1] + ((double)(8 * bp.y) + 3.5) * f.voxel,
                  C2 = f.origin[2] + ((double)(8 * bp.z) + 3.5) * f.voxel;
@@ -178,6 +172,21 @@ __global__ __launch_bounds__(512) void tsdf_integrate_kernel(const int* __restri
     s_see[tid] = see ? 1 : 0;
   }
   __syncthreads();
+}
+
+__global__ __launch_bounds__(512) void tsdf_integrate_kernel(const int* __restrict__ keys, TsdfFrame f, double trunc,
+                                                             const float* __restrict__ depths,
+                                                             const unsigned char* __restrict__ masks,
+                                                             const unsigned char* __restrict__ images,
+                                                             const double* __restrict__ cams, int nv, int h, int w,
+                                                             float* __restrict__ sum, int* __restrict__ n, int* __restrict__ nc,
+                                                             int* __restrict__ rgb, long long n_blocks) {
+  __shared__ double s_cam[kMaxChunk * kCam];
+  __shared__ int s_see[kMaxChunk];
+  const int tid = threadIdx.x;
+  const long long b = blockIdx.x;
+  const BlockPos bp = block_pos(keys[b], f);
+  stage_views(cams, nv, f, bp, trunc, h, w, s_cam, s_see);
 
   const int lx = tid & 7, ly = (tid >> 3) & 7, lz = tid >> 6;
   const double X0 = f.origin[0] + (double)(8 * bp.x + lx) * f.voxel, X1 = f.origin[1] + (double)(8 * bp.y + ly) * f.voxel,
@@ -214,6 +223,130 @@ __global__ __launch_bounds__(512) void tsdf_integrate_kernel(const int* __restri
   sum[p] = acc;
   n[p] = cnt; nc[p] = ccnt;
   rgb[p] = cr; rgb[plane + p] = cg; rgb[2 * plane + p] = cb;
+}
+
+__device__ __forceinline__ bool kept_depth(float d) { return d > 0.f && d <= 3.402823466e+38f; }    // false for NaN and +inf
+
+// The weighted rule: tsdf_integrate_kernel with a weight per pixel and, with kInterp, the depth interpolated
+// between the four pixel centres around (u, v) in inverse depth.  The nearest pixel decides as before whether the view counts
+// and gives the weight and the colour; the interpolation only replaces the depth, and only where its four pixels are kept and
+// within `jump` of each other.  `weights` and `wn` are both null or both set (the host checks it).
+template <bool kInterp>
+__global__ __launch_bounds__(512) void tsdf_integrate_w_kernel(const int* __restrict__ keys, TsdfFrame f, double trunc,
+                                                               const float* __restrict__ depths,
+                                                               const unsigned char* __restrict__ masks,
+                                                               const unsigned char* __restrict__ images,
+                                                               const unsigned char* __restrict__ weights, float jump,
+                                                               const double* __restrict__ cams, int nv, int h, int w,
+                                                               float* __restrict__ sum, int* __restrict__ n, int* __restrict__ nc,
+                                                               int* __restrict__ rgb, int* __restrict__ wn, long long n_blocks) {
+  __shared__ double s_cam[kMaxChunk * kCam];
+  __shared__ int s_see[kMaxChunk];
+  const int tid = threadIdx.x;
+  const long long b = blockIdx.x;
+  const BlockPos bp = block_pos(keys[b], f);
+  stage_views(cams, nv, f, bp, trunc, h, w, s_cam, s_see);
+
+  const int lx = tid & 7, ly = (tid >> 3) & 7, lz = tid >> 6;
+  const double X0 = f.origin[0] + (double)(8 * bp.x + lx) * f.voxel, X1 = f.origin[1] + (double)(8 * bp.y + ly) * f.voxel,
+               X2 = f.origin[2] + (double)(8 * bp.z + lz) * f.voxel;
+  const long long p = b * kPts + tid, plane = n_blocks * kPts;
+  float acc = sum[p];
+  int cnt = n[p], ccnt = nc[p], cr = rgb[p], cg = rgb[plane + p], cb = rgb[2 * plane + p];
+  int wcnt = weights ? wn[p] : 0;
+  const size_t hw = (size_t)h * w;
+  for (int v = 0; v < nv; ++v) {
+    if (!s_see[v]) continue;                                           // the same for the whole workgroup
+    const double* c = s_cam + v * kCam;
+    const double xc0 = ((c[0] * X0 + c[1] * X1) + c[2] * X2) + c[9];
+    const double xc1 = ((c[3] * X0 + c[4] * X1) + c[5] * X2) + c[10];
+    const double z = ((c[6] * X0 + c[7] * X1) + c[8] * X2) + c[11];
+    if (!(z > 0.0)) continue;
+    const double p0 = (c[12] * xc0 + c[13] * xc1) + c[14] * z;
+    const double p1 = (c[15] * xc0 + c[16] * xc1) + c[17] * z;
+    const double p2 = (c[18] * xc0 + c[19] * xc1) + c[20] * z;
+    const double pu = p0 / p2, pv = p1 / p2;
+    if (!(pu >= 0.0 && pu < (double)w && pv >= 0.0 && pv < (double)h)) continue;     // false for NaN
+    const size_t q = (size_t)v * hw + (size_t)(int)pv * w + (size_t)(int)pu;         // 0 <= floor < w, h: truncation is floor
+    const float d = depths[q];
+    if (masks[q] == 0 || !kept_depth(d)) continue;
+    const int wq = weights ? (int)weights[q] : 1;
+    if (wq == 0) continue;
+    double dd = (double)d;
+    if (kInterp) {
+      const double a = pu - 0.5, bb = pv - 0.5;                        // >= -0.5: the floors are >= -1
+      const double fa = floor(a), fb = floor(bb);
+      const int x0 = (int)fa, y0 = (int)fb;
+      if (x0 >= 0 && x0 + 1 < w && y0 >= 0 && y0 + 1 < h) {            // the four pixels lie inside the map
+        const size_t q0 = (size_t)v * hw + (size_t)y0 * w + (size_t)x0;
+        const float d00 = depths[q0], d10 = depths[q0 + 1], d01 = depths[q0 + w], d11 = depths[q0 + w + 1];
+        const bool kept = masks[q0] != 0 && masks[q0 + 1] != 0 && masks[q0 + w] != 0 && masks[q0 + w + 1] != 0 &&
+                          kept_depth(d00) && kept_depth(d10) && kept_depth(d01) && kept_depth(d11);
+        const float lo = fminf(fminf(d00, d10), fminf(d01, d11)), hi = fmaxf(fmaxf(d00, d10), fmaxf(d01, d11));
+        if (kept && (double)hi - (double)lo <= (double)jump * (double)lo) {
+          const double fx = a - fa, fy = bb - fb;
+          const double i00 = 1.0 / (double)d00, i10 = 1.0 / (double)d10, i01 = 1.0 / (double)d01, i11 = 1.0 / (double)d11;
+          const double i0 = i00 + fx * (i10 - i00), i1 = i01 + fx * (i11 - i01);
+          dd = 1.0 / (i0 + fy * (i1 - i0));
+        }
+      }
+    }
+    const double sdf = dd - z;
+    if (sdf < -trunc) continue;
+    acc = acc + (float)((double)wq * fmin(1.0, sdf / trunc));
+    ++cnt;
+    wcnt += wq;
+    if (sdf <= trunc) {
+      const unsigned char* px = images + 3 * q;
+      cr += px[0]; cg += px[1]; cb += px[2];
+      ++ccnt;
+    }
+  }
+  sum[p] = acc;
+  n[p] = cnt; nc[p] = ccnt;
+  rgb[p] = cr; rgb[plane + p] = cg; rgb[2 * plane + p] = cb;
+  if (weights) wn[p] = wcnt;
+}
+
+// The weight of every pixel of one view (the rule is in the header): one thread per pixel.
+struct WeightCam {
+  float fx, s, cx, fy, cy, R[9];         // K = [[fx, s, cx], [0, fy, cy], [0, 0, 1]] and the rotation of E, row-major
+};
+
+__global__ __launch_bounds__(256) void tsdf_view_weights_kernel(const float* __restrict__ depth,
+                                                                const unsigned char* __restrict__ mask,
+                                                                const float* __restrict__ normals,
+                                                                const unsigned char* __restrict__ ok,
+                                                                const float* __restrict__ conf, WeightCam cam, int h, int w,
+                                                                unsigned char* __restrict__ weights) {
+  const long long hw = (long long)h * w, p = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (p >= hw) return;
+  if (mask[p] == 0 || !kept_depth(depth[p])) {
+    weights[p] = 0;
+    return;
+  }
+  double a = 1.0;
+  if (normals) {
+    a = 0.0;
+    if (ok[p] != 0) {
+      const int x = (int)(p % w), y = (int)(p / w);
+      const double c1 = (((double)y + 0.5) - (double)cam.cy) / (double)cam.fy;
+      const double c0 = ((((double)x + 0.5) - (double)cam.cx) - (double)cam.s * c1) / (double)cam.fx;
+      const double n0 = (double)normals[p], n1 = (double)normals[hw + p], n2 = (double)normals[2 * hw + p];
+      const double nc0 = ((double)cam.R[0] * n0 + (double)cam.R[1] * n1) + (double)cam.R[2] * n2;
+      const double nc1 = ((double)cam.R[3] * n0 + (double)cam.R[4] * n1) + (double)cam.R[5] * n2;
+      const double nc2 = ((double)cam.R[6] * n0 + (double)cam.R[7] * n1) + (double)cam.R[8] * n2;
+      const double t = -((nc0 * c0 + nc1 * c1) + nc2) / sqrt((c0 * c0 + c1 * c1) + 1.0);
+      a = !(t >= 0.0 && t <= 1.7976931348623157e308) ? 0.0 : t > 1.0 ? 1.0 : t;       // NaN, +-inf and negatives give 0
+    }
+  }
+  double cf = 1.0;
+  if (conf) {
+    const double t = (double)conf[p];
+    cf = !(t >= 0.0) ? 0.0 : t > 1.0 ? 1.0 : t;                        // NaN gives 0
+  }
+  const int wt = (int)floor(255.0 * (a * cf) + 0.5);
+  weights[p] = (unsigned char)(wt < 1 ? 1 : wt > 255 ? 255 : wt);
 }
 
 // ----------------------------------------------------------------------------------------------------------------- classify
@@ -407,6 +540,42 @@ extern "C" int cds_tsdf_integrate_f32(const int* keys, long long n_blocks, const
   if (!keys || !depths || !masks || !images || !cams || !sum || !n || !nc || !rgb) return CDS_EINVAL;
   hipLaunchKernelGGL(tsdf_integrate_kernel, dim3((unsigned)n_blocks), dim3(kPts), 0, (hipStream_t)stream, keys, f, trunc, depths,
                      masks, images, cams, n_views, h, w, sum, n, nc, rgb, n_blocks);
+  return cds_launch_status();
+}
+
+extern "C" int cds_tsdf_integrate_w_f32(const int* keys, long long n_blocks, const double* frame_host, const int* dims_host,
+                                        double trunc, const float* depths, const unsigned char* masks, const unsigned char* images,
+                                        const double* cams, int n_views, int h, int w, float* sum, int* n, int* nc, int* rgb,
+                                        const unsigned char* weights, int interp, float jump, int* wn, void* stream) {
+  TsdfFrame f;
+  if (!frame_from_host(frame_host, dims_host, f) || n_blocks < 0 || n_blocks > CDS_TSDF_MAX_CELLS || n_views < 1 ||
+      n_views > kMaxChunk || h < 1 || w < 1 || (long long)h * w * n_views > 0x7fffffffLL || !(trunc >= f.voxel) ||
+      !(trunc <= 8.0 * f.voxel) || (weights != nullptr) != (wn != nullptr) ||
+      (interp != 0 && !(jump > 0.f && jump <= 3.402823466e+38f)))
+    return CDS_EINVAL;
+  if (n_blocks == 0) return 0;
+  if (!keys || !depths || !masks || !images || !cams || !sum || !n || !nc || !rgb) return CDS_EINVAL;
+  if (interp != 0)
+    hipLaunchKernelGGL(tsdf_integrate_w_kernel<true>, dim3((unsigned)n_blocks), dim3(kPts), 0, (hipStream_t)stream, keys, f, trunc,
+                       depths, masks, images, weights, jump, cams, n_views, h, w, sum, n, nc, rgb, wn, n_blocks);
+  else
+    hipLaunchKernelGGL(tsdf_integrate_w_kernel<false>, dim3((unsigned)n_blocks), dim3(kPts), 0, (hipStream_t)stream, keys, f, trunc,
+                       depths, masks, images, weights, jump, cams, n_views, h, w, sum, n, nc, rgb, wn, n_blocks);
+  return cds_launch_status();
+}
+
+extern "C" int cds_tsdf_view_weights(const float* depth, const unsigned char* mask, const float* normals, const unsigned char* ok,
+                                     const float* conf, const float* cam_host, int h, int w, unsigned char* weights, void* stream) {
+  if (!depth || !mask || !cam_host || !weights || (normals != nullptr) != (ok != nullptr) || h < 1 || w < 1 ||
+      (long long)h * w > 0x7fffffffLL)
+    return CDS_EINVAL;
+  if (!(cam_host[3] == 0.f && cam_host[6] == 0.f && cam_host[7] == 0.f && cam_host[8] == 1.f)) return CDS_EINVAL;
+  WeightCam cam;
+  cam.fx = cam_host[0]; cam.s = cam_host[1]; cam.cx = cam_host[2]; cam.fy = cam_host[4]; cam.cy = cam_host[5];
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < 3; ++c) cam.R[3 * r + c] = cam_host[9 + 4 * r + c];
+  hipLaunchKernelGGL(tsdf_view_weights_kernel, dim3((unsigned)(((long long)h * w + 255) / 256)), dim3(256), 0,
+                     (hipStream_t)stream, depth, mask, normals, ok, conf, cam, h, w, weights);
   return cds_launch_status();
 }
 

@@ -205,7 +205,8 @@ def filter_depth(pair_folder: str, scan_folder: str, plyfilename: str, conf: Seq
 
     ``collect``: a list that receives, per reference view and in ``pair.txt`` order, what a later stage needs of the same pass
     (:func:`cds_mvsnet_amd.mesh.mesh_scan`), all on the device: {"depth" [h,w] the fused depth, "mask" bool [h,w] the
-    fusion mask, "image" uint8 [h,w,3], "cam" [2,4,4] (CPU), "points" [k,3] the kept world points}.  The cloud is written as
+    fusion mask, "image" uint8 [h,w,3], "cam" [2,4,4] (CPU), "points" [k,3] the kept world points, "conf" [h,w] the view's
+    last-stage confidence map, the one of the depth map itself}.  The cloud is written as
     without it; ``plyfilename`` may then be None, and no cloud is written."""
     if method not in ("normal", "dynamic"):
         raise ValueError(f"filter_depth: method must be 'normal' or 'dynamic', got {method!r}")
@@ -251,7 +252,7 @@ def filter_depth(pair_folder: str, scan_folder: str, plyfilename: str, conf: Seq
         img = torch.from_numpy(np.ascontiguousarray(rimg())).to(device)            # [h,w,3]
         if collect is not None:
             collect.append({"depth": out["depth"], "mask": keep, "image": (img * 255).to(torch.uint8), "cam": rcam,
-                            "points": out["points"][:, keep].t().contiguous()})
+                            "points": out["points"][:, keep].t().contiguous(), "conf": rc[-1]})
         if cloud:
             kept = keep.sum()
             if normals:

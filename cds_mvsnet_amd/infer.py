@@ -16,7 +16,8 @@ normal and `--merge_voxel SIZE` (`--merge_min_points K`) merges the scan to one 
 from the same fusion pass (mesh.py); `--mesh_min_component N` / `--mesh_keep_largest K` drop its small connected
 components first and `--mesh_simplify CELL` (`--mesh_simplify_placement quadric|mean`) then merges the vertices
 of every cell of that side into one; `--mesh_sample SPACING` also writes `<out>/<scan>_surface.ply`, the surface
-of that mesh as a cloud.  With `--mesh_voxel`, `--render_mesh` (`--back`, `--max_rel_diff R`, `--save_image`) renders
+of that mesh as a cloud; `--mesh_weight angle|conf|angle_conf` and `--mesh_interp` (`--mesh_interp_jump J`) weigh
+the pixels and interpolate the depth in the integration.  With `--mesh_voxel`, `--render_mesh` (`--back`, `--max_rel_diff R`, `--save_image`) renders
 that mesh into every view, `<out>/<scan>/depth_mesh/%08d.pfm`, and `--export_blended DIR` writes the tree `fit --dataset blended`
 trains from (render.py).
 `--save_stages` also writes the three stages' own depth maps, `<out>/<scan>/depth_stage{1,2,3}/%08d.pfm`, at their resolutions
@@ -239,7 +240,8 @@ def run(args) -> float:
                              os.path.join(args.outdir, f"{scan}_mesh.ply"), args.mesh_voxel, args.mesh_trunc, args.mesh_min_weight,
                              cloud_ply=ply, min_component=args.mesh_min_component, keep_largest=args.mesh_keep_largest,
                              simplify=args.mesh_simplify or 0.0, placement=args.mesh_simplify_placement,
-                             sample=args.mesh_sample or 0.0, surface_ply=os.path.join(args.outdir, f"{scan}_surface.ply"), **kw)
+                             sample=args.mesh_sample or 0.0, surface_ply=os.path.join(args.outdir, f"{scan}_surface.ply"),
+                             weight=args.mesh_weight, interp=args.mesh_interp, interp_jump=args.mesh_interp_jump, **kw)
             print(f"[{rank}] {scan}_mesh.ply: {format_mesh(info)}", flush=True)
             if args.render_mesh:
                 # the mesh just written, from the device tensors, into every view of the scan
@@ -326,7 +328,7 @@ def parse_args(argv=None) -> argparse.Namespace:
                     help="dynamic: a pixel is kept when n views agree at level n for some n in this range")
     from .fusion import add_cloud_args
     add_cloud_args(ap)
-    from .mesh import add_mesh_args, check_clean_args, check_voxel
+    from .mesh import add_mesh_args, check_clean_args, check_voxel, check_weight_args
     add_mesh_args(ap)
     from .render import add_render_args
     ap.add_argument("--render_mesh", action="store_true",
@@ -341,6 +343,7 @@ def parse_args(argv=None) -> argparse.Namespace:
     if args.max_rel_diff is not None and not args.max_rel_diff >= 0:
         ap.error(f"--max_rel_diff must be >= 0, got {args.max_rel_diff}")
     check_clean_args(ap, args, args.mesh_voxel is not None)
+    args.mesh_interp_jump = check_weight_args(ap, args, args.mesh_voxel is not None)
     if args.mesh_voxel is not None:
         if args.filter_method == "gipuma":
             ap.error("--mesh_voxel is not implemented for --filter_method gipuma (its fused point has no single depth map); "

@@ -9,8 +9,9 @@ the blocks out.  There is no CPU path.
 
     python -m cds_mvsnet_amd.mesh --testpath <scenes> --outdir <out> --testlist <list> --mesh_voxel SIZE [--mesh_trunc T]
         [--mesh_min_weight 2] [--mesh_min_component N] [--mesh_keep_largest K] [--mesh_simplify CELL]
-        [--mesh_simplify_placement quadric|mean] [--mesh_sample SPACING] [--filter_method normal|dynamic] [--conf 0,0,0] [--thres_disp 1.0]
-        [--thres_view 3] [--dyn_dist_base 0.25] [--dyn_rel_base 0.000769] [--dyn_views 2,10]
+        [--mesh_simplify_placement quadric|mean] [--mesh_sample SPACING] [--mesh_weight one|angle|conf|angle_conf] [--mesh_interp]
+        [--mesh_interp_jump 0.05] [--filter_method normal|dynamic] [--conf 0,0,0] [--thres_disp 1.0] [--thres_view 3]
+        [--dyn_dist_base 0.25] [--dyn_rel_base 0.000769] [--dyn_views 2,10]
 
 fuses the saved depth maps of ``<out>/<scan>/`` as ``python -m cds_mvsnet_amd.fusion`` does and writes
 ``<out>/<scan>_mesh.ply``.  ``infer ... --fuse --mesh_voxel SIZE`` writes cloud and mesh from one fusion pass.
@@ -32,6 +33,11 @@ collapse or repeat are dropped.  ``--from_mesh FILE --mesh_simplify CELL`` does 
 kernels of ``csrc/mesh_sample.hip``): every face is cut into n^2 congruent sub-triangles with edges of at most SPACING and the
 centroid of each becomes a point, so that every point of the surface lies within 2/3 SPACING of one.  It is what
 ``dtu_eval --sample_faces`` and ``tt_eval --sample_faces`` score instead of a mesh's vertices (:func:`sample_mesh`).
+
+``--mesh_weight angle|conf|angle_conf`` weighs every kept pixel by the cosine between its viewing ray and the normal of its depth
+map, by its confidence, or by both, and ``--mesh_interp`` interpolates the depth between pixels where they belong to one surface
+(``cds_tsdf_view_weights``, ``cds_tsdf_integrate_w_f32``): a pixel seen at a grazing angle no longer pulls the
+surface as hard as one seen head-on.  Without them nothing of that runs and the mesh is what it was.
 """
 from __future__ import annotations
 
@@ -51,6 +57,7 @@ Tensor = torch.Tensor
 MAX_CELLS = 1 << 26            # cells of the dense block table (CDS_TSDF_MAX_CELLS): 256 MiB of int32
 MAX_CHUNK = 32                 # views per launch the kernel takes (CDS_TSDF_MAX_CHUNK)
 CHUNK_VIEWS = 32               # views per launch of TsdfVolume.integrate (profiles/tsdf_mesh.md: 3.5 x faster than 1)
+WEIGHT_MODES = ("one", "angle", "conf", "angle_conf")   # what a pixel weighs in the integration
 MAX_ROUNDS = 64                # hook passes of the component labelling before it gives up (CDS_MESH_CC_MAX_ROUNDS)
 PLACEMENTS = ("quadric", "mean")   # where simplify_mesh puts a cluster's vertex
 MAX_SAMPLE_N = 1 << 15         # subdivisions per edge sample_mesh takes (CDS_MESH_SAMPLE_MAX_N): n^2 and the weights fit an int32
@@ -102,7 +109,8 @@ class TsdfVolume:
 
     Attributes: ``voxel``, ``trunc``, ``origin`` (float64 numpy [3]), ``nb`` (int64 numpy [3]: blocks per axis x, y, z),
     ``keys`` int32 [NB] ascending, ``table`` int32 [nbz,nby,nbx] (-1: no block), ``sum`` float32 [NB,512], ``n`` / ``nc``
-    int32 [NB,512], ``rgb`` int32 [3,NB,512]."""
+    int32 [NB,512], ``rgb`` int32 [3,NB,512]; ``wn`` int32 [NB,512], the sum of the weights, once views came with weights
+    (DESIGN §1.14), else None."""
 
     def __init__(self, points: Tensor, voxel: float, trunc: Optional[float] = None):
         voxel, trunc = check_voxel(voxel, trunc, "TsdfVolume")
@@ -163,15 +171,27 @@ class TsdfVolume:
         self.n = torch.zeros((k, 512), dtype=torch.int32, device=dev)
         self.nc = torch.zeros((k, 512), dtype=torch.int32, device=dev)
         self.rgb = torch.zeros((3, k, 512), dtype=torch.int32, device=dev)
+        self.wn = None                       # int32 [NB,512], the sum of the weights: allocated by the first weighted integrate
+        self._weighted = None                # whether the views so far came with weights; None before the first
         self._frame = torch.tensor([*origin.tolist(), voxel], dtype=torch.float64)          # host arguments of the kernels
         self._dims = torch.tensor(nb.tolist(), dtype=torch.int32)
 
-    def integrate(self, depths: Tensor, masks: Tensor, images: Tensor, cams: Tensor, chunk: int = CHUNK_VIEWS) -> None:
+    def integrate(self, depths: Tensor, masks: Tensor, images: Tensor, cams: Tensor, chunk: int = CHUNK_VIEWS,
+                  weights: Optional[Tensor] = None, interp: bool = False, interp_jump: float = 0.05) -> None:
         """Add views in the order given: depths [V,h,w] float32, masks [V,h,w] (bool, uint8 or float: non-zero keeps the
         pixel), images [V,h,w,3] uint8, all on the volume's device; cams [V,2,4,4] float32 (extrinsic; intrinsic in [:3,:3]),
-        any device.  ``chunk`` views go into one launch (1..32); the result does not depend on it."""
+        any device.  ``chunk`` views go into one launch (1..32); the result does not depend on it.
+
+        ``weights`` uint8 [V,h,w] on the volume's device (:func:`view_weights`): a pixel counts that many times in ``sum`` and in
+        ``wn``, the weight sum that :meth:`extract` then divides by, and not at all at 0; every call on one volume comes with
+        weights or none does (ValueError).  ``interp``: the depth is interpolated in inverse depth between the four pixel centres
+        around the projection where all four are kept and within ``interp_jump`` (relative) of each other, and is the nearest
+        pixel's elsewhere.  Both are the rule of DESIGN §1.14 (``cds_tsdf_integrate_w_f32``); with neither, the call is what it
+        was without them."""
         if not (1 <= int(chunk) <= MAX_CHUNK):
             raise ValueError(f"TsdfVolume.integrate: chunk must lie in 1..{MAX_CHUNK}, got {chunk}")
+        if interp:
+            interp_jump = _positive(interp_jump, "interp_jump", "TsdfVolume.integrate")
         if depths.dim() != 3 or depths.dtype != torch.float32:
             raise ValueError(f"TsdfVolume.integrate: depths must be float32 [V,h,w], got {depths.dtype} {tuple(depths.shape)}")
         v, h, w = depths.shape
@@ -179,11 +199,21 @@ class TsdfVolume:
                 tuple(cams.shape) != (v, 2, 4, 4):
             raise ValueError(f"TsdfVolume.integrate: for depths {tuple(depths.shape)} masks must be [V,h,w], images uint8 [V,h,w,3] "
                              f"and cams [V,2,4,4]; got {tuple(masks.shape)}, {images.dtype} {tuple(images.shape)}, {tuple(cams.shape)}")
-        for t, name in ((depths, "depths"), (masks, "masks"), (images, "images")):
-            if t.device != self.device:
+        if weights is not None and (tuple(weights.shape) != (v, h, w) or weights.dtype != torch.uint8):
+            raise ValueError(f"TsdfVolume.integrate: weights must be uint8 {(v, h, w)}, got {weights.dtype} {tuple(weights.shape)}")
+        for t, name in ((depths, "depths"), (masks, "masks"), (images, "images"), (weights, "weights")):
+            if t is not None and t.device != self.device:
                 raise RuntimeError(f"TsdfVolume.integrate: {name} must be on {self.device}; there is no CPU fallback")
+        if self._weighted is not None and self._weighted != (weights is not None):
+            raise ValueError("TsdfVolume.integrate: this volume holds views " + ("with" if self._weighted else "without") +
+                             " weights; weighted and unweighted views do not mix in one volume")
         if v == 0 or self.n_blocks == 0:
             return
+        self._weighted = weights is not None
+        if weights is not None:
+            weights = weights.contiguous()
+            if self.wn is None:
+                self.wn = torch.zeros((self.n_blocks, 512), dtype=torch.int32, device=self.device)
         depths, images = depths.contiguous(), images.contiguous()
         masks = (masks != 0).to(torch.uint8).contiguous()
         cam = cams.detach().to(torch.float32).to(self.device).double()
@@ -198,11 +228,17 @@ class TsdfVolume:
         with torch.cuda.device(self.device):
             for v0 in range(0, v, int(chunk)):
                 nv = min(int(chunk), v - v0)
-                check(lib.cds_tsdf_integrate_f32(self.keys.data_ptr(), self.n_blocks, self._frame.data_ptr(), self._dims.data_ptr(),
-                                                 self.trunc, depths.data_ptr() + 4 * v0 * hw, masks.data_ptr() + v0 * hw,
-                                                 images.data_ptr() + 3 * v0 * hw, tab.data_ptr() + 8 * 24 * v0, nv, h, w,
-                                                 self.sum.data_ptr(), self.n.data_ptr(), self.nc.data_ptr(), self.rgb.data_ptr(),
-                                                 _stream(self.device)), "cds_tsdf_integrate_f32")
+                args = (self.keys.data_ptr(), self.n_blocks, self._frame.data_ptr(), self._dims.data_ptr(), self.trunc,
+                        depths.data_ptr() + 4 * v0 * hw, masks.data_ptr() + v0 * hw, images.data_ptr() + 3 * v0 * hw,
+                        tab.data_ptr() + 8 * 24 * v0, nv, h, w, self.sum.data_ptr(), self.n.data_ptr(), self.nc.data_ptr(),
+                        self.rgb.data_ptr())
+                if weights is None and not interp:
+                    check(lib.cds_tsdf_integrate_f32(*args, _stream(self.device)), "cds_tsdf_integrate_f32")
+                else:
+                    check(lib.cds_tsdf_integrate_w_f32(*args, weights.data_ptr() + v0 * hw if weights is not None else None,
+                                                       1 if interp else 0, float(interp_jump),
+                                                       self.wn.data_ptr() if weights is not None else None, _stream(self.device)),
+                          "cds_tsdf_integrate_w_f32")
 
     def extract(self, min_weight: int = 2) -> Dict[str, Tensor]:
         """The zero level set over the cubes whose eight corners were seen at least ``min_weight`` times
@@ -232,11 +268,61 @@ class TsdfVolume:
             tfirst = (ends[1] - bt).to(torch.int32)
             vstart = torch.empty((k, 512), dtype=torch.int32, device=dev)
             out = _empty_mesh(dev, nv, nf)
-            check(lib.cds_tsdf_emit(self.keys.data_ptr(), self.table.data_ptr(), k, *frame, self.sum.data_ptr(), self.n.data_ptr(),
+            denom = self.wn if self.wn is not None else self.n                 # a weighted volume's distance is sum / wn (§1.14)
+            check(lib.cds_tsdf_emit(self.keys.data_ptr(), self.table.data_ptr(), k, *frame, self.sum.data_ptr(), denom.data_ptr(),
                                     self.nc.data_ptr(), self.rgb.data_ptr(), vmask.data_ptr(), tcount.data_ptr(), vfirst.data_ptr(),
                                     tfirst.data_ptr(), nv, nf, vstart.data_ptr(), out["vertices"].data_ptr(), out["colors"].data_ptr(),
                                     out["faces"].data_ptr() if nf else None, _stream(self.device)), "cds_tsdf_emit")
         return out
+
+
+def view_weights(depth: Tensor, mask: Tensor, cam: Tensor, conf: Optional[Tensor] = None, mode: str = "angle", radius: int = 2,
+                 jump: float = 0.01, min_pts: int = 6) -> Tensor:
+    """The weight map of one view for :meth:`TsdfVolume.integrate` (``cds_tsdf_view_weights``): depth float32
+    [h,w] and mask [h,w] (bool, uint8 or float: non-zero keeps the pixel) on a ROCm device, cam [2,4,4] (extrinsic; intrinsic in
+    [:3,:3]; any device), conf [h,w] floating point on the device or None -> uint8 [h,w] on the device: 0 where the pixel is not kept,
+    else 1..255.  ``mode``: "angle", 255 times the cosine between the viewing ray and the normal of the depth map there
+    (:func:`ops.depth_normals` over the kept pixels with ``radius``, ``jump``, ``min_pts``; 1 where there is no normal or it
+    faces away); "conf", 255 times ``conf`` clamped to [0, 1]; "angle_conf", their product."""
+    from . import ops
+    if mode not in WEIGHT_MODES[1:]:
+        raise ValueError(f"view_weights: mode must be one of {WEIGHT_MODES[1:]}, got {mode!r}")
+    if mode != "angle" and conf is None:
+        raise ValueError(f"view_weights: mode {mode!r} needs conf, the confidence map of the view")
+    if not isinstance(depth, torch.Tensor) or depth.dim() != 2 or depth.dtype != torch.float32:
+        raise ValueError(f"view_weights: depth must be a float32 [h,w] tensor, got {getattr(depth, 'dtype', type(depth))} "
+                         f"{tuple(getattr(depth, 'shape', ()))}")
+    h, w = depth.shape
+    if tuple(mask.shape) != (h, w) or tuple(cam.shape) != (2, 4, 4):
+        raise ValueError(f"view_weights: for depth {(h, w)} mask must be [h,w] and cam [2,4,4], got {tuple(mask.shape)}, "
+                         f"{tuple(cam.shape)}")
+    if not depth.is_cuda:
+        raise RuntimeError("view_weights: depth must be a ROCm (cuda) tensor; there is no CPU fallback")
+    dev = depth.device
+    use_conf = mode != "angle"
+    if use_conf and (tuple(conf.shape) != (h, w) or not conf.is_floating_point()):
+        raise ValueError(f"view_weights: conf must be a floating-point {(h, w)} tensor, got {conf.dtype} {tuple(conf.shape)}")
+    for t, name in ((mask, "mask"), (conf if use_conf else None, "conf")):
+        if t is not None and t.device != dev:
+            raise RuntimeError(f"view_weights: {name} must be on {dev}; there is no CPU fallback")
+    cam32 = cam.detach().to("cpu", torch.float32)
+    K, E = cam32[1, :3, :3], cam32[0]
+    if K[1, 0] != 0 or K[2].tolist() != [0.0, 0.0, 1.0]:
+        raise ValueError(f"view_weights: the intrinsic must have the rows (fx, s, cx), (0, fy, cy), (0, 0, 1), got {K.tolist()}")
+    depth = depth.contiguous()
+    mask = (mask != 0).to(torch.uint8).contiguous()
+    normals = ok = None
+    if mode != "conf":
+        normals, ok = ops.depth_normals(depth, K, E, valid=mask, radius=radius, jump=jump, min_pts=min_pts)
+    if use_conf:
+        conf = conf.to(torch.float32).contiguous()
+    cam_host = torch.cat([K.reshape(9), E.reshape(16)]).contiguous()
+    out = torch.empty((h, w), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        check(_lib.load().cds_tsdf_view_weights(depth.data_ptr(), mask.data_ptr(), normals.data_ptr() if normals is not None else None,
+                                                ok.data_ptr() if ok is not None else None, conf.data_ptr() if use_conf else None,
+                                                cam_host.data_ptr(), h, w, out.data_ptr(), _stream(dev)), "cds_tsdf_view_weights")
+    return out
 
 
 # -------------------------------------------------------------------------------------------------------------- components
@@ -649,15 +735,30 @@ def read_mesh_ply(path: str):
 
 
 # -------------------------------------------------------------------------------------------------------------------- scans
-def mesh_views(views: Sequence[dict], voxel: float, trunc: Optional[float] = None, min_weight: int = 2, device="cuda"):
+def _check_weighting(weight, interp, interp_jump, what: str) -> float:
+    """-> interp_jump as a float; ValueError for an unknown weight mode or, with interp, a jump that is not finite and > 0."""
+    if weight not in WEIGHT_MODES:
+        raise ValueError(f"{what}: weight must be one of {WEIGHT_MODES}, got {weight!r}")
+    return _positive(interp_jump, "interp_jump", what) if interp else float(interp_jump)
+
+
+def mesh_views(views: Sequence[dict], voxel: float, trunc: Optional[float] = None, min_weight: int = 2, device="cuda",
+               weight: str = "one", interp: bool = False, interp_jump: float = 0.05):
     """Allocation, integration and extraction for the per-view records that ``filter_depth(collect=...)`` gathers
-    -> (mesh dict of :meth:`TsdfVolume.extract`, the volume)."""
+    -> (mesh dict of :meth:`TsdfVolume.extract`, the volume).  ``weight``: "one", or a mode of :func:`view_weights`, whose maps
+    (from each record's depth, mask, cam and, for the conf modes, "conf") then weigh the pixels; ``interp`` / ``interp_jump`` as in
+    :meth:`TsdfVolume.integrate`.  At their defaults nothing of that runs."""
+    interp_jump = _check_weighting(weight, interp, interp_jump, "mesh_views")
     dev = torch.device(device)
     pts = torch.cat([v["points"] for v in views]) if views else torch.zeros((0, 3), dtype=torch.float32, device=dev)
     vol = TsdfVolume(pts, voxel, trunc)
     if views and vol.n_blocks:
+        weights = None
+        if weight != "one":
+            weights = torch.stack([view_weights(v["depth"], v["mask"], v["cam"], v.get("conf"), mode=weight) for v in views])
         vol.integrate(torch.stack([v["depth"] for v in views]), torch.stack([v["mask"] for v in views]),
-                      torch.stack([v["image"] for v in views]), torch.stack([v["cam"] for v in views]))
+                      torch.stack([v["image"] for v in views]), torch.stack([v["cam"] for v in views]), weights=weights,
+                      interp=bool(interp), interp_jump=interp_jump)
     return vol.extract(min_weight), vol
 
 
@@ -697,7 +798,8 @@ def _finish(mesh, plyfilename: str, clean, simplify: float, placement: str, samp
 def mesh_scan(pair_folder: str, scan_folder: str, plyfilename: str, voxel: float, trunc: Optional[float] = None, min_weight: int = 2,
               method: str = "normal", cloud_ply: Optional[str] = None, device: str = "cuda", min_component: int = 0,
               keep_largest: int = 0, simplify: float = 0.0, placement: str = "quadric", sample: float = 0.0,
-              surface_ply: Optional[str] = None, **fusion_options) -> Dict[str, object]:
+              surface_ply: Optional[str] = None, weight: str = "one", interp: bool = False, interp_jump: float = 0.05,
+              **fusion_options) -> Dict[str, object]:
     """One scan from saved depth maps to a mesh at ``plyfilename``: the fusion pass of :func:`fusion.filter_depth` (``method``
     "normal" or "dynamic" and its ``fusion_options``), then allocation from every view's kept points, integration of the fused
     depth maps in ``pair.txt`` order and extraction.  ``cloud_ply``: also write the fused cloud there, from the same pass and byte
@@ -705,7 +807,8 @@ def mesh_scan(pair_folder: str, scan_folder: str, plyfilename: str, voxel: float
     :func:`clean_mesh` before it is written; at 0 nothing of that runs.  ``simplify``: a cell side > 0 sends the
     mesh, after the clean-up, through :func:`simplify_mesh` with ``placement``; at 0 nothing of that runs.
     ``sample``: a spacing > 0 also writes the sampled surface of the mesh written (:func:`sample_mesh`) as a cloud
-    at ``surface_ply``; at 0 nothing of that runs.
+    at ``surface_ply``; at 0 nothing of that runs.  ``weight`` / ``interp`` / ``interp_jump``: the weighted, interpolating
+    integration of :func:`mesh_views`; the confidence of the conf modes is the view's last-stage confidence map.
     -> {"vertices", "faces", "blocks": counts, "cloud": filter_depth's result, "mesh": the mesh dict written, still on the device
     (render.render_scan takes it)[, "clean": clean_mesh's info][, "simplify": simplify_mesh's info][, "sample": sample_mesh's
     info and the spacing]}."""
@@ -719,9 +822,10 @@ def mesh_scan(pair_folder: str, scan_folder: str, plyfilename: str, voxel: float
         raise ValueError(f"mesh_scan: min_component and keep_largest must be >= 0, got {min_component} and {keep_largest}")
     simplify = _check_simplify(simplify, placement, "mesh_scan")
     sample = _check_sample(sample, surface_ply, "mesh_scan")
+    interp_jump = _check_weighting(weight, interp, interp_jump, "mesh_scan")
     views: list = []
     cloud = filter_depth(pair_folder, scan_folder, cloud_ply, device=device, method=method, collect=views, **fusion_options)
-    mesh, vol = mesh_views(views, voxel, trunc, min_weight, device)
+    mesh, vol = mesh_views(views, voxel, trunc, min_weight, device, weight, interp, interp_jump)
     clean = (min_component, keep_largest) if int(min_component) > 0 or int(keep_largest) > 0 else None
     return dict(_finish(mesh, plyfilename, clean, simplify, placement, sample, surface_ply), blocks=vol.n_blocks, cloud=cloud)
 
@@ -762,7 +866,7 @@ def format_mesh(info: Dict[str, object]) -> str:
 
 # ---------------------------------------------------------------------------------------------------------------------- CLI
 def add_mesh_args(ap: argparse.ArgumentParser, required: bool = False) -> None:
-    """The options of DESIGN §1.9, §1.11, §1.12 and §1.13, shared with ``infer --fuse``."""
+    """The options of DESIGN §1.9, §1.11, §1.12, §1.13 and §1.14, shared with ``infer --fuse``."""
     ap.add_argument("--mesh_voxel", type=float, default=None, required=required, metavar="SIZE",
                     help="write <outdir>/<scan>_mesh.ply: a triangle mesh from a TSDF volume with this lattice spacing (world units)")
     ap.add_argument("--mesh_trunc", type=float, default=None, metavar="T",
@@ -782,6 +886,32 @@ def add_mesh_args(ap: argparse.ArgumentParser, required: bool = False) -> None:
     ap.add_argument("--mesh_sample", type=float, default=None, metavar="SPACING",
                     help="--mesh_voxel: also write <outdir>/<scan>_surface.ply, the surface of the mesh written as a cloud: the "
                          "centroids of every face's sub-triangles with edges of at most SPACING (world units)")
+    ap.add_argument("--mesh_weight", default="one", choices=list(WEIGHT_MODES),
+                    help="--mesh_voxel: what a kept pixel weighs in the volume: one; angle, the cosine between its viewing ray and "
+                         "the normal of its depth map; conf, its last-stage confidence; angle_conf, their product")
+    ap.add_argument("--mesh_interp", action="store_true",
+                    help="--mesh_voxel: interpolate the depth between the four pixels around a projection (in inverse depth) where "
+                         "they are kept and close in depth, instead of taking the nearest pixel's")
+    ap.add_argument("--mesh_interp_jump", type=float, default=None, metavar="J",
+                    help="--mesh_interp: the largest relative depth difference among the four pixels (default 0.05)")
+
+
+def check_weight_args(ap: argparse.ArgumentParser, args, allowed: bool) -> float:
+    """ap.error for --mesh_weight, --mesh_interp or --mesh_interp_jump where no volume is integrated (``allowed`` false), for a
+    jump without --mesh_interp and for one that is not positive -> the jump (0.05 unless given)."""
+    given = [name for name, on in (("--mesh_weight", args.mesh_weight != "one"), ("--mesh_interp", args.mesh_interp),
+                                   ("--mesh_interp_jump", args.mesh_interp_jump is not None)) if on]
+    if given and not allowed:
+        ap.error(f"{', '.join(given)}: these options weigh the views of --mesh_voxel: give --mesh_voxel SIZE (a saved mesh of "
+                 "--from_mesh is not integrated again)")
+    if args.mesh_interp_jump is None:
+        return 0.05
+    if not args.mesh_interp:
+        ap.error("--mesh_interp_jump belongs to --mesh_interp")
+    try:
+        return _positive(args.mesh_interp_jump, "--mesh_interp_jump")
+    except ValueError as e:
+        ap.error(str(e))
 
 
 def check_clean_args(ap: argparse.ArgumentParser, args, allowed: bool) -> None:
@@ -829,6 +959,7 @@ def main(argv=None) -> Dict[str, Dict[str, object]]:
     if (args.mesh_voxel is None) == (args.from_mesh is None):
         ap.error("give either --mesh_voxel SIZE (fuse and mesh) or --from_mesh FILE (clean a saved mesh)")
     check_clean_args(ap, args, True)
+    interp_jump = check_weight_args(ap, args, args.from_mesh is None)
     if args.from_mesh is None and args.testpath is None:
         ap.error("--testpath is required with --mesh_voxel")
     if args.filter_method == "gipuma":
@@ -851,7 +982,8 @@ def main(argv=None) -> Dict[str, Dict[str, object]]:
                          method=args.filter_method, device=args.device, min_component=args.mesh_min_component,
                          keep_largest=args.mesh_keep_largest, simplify=args.mesh_simplify or 0.0,
                          placement=args.mesh_simplify_placement, sample=args.mesh_sample or 0.0,
-                         surface_ply=os.path.join(args.outdir, f"{scan}_surface.ply"), conf=_floats(args.conf, 3, "--conf"),
+                         surface_ply=os.path.join(args.outdir, f"{scan}_surface.ply"), weight=args.mesh_weight,
+                         interp=args.mesh_interp, interp_jump=interp_jump, conf=_floats(args.conf, 3, "--conf"),
                          thres_disp=args.thres_disp, thres_view=args.thres_view, dist_base=args.dyn_dist_base,
                          rel_base=args.dyn_rel_base, n_views=tuple(int(v) for v in _floats(args.dyn_views, 2, "--dyn_views")))
         out[scan] = info

@@ -671,6 +671,58 @@ int cds_tsdf_emit(const int* keys, const int* table, long long n_blocks, const d
                   long long n_faces, int* vstart, float* vertices, unsigned char* colors, int* faces, void* stream);
 
 /*
+ * Weighted TSDF fusion: a weight per pixel and a depth interpolated between pixels (csrc/tsdf.hip).
+ *
+ * cds_tsdf_view_weights: the weight map of one view.
+ *   depth [h][w] fp32; mask [h][w] uint8; normals [3][h][w] fp32 (world frame) with ok [h][w] uint8, as cds_depth_normals_f32
+ *   writes them when called with valid = mask, both NULL or both set; conf [h][w] fp32 or NULL; cam_host: the 25 HOST floats
+ *   of cds_depth_normals_f32 (K 3x3, then E 4x4); weights [h][w] uint8.
+ *   The rule, per pixel (x, y), in fp64 from the fp32 values, bracketed as written:
+ *   1. K has the rows (fx, s, cx), (0, fy, cy), (0, 0, 1); R = E[:3,:3].
+ *   2. weights = 0 where mask is 0 or the depth is not finite or is <= 0.
+ *   3. Angle term a: 1 when normals is NULL; 0 where ok is 0; else, with the camera-frame ray through the pixel centre
+ *        c1 = ((y + 0.5) - cy) / fy,  c0 = (((x + 0.5) - cx) - s c1) / fx,  c2 = 1,
+ *      and the camera-frame normal nc[r] = (R[r][0] n0 + R[r][1] n1) + R[r][2] n2,
+ *        a = -((nc0 c0 + nc1 c1) + nc2) / sqrt((c0 c0 + c1 c1) + 1.0),
+ *      the cosine between the normal and the direction to the camera.  A value that is not finite or is below 0 gives 0, a
+ *      value above 1 gives 1.
+ *   4. Confidence term c: 1 when conf is NULL, else conf clamped to [0, 1]; NaN gives 0.
+ *   5. weights = min(255, max(1, (int)floor(255.0 * (a * c) + 0.5))): a kept pixel weighs at least 1, so it still counts
+ *      towards min_weight; grazing pixels and pixels without a normal get that minimum.
+ *   Division and sqrt are the correctly rounded fp64 operations.
+ *   CDS_EINVAL: a null depth, mask, cam_host or weights; normals without ok or ok without normals; h or w < 1, h w >= 2^31;
+ *   a K whose last row is not (0, 0, 1) or whose K[1][0] is not 0.
+ *
+ * cds_tsdf_integrate_w_f32: cds_tsdf_integrate_f32 with weights [n_views][h][w] uint8 or NULL (every kept pixel weighs 1),
+ *   interp (0 / non-zero), jump, and wn [n_blocks][512] int32, the sum of the weights, set iff weights is.
+ *   Per lattice point and view, steps 1-4 of the integration above give u, v, the nearest pixel q = (x, y) and its depth d. Then
+ *   4a. wq = weights ? weights[view][y][x] : 1.  Skip the view if wq == 0.
+ *   4b. dd = (double)d, unless interp is set and all of this holds, then dd = 1.0 / i:
+ *       a = u - 0.5, b = v - 0.5, x0 = floor(a), y0 = floor(b), fx = a - x0, fy = b - y0 (pixel centres lie at x + 0.5);
+ *       x0 >= 0, x0 + 1 < w, y0 >= 0, y0 + 1 < h;
+ *       the pixels (x0, y0), (x0 + 1, y0), (x0, y0 + 1), (x0 + 1, y0 + 1), depths d00 d10 d01 d11, all have a non-zero mask and
+ *       a finite depth > 0 (their weights are not looked at);
+ *       with lo / hi the smallest / largest of the four, (double)hi - (double)lo <= (double)jump * (double)lo;
+ *       i00 = 1.0 / (double)d00 and so on;  i0 = i00 + fx (i10 - i00),  i1 = i01 + fx (i11 - i01),  i = i0 + fy (i1 - i0).
+ *       1 / z is affine in the pixel for a plane (the fact cds_depth_normals_f32 uses), so dd is exact on planes up to the
+ *       rounding of the fp32 depths.  q is always one of the four; the mask test, the weight and the colour stay its own.
+ *   5.  sdf = dd - z.  Skip if sdf < -T.
+ *   6.  sum = sum + (float)((double)wq * min(1.0, sdf / T)), one fp32 add per view, in view order;  n += 1;  wn += wq.
+ *   7.  As above: colours are not weighted and come from q.
+ *   With weights NULL and interp 0 the accumulators get the bits of cds_tsdf_integrate_f32.
+ *   Extraction of a weighted volume: cds_tsdf_classify reads n (valid iff n >= min_weight views), cds_tsdf_emit takes wn in the
+ *   place of n, so that Da = sum / wn.  inside iff sum < 0 stands, because the weights are positive.
+ *   CDS_EINVAL: the cases of cds_tsdf_integrate_f32; weights without wn or wn without weights; interp != 0 with a jump that is
+ *   not finite or not > 0.
+ */
+int cds_tsdf_view_weights(const float* depth, const unsigned char* mask, const float* normals, const unsigned char* ok,
+                          const float* conf, const float* cam_host, int h, int w, unsigned char* weights, void* stream);
+int cds_tsdf_integrate_w_f32(const int* keys, long long n_blocks, const double* frame_host, const int* dims_host, double trunc,
+                             const float* depths, const unsigned char* masks, const unsigned char* images, const double* cams,
+                             int n_views, int h, int w, float* sum, int* n, int* nc, int* rgb, const unsigned char* weights,
+                             int interp, float jump, int* wn, void* stream);
+
+/*
  * Rendering a triangle mesh into the views of a scan: depth, face, facing and colour per pixel (csrc/raster.hip).
  *
  * Inputs.  vertices fp32 [n_vertices][3], faces int32 [n_faces][3], optional colours uint8 [n_vertices][3]; per view

@@ -1,6 +1,7 @@
 """Time the mesher of csrc/tsdf.hip on a DTU-shaped scan: allocation, integration and extraction.
 
     python scripts/time_tsdf_mesh.py [--views 49 --h 864 --w 1152 --voxel 0.35] [--rounds 5] [--write profiles/tsdf_mesh.md]
+        [--mesh_weight angle|conf|angle_conf] [--mesh_interp]
 
 The scan: the height field of synth.make_fusion_scene rendered on the GPU from --views cameras of synth.make_cameras (noise-free
 depth maps through the pixel centres, every pixel kept except an 8-pixel border, random images).  The kept points of all views
@@ -12,6 +13,9 @@ process:
   integration   TsdfVolume.integrate of all views with 32 views per launch (the default), 16, and 1 (the same kernel launched
                 once per view: the volume is then read and written once per view), between two HIP events
   extraction    TsdfVolume.extract(2): classify, two prefix sums, emit
+  weighted      with --mesh_weight / --mesh_interp: the integration of all views, 32 per launch, without weights
+                (the baseline), with the weight maps of the mode, and with them and the interpolated depth, alternating inside
+                every round, and the time the weight maps take (profiles/tsdf_weighted.md)
 The floor of an integration is its compulsory traffic at the 6.3 TB/s a streaming kernel reaches on the MI355X: 24 B per
 lattice point read and written once per launch, plus the maps (8 B per pixel) once.  Before anything is timed the volumes of
 the three chunk sizes are compared: they must be equal bit for bit.  Recorded values, not thresholds.  There is no CPU
@@ -72,6 +76,48 @@ def kernel_resources():
         return [f"not available ({e})"]
 
 
+def weighted_section(args, fresh, depths, masks8, images, cams, V):
+    """The integration of all views, 32 per launch, in the modes of DESIGN §1.14, alternating inside every round with the
+    unweighted kernel as the baseline; every mode adds to a volume of its own.  -> lines of the report."""
+    mode = args.mesh_weight
+    weights, t_maps = None, []
+    if mode != "one":
+        g = torch.Generator(device="cuda").manual_seed(1)
+        confs = torch.rand(depths.shape, generator=g, device="cuda") if mode != "angle" else [None] * V
+        for _ in range(args.rounds + 1):                          # the first is the warm-up
+            start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            start.record()
+            weights = torch.stack([mesh.view_weights(depths[i], masks8[i], cams[i], confs[i], mode=mode) for i in range(V)])
+            end.record()
+            torch.cuda.synchronize()
+            t_maps.append(start.elapsed_time(end))
+    modes = [("one (cds_tsdf_integrate_f32, the baseline)", {})]
+    if mode != "one":
+        modes.append((f"{mode}, nearest pixel", dict(weights=weights)))
+    if args.mesh_interp:
+        modes.append((f"{mode}, interpolated depth", dict(weights=weights, interp=True)))
+    vols = [fresh() for _ in modes]
+    times = [[] for _ in modes]
+    for r in range(args.rounds + 1):                              # the first round is the warm-up
+        for vol, (_, kw), t in zip(vols, modes, times):
+            start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            start.record()
+            vol.integrate(depths, masks8, images, cams, **kw)
+            end.record()
+            torch.cuda.synchronize()
+            if r:
+                t.append(start.elapsed_time(end))
+    lines = [f"\n## Weighted integration (DESIGN §1.14): {V} views, 32 per launch\n", "| mode | median ms | min | max | note |\n|---|---|---|---|---|"]
+    base = np.median(times[0])
+    for (name, _), t in zip(modes, times):
+        lines.append(f"| {name} | {stats(t)} | {np.median(t) / base:.2f} x the baseline |")
+    if t_maps:
+        share = float((weights > 1).float().mean())
+        lines.append(f"| weight maps of {V} views ({mode}: normals, then cds_tsdf_view_weights) | {stats(t_maps[1:])} | "
+                     f"{100 * share:.1f} % of the pixels weigh more than 1 |")
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--views", type=int, default=49)
@@ -80,6 +126,9 @@ def main():
     ap.add_argument("--voxel", type=float, default=0.35)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--write", default=None, help="markdown file to record the result in")
+    ap.add_argument("--mesh_weight", default="one", choices=list(mesh.WEIGHT_MODES),
+                    help="also time the weighted integration of DESIGN §1.14 with the weight maps of this mode")
+    ap.add_argument("--mesh_interp", action="store_true", help="also time the integration with the interpolated depth")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("time_tsdf_mesh.py needs the GPU: nothing is measured without one")
@@ -144,6 +193,8 @@ def main():
                      f"{STREAM_TBS} TB/s: fraction {f / np.median(t_int[c]):.2f}; {np.median(t_int[c]) / np.median(t_int[32]):.2f} x the default |")
     lines.append(f"| extraction (classify, prefix sums, emit) | {stats(t_ext)} | host clock around a synchronise; includes one read-back "
                  "of the two totals |")
+    if args.mesh_weight != "one" or args.mesh_interp:
+        lines += weighted_section(args, fresh, depths, masks8, images, cams, V)
     lines.append("\n## Kernel resources (`scripts/kernel_resources.py tsdf.hip`)\n\n```\n" + "\n".join(kernel_resources()) + "\n```")
     text = "\n".join(lines)
     print(text, flush=True)

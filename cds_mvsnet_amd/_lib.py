@@ -166,6 +166,12 @@ SIGNATURES = {
     "cds_mesh_simplify_quadric_f32": [P, L, P, L, P, P, P, P, L, F, P, P, P],
     "cds_mesh_simplify_mark": [P, P, L, L, P, P],
     "cds_mesh_simplify_gather": [P, P, L, P, P, P, L, P, P, L, L, P, P, P, P],
+    "cds_mesh_adj_small": [],
+    "cds_mesh_adj_count": [P, L, L, P, P],
+    "cds_mesh_adj_fill": [P, L, L, P, P, P, L, P],
+    "cds_mesh_adj_finish": [L, P, P, L, P, P, P],
+    "cds_mesh_smooth_step_f32": [P, P, L, P, P, P, DB, P],
+    "cds_mesh_smooth_limit_f32": [P, P, L, DB, P, P, P],
     "cds_mesh_sample_max_n": [],
     "cds_mesh_sample_count": [P, L, P, L, DB, P, P, P],
     "cds_mesh_sample_emit": [P, P, L, P, L, P, P, L, P, P, P, P],

@@ -1,4 +1,4 @@
-// What the mesh kernels share (mesh_clean.hip, mesh_simplify.hip, mesh_sample.hip, raster.hip): the launch
+// What the mesh kernels share (mesh_clean.hip, mesh_simplify.hip, mesh_smooth.hip, mesh_sample.hip, raster.hip): the launch
 // shape, the size and finiteness tests, the face loader, and the one compaction behind cds_mesh_cc_gather and
 // cds_mesh_simplify_gather.
 #pragma once

@@ -15,7 +15,8 @@ normal and `--merge_voxel SIZE` (`--merge_min_points K`) merges the scan to one 
 `--mesh_voxel SIZE` (`--mesh_trunc T`, `--mesh_min_weight N`; not for gipuma) also writes `<out>/<scan>_mesh.ply`, a triangle mesh
 from the same fusion pass (mesh.py); `--mesh_min_component N` / `--mesh_keep_largest K` drop its small connected
 components first and `--mesh_simplify CELL` (`--mesh_simplify_placement quadric|mean`) then merges the vertices
-of every cell of that side into one; `--mesh_sample SPACING` also writes `<out>/<scan>_surface.ply`, the surface
+of every cell of that side into one, after `--mesh_smooth ITER` (`--mesh_smooth_lambda L`, `--mesh_smooth_mu M`,
+`--mesh_smooth_max_move D`) has smoothed it; `--mesh_sample SPACING` also writes `<out>/<scan>_surface.ply`, the surface
 of that mesh as a cloud; `--mesh_weight angle|conf|angle_conf` and `--mesh_interp` (`--mesh_interp_jump J`) weigh
 the pixels and interpolate the depth in the integration.  With `--mesh_voxel`, `--render_mesh` (`--back`, `--max_rel_diff R`, `--save_image`) renders
 that mesh into every view, `<out>/<scan>/depth_mesh/%08d.pfm`, and `--export_blended DIR` writes the tree `fit --dataset blended`
@@ -229,7 +230,7 @@ def run(args) -> float:
         # step 2 of the reference's test.py (pcd_filter, test.py:386-396): scans are independent -> shard over ranks
         from .fusion import cloud_kwargs, filter_depth, format_admitted, format_cloud
         from .gipuma import filter_scan
-        from .mesh import format_mesh, mesh_scan
+        from .mesh import SMOOTH_KEYS, format_mesh, mesh_scan, smooth_args
 
         def fuse(scan, **kw):
             """The cloud alone, or with --mesh_voxel cloud and mesh from one fusion pass."""
@@ -241,7 +242,8 @@ def run(args) -> float:
                              cloud_ply=ply, min_component=args.mesh_min_component, keep_largest=args.mesh_keep_largest,
                              simplify=args.mesh_simplify or 0.0, placement=args.mesh_simplify_placement,
                              sample=args.mesh_sample or 0.0, surface_ply=os.path.join(args.outdir, f"{scan}_surface.ply"),
-                             weight=args.mesh_weight, interp=args.mesh_interp, interp_jump=args.mesh_interp_jump, **kw)
+                             weight=args.mesh_weight, interp=args.mesh_interp, interp_jump=args.mesh_interp_jump,
+                             **dict(zip(SMOOTH_KEYS, smooth_args(args))), **kw)
             print(f"[{rank}] {scan}_mesh.ply: {format_mesh(info)}", flush=True)
             if args.render_mesh:
                 # the mesh just written, from the device tensors, into every view of the scan

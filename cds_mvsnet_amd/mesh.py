@@ -9,7 +9,8 @@ the blocks out.  There is no CPU path.
 
     python -m cds_mvsnet_amd.mesh --testpath <scenes> --outdir <out> --testlist <list> --mesh_voxel SIZE [--mesh_trunc T]
         [--mesh_min_weight 2] [--mesh_min_component N] [--mesh_keep_largest K] [--mesh_simplify CELL]
-        [--mesh_simplify_placement quadric|mean] [--mesh_sample SPACING] [--mesh_weight one|angle|conf|angle_conf] [--mesh_interp]
+        [--mesh_simplify_placement quadric|mean] [--mesh_smooth ITER] [--mesh_smooth_lambda 0.5] [--mesh_smooth_mu -0.53]
+        [--mesh_smooth_max_move D] [--mesh_sample SPACING] [--mesh_weight one|angle|conf|angle_conf] [--mesh_interp]
         [--mesh_interp_jump 0.05] [--filter_method normal|dynamic] [--conf 0,0,0] [--thres_disp 1.0] [--thres_view 3]
         [--dyn_dist_base 0.25] [--dyn_rel_base 0.000769] [--dyn_views 2,10]
 
@@ -28,6 +29,12 @@ cleans saved meshes in place, without the fusion.
 ``csrc/mesh_simplify.hip``): the vertices of a cell of side CELL, the cells of ``--merge_voxel``, become one vertex at the
 regularised minimiser of its faces' quadric error (``--mesh_simplify_placement mean``: at their mean), and the faces that
 collapse or repeat are dropped.  ``--from_mesh FILE --mesh_simplify CELL`` does it to a saved mesh.
+
+``--mesh_smooth ITER`` smooths the mesh after the clean-up and before the simplification (the kernels of
+``csrc/mesh_smooth.hip``): ITER iterations of the lambda|mu filter move every vertex towards the mean of its neighbours and back,
+which takes the noise of the depth maps and the staircase of the tetrahedra out of the surface without shrinking it; faces,
+colours and counts stay as they are.  ``--mesh_smooth_max_move D`` keeps every vertex within D of where it was.
+``--from_mesh FILE --mesh_smooth ITER`` does it to a saved mesh.
 
 ``--mesh_sample SPACING`` also writes ``<out>/<scan>_surface.ply``, the surface of the mesh written as a cloud (the
 kernels of ``csrc/mesh_sample.hip``): every face is cut into n^2 congruent sub-triangles with edges of at most SPACING and the
@@ -59,9 +66,13 @@ MAX_CHUNK = 32                 # views per launch the kernel takes (CDS_TSDF_MAX
 CHUNK_VIEWS = 32               # views per launch of TsdfVolume.integrate (profiles/tsdf_mesh.md: 3.5 x faster than 1)
 WEIGHT_MODES = ("one", "angle", "conf", "angle_conf")   # what a pixel weighs in the integration
 MAX_ROUNDS = 64                # hook passes of the component labelling before it gives up (CDS_MESH_CC_MAX_ROUNDS)
+SMOOTH_KEYS = ("smooth", "smooth_lambda", "smooth_mu", "smooth_max_move")   # the smoothing arguments of mesh_scan and clean_file
 PLACEMENTS = ("quadric", "mean")   # where simplify_mesh puts a cluster's vertex
 MAX_SAMPLE_N = 1 << 15         # subdivisions per edge sample_mesh takes (CDS_MESH_SAMPLE_MAX_N): n^2 and the weights fit an int32
 MAX_SAMPLES = 1 << 28          # points sample_mesh makes unless told otherwise: 19 bytes each, 4.75 GiB
+MAX_SMOOTH = 1000              # iterations smooth_mesh takes
+ADJ_SMALL = 64                 # entries of a vertex's segment that cds_mesh_adj_finish sorts itself (CDS_MESH_ADJ_SMALL)
+ADJ_BOUNDARY, ADJ_ISOLATED = 1, 2   # the flag bits of cds_mesh_adj_finish
 PACK_BITS = 21                 # three cluster numbers of at most this many bits make one sort key of a face's identity
 
 
@@ -596,6 +607,128 @@ def simplify_mesh(mesh_dict: Dict[str, Tensor], cell: float, placement: str = "q
     return out, info
 
 
+# --------------------------------------------------------------------------------------------------------------- smoothing
+def check_smooth(iterations, lam=0.5, mu=-0.53, max_move=0.0, what: str = "smooth_mesh"):
+    """-> (iterations, lam, mu, max_move) as an int and three floats; ValueError unless iterations is an int in 1..MAX_SMOOTH,
+    lam is finite and in (0, 1], mu is finite and in [-1, 0] and max_move is finite and >= 0 (rule 7 of DESIGN §1.15)."""
+    if isinstance(iterations, bool) or not isinstance(iterations, (int, np.integer)) or not (1 <= int(iterations) <= MAX_SMOOTH):
+        raise ValueError(f"{what}: iterations must be an int in 1..{MAX_SMOOTH}, got {iterations!r}")
+    values = []
+    for value, name, ok, span in ((lam, "lam", lambda x: 0.0 < x <= 1.0, "(0, 1]"), (mu, "mu", lambda x: -1.0 <= x <= 0.0, "[-1, 0]"),
+                                  (max_move, "max_move", lambda x: x >= 0.0, "[0, inf)")):
+        try:
+            x = float(value)
+        except (TypeError, ValueError):
+            x = math.nan
+        if not (math.isfinite(x) and ok(x)):
+            raise ValueError(f"{what}: {name} must be finite and in {span}, got {value!r}")
+        values.append(x)
+    return (int(iterations), *values)
+
+
+def _adjacency(faces: Tensor, nv: int):
+    """Rules 1-3 of DESIGN §1.15 for a contiguous int32 [F,3] face list on the current device, nv > 0 -> None when no valid edge
+    slot exists, else (start int32 [nv+1], deg int32 [nv], nbr int32 [E], flags uint8 [nv]).  The counting build: a count pass, the
+    prefix sum, a fill pass at integer cursors and the finishing kernel; the segments longer than ADJ_SMALL, which that kernel
+    does not sort itself, go through one torch sort of just their entries."""
+    dev, nf = faces.device, int(faces.shape[0])
+    if nf == 0:
+        return None
+    if 6 * nf >= 2 ** 31:
+        raise ValueError(f"mesh_adjacency: {nf} faces, at most {(2 ** 31 - 1) // 6}")
+    lib, stream = _lib.load(), _stream(dev)
+    count = torch.zeros(nv, dtype=torch.int32, device=dev)
+    check(lib.cds_mesh_adj_count(faces.data_ptr(), nf, nv, count.data_ptr(), stream), "cds_mesh_adj_count")
+    start = torch.zeros(nv + 1, dtype=torch.int32, device=dev)
+    start[1:] = torch.cumsum(count, 0, dtype=torch.int32)
+    long_ones = torch.nonzero(count > ADJ_SMALL).reshape(-1)
+    ne = int(start[-1])                                                      # the one read of the build, after nonzero's
+    if ne == 0:
+        return None
+    nbr = torch.empty(ne, dtype=torch.int32, device=dev)
+    cursor = torch.zeros(nv, dtype=torch.int32, device=dev)
+    check(lib.cds_mesh_adj_fill(faces.data_ptr(), nf, nv, start.data_ptr(), cursor.data_ptr(), nbr.data_ptr(), ne, stream),
+          "cds_mesh_adj_fill")
+    if long_ones.numel():
+        lens = count[long_ones].long()
+        owner = torch.repeat_interleave(torch.arange(long_ones.numel(), device=dev), lens)
+        first = torch.cumsum(lens, 0) - lens
+        at = start[long_ones].long()[owner] + (torch.arange(owner.numel(), device=dev) - first[owner])
+        nbr[at] = (torch.sort((owner << 32) | nbr[at].long()).values & 0xffffffff).to(torch.int32)
+    deg = torch.empty(nv, dtype=torch.int32, device=dev)
+    flags = torch.empty(nv, dtype=torch.uint8, device=dev)
+    check(lib.cds_mesh_adj_finish(nv, start.data_ptr(), nbr.data_ptr(), ne, deg.data_ptr(), flags.data_ptr(), stream),
+          "cds_mesh_adj_finish")
+    return start, deg, nbr, flags
+
+
+def mesh_adjacency(faces: Tensor, n_vertices: int) -> Dict[str, Tensor]:
+    """The neighbours that :func:`smooth_mesh` averages over (DESIGN §1.15 rules 1-3): faces int32 [F,3] on a ROCm device, every
+    index in [0, n_vertices) -> the CSR the step kernel reads, on that device: {"start" int32 [V+1]: vertex v owns
+    ``neighbors[start[v] : start[v+1]]``, of which the first ``degree[v]`` are its neighbours, ascending (the rest is slack),
+    "degree" int32 [V], "neighbors" int32 [E], "boundary" bool [V]: the vertex has an edge that one face slot holds, and its
+    neighbours are then only those across such edges, "isolated" bool [V]: no neighbour}."""
+    nv = _check_faces(faces, n_vertices, "mesh_adjacency")
+    dev = faces.device
+    with torch.cuda.device(dev):
+        built = _adjacency(faces.contiguous(), nv) if nv else None
+    if built is None:
+        return {"start": torch.zeros(nv + 1, dtype=torch.int32, device=dev), "degree": torch.zeros(nv, dtype=torch.int32, device=dev),
+                "neighbors": torch.zeros(0, dtype=torch.int32, device=dev), "boundary": torch.zeros(nv, dtype=torch.bool, device=dev),
+                "isolated": torch.ones(nv, dtype=torch.bool, device=dev)}
+    start, deg, nbr, flags = built
+    return {"start": start, "degree": deg, "neighbors": nbr, "boundary": (flags & ADJ_BOUNDARY) != 0,
+            "isolated": (flags & ADJ_ISOLATED) != 0}
+
+
+def smooth_mesh(mesh_dict: Dict[str, Tensor], iterations: int, lam: float = 0.5, mu: float = -0.53, max_move: float = 0.0):
+    """Taubin's lambda|mu filter with uniform weights: ``mesh_dict`` as :meth:`TsdfVolume.extract` returns it
+    (vertices float32 [V,3], all finite, colors uint8 [V,3], faces int32 [F,3], on one ROCm device).  ``iterations`` times, every
+    vertex moves by ``lam`` towards the mean of its neighbours and then, unless ``mu`` is 0 (the plain Laplacian filter, which
+    shrinks), by ``mu`` < 0 away from the new one; a vertex on an open border averages over its border neighbours only, and one
+    without neighbours stays.  ``max_move`` > 0 (world units) then pulls every vertex back to within that distance of where it
+    was.  Only the positions change: colours and faces are the input's tensors.  -> (mesh dict; info: {"iterations", "lam", "mu",
+    "vertices": V, "boundary", "isolated", "clamped": vertices, "max_move": the largest move, before the limit})."""
+    what = "smooth_mesh"
+    iterations, lam, mu, max_move = check_smooth(iterations, lam, mu, max_move, what)
+    vert, col, faces, nv, dev = _check_mesh(mesh_dict, what)
+    if nv and not bool(torch.isfinite(vert).all()):
+        raise ValueError(f"{what}: vertices must be finite")
+    info = {"iterations": iterations, "lam": lam, "mu": mu, "vertices": nv, "boundary": 0, "isolated": nv, "clamped": 0,
+            "max_move": 0.0}
+    same = {"vertices": vert, "colors": col, "faces": faces}
+    if nv == 0:
+        return same, info
+    vert, faces = vert.contiguous(), faces.contiguous()
+    with torch.cuda.device(dev):
+        built = _adjacency(faces, nv)
+        if built is None:                                                    # no valid edge: every vertex is isolated
+            return same, info
+        start, deg, nbr, flags = built
+        lib, stream = _lib.load(), _stream(dev)
+        src, dst = vert, torch.empty_like(vert)
+        spare = None
+        for _ in range(iterations):
+            for factor in (lam, mu):
+                if factor == 0.0:
+                    continue
+                check(lib.cds_mesh_smooth_step_f32(src.data_ptr(), dst.data_ptr(), nv, start.data_ptr(), deg.data_ptr(),
+                                                   nbr.data_ptr(), factor, stream), "cds_mesh_smooth_step_f32")
+                if src is vert:                                              # the input is read, never written
+                    spare = torch.empty_like(vert)
+                    src, dst = dst, spare
+                else:
+                    src, dst = dst, src
+        move2 = torch.empty(nv, dtype=torch.float64, device=dev)
+        clamped = torch.empty(nv, dtype=torch.uint8, device=dev)
+        check(lib.cds_mesh_smooth_limit_f32(vert.data_ptr(), src.data_ptr(), nv, max_move, move2.data_ptr(), clamped.data_ptr(),
+                                            stream), "cds_mesh_smooth_limit_f32")
+        stats = torch.stack([move2.max(), ((flags & ADJ_BOUNDARY) != 0).sum().double(), ((flags & ADJ_ISOLATED) != 0).sum().double(),
+                             clamped.sum().double()]).cpu().tolist()           # the one read after the launches
+    info.update(boundary=int(stats[1]), isolated=int(stats[2]), clamped=int(stats[3]), max_move=math.sqrt(stats[0]))
+    return {"vertices": src, "colors": col, "faces": faces}, info
+
+
 # ---------------------------------------------------------------------------------------------------------------- sampling
 def check_spacing(spacing, what: str = "sample_mesh") -> float:
     """-> spacing as a float; ValueError unless it is finite and > 0."""
@@ -780,13 +913,24 @@ def _check_simplify(simplify, placement, what: str) -> float:
     return check_cell(simplify, what)
 
 
-def _finish(mesh, plyfilename: str, clean, simplify: float, placement: str, sample: float, surface_ply) -> Dict[str, object]:
+def _check_smooth(smooth, lam, mu, max_move, what: str):
+    """-> None for "off" (smooth None or 0), else (iterations, lam, mu, max_move) through :func:`check_smooth` (ValueError)."""
+    if smooth is None or (not isinstance(smooth, bool) and isinstance(smooth, (int, np.integer)) and int(smooth) == 0):
+        return None
+    return check_smooth(smooth, lam, mu, max_move, what)
+
+
+def _finish(mesh, plyfilename: str, clean, smooth, simplify: float, placement: str, sample: float, surface_ply) -> Dict[str, object]:
     """The way of an extracted or loaded mesh into its files: :func:`clean_mesh` with ``clean`` = (min_component, keep_largest)
-    unless it is None, :func:`simplify_mesh` when ``simplify`` > 0, the mesh PLY, and when ``sample`` > 0 the sampled surface at
-    ``surface_ply`` -> {"vertices", "faces", "mesh": the mesh written, on the device[, "clean"][, "simplify"][, "sample"]}."""
+    unless it is None, :func:`smooth_mesh` with ``smooth`` = (iterations, lam, mu, max_move) unless it is None,
+    :func:`simplify_mesh` when ``simplify`` > 0, the mesh PLY, and when ``sample`` > 0 the sampled surface at ``surface_ply``
+    -> {"vertices", "faces", "mesh": the mesh written, on the device[, "clean"][, "smooth"][, "simplify"][, "sample"]}."""
     out = {}
     if clean is not None:
         mesh, out["clean"] = clean_mesh(mesh, *clean)
+    if smooth is not None:
+        mesh, out["smooth"] = smooth_mesh(mesh, *smooth)
+        out["smooth"] = dict(out["smooth"], limit=smooth[3])
     if simplify > 0:
         mesh, out["simplify"] = simplify_mesh(mesh, simplify, placement)
     write_mesh_ply(plyfilename, mesh["vertices"].cpu().numpy(), mesh["colors"].cpu().numpy(), mesh["faces"].cpu().numpy())
@@ -799,6 +943,7 @@ def mesh_scan(pair_folder: str, scan_folder: str, plyfilename: str, voxel: float
               method: str = "normal", cloud_ply: Optional[str] = None, device: str = "cuda", min_component: int = 0,
               keep_largest: int = 0, simplify: float = 0.0, placement: str = "quadric", sample: float = 0.0,
               surface_ply: Optional[str] = None, weight: str = "one", interp: bool = False, interp_jump: float = 0.05,
+              smooth: int = 0, smooth_lambda: float = 0.5, smooth_mu: float = -0.53, smooth_max_move: float = 0.0,
               **fusion_options) -> Dict[str, object]:
     """One scan from saved depth maps to a mesh at ``plyfilename``: the fusion pass of :func:`fusion.filter_depth` (``method``
     "normal" or "dynamic" and its ``fusion_options``), then allocation from every view's kept points, integration of the fused
@@ -809,8 +954,10 @@ def mesh_scan(pair_folder: str, scan_folder: str, plyfilename: str, voxel: float
     ``sample``: a spacing > 0 also writes the sampled surface of the mesh written (:func:`sample_mesh`) as a cloud
     at ``surface_ply``; at 0 nothing of that runs.  ``weight`` / ``interp`` / ``interp_jump``: the weighted, interpolating
     integration of :func:`mesh_views`; the confidence of the conf modes is the view's last-stage confidence map.
+    ``smooth``: iterations > 0 send the mesh, after the clean-up and before the simplification, through :func:`smooth_mesh` with
+    ``smooth_lambda``, ``smooth_mu`` and ``smooth_max_move``; at 0 nothing of that runs.
     -> {"vertices", "faces", "blocks": counts, "cloud": filter_depth's result, "mesh": the mesh dict written, still on the device
-    (render.render_scan takes it)[, "clean": clean_mesh's info][, "simplify": simplify_mesh's info][, "sample": sample_mesh's
+    (render.render_scan takes it)[, "clean": clean_mesh's info][, "smooth": smooth_mesh's info][, "simplify": simplify_mesh's info][, "sample": sample_mesh's
     info and the spacing]}."""
     from .fusion import filter_depth
     if method == "gipuma":
@@ -822,28 +969,34 @@ def mesh_scan(pair_folder: str, scan_folder: str, plyfilename: str, voxel: float
         raise ValueError(f"mesh_scan: min_component and keep_largest must be >= 0, got {min_component} and {keep_largest}")
     simplify = _check_simplify(simplify, placement, "mesh_scan")
     sample = _check_sample(sample, surface_ply, "mesh_scan")
+    smooth = _check_smooth(smooth, smooth_lambda, smooth_mu, smooth_max_move, "mesh_scan")
     interp_jump = _check_weighting(weight, interp, interp_jump, "mesh_scan")
     views: list = []
     cloud = filter_depth(pair_folder, scan_folder, cloud_ply, device=device, method=method, collect=views, **fusion_options)
     mesh, vol = mesh_views(views, voxel, trunc, min_weight, device, weight, interp, interp_jump)
     clean = (min_component, keep_largest) if int(min_component) > 0 or int(keep_largest) > 0 else None
-    return dict(_finish(mesh, plyfilename, clean, simplify, placement, sample, surface_ply), blocks=vol.n_blocks, cloud=cloud)
+    return dict(_finish(mesh, plyfilename, clean, smooth, simplify, placement, sample, surface_ply), blocks=vol.n_blocks, cloud=cloud)
 
 
 def clean_file(src_ply: str, dst_ply: str, min_component: int = 0, keep_largest: int = 0, device: str = "cuda",
                simplify: float = 0.0, placement: str = "quadric", sample: float = 0.0,
-               surface_ply: Optional[str] = None) -> Dict[str, object]:
+               surface_ply: Optional[str] = None, smooth: int = 0, smooth_lambda: float = 0.5, smooth_mu: float = -0.53,
+               smooth_max_move: float = 0.0) -> Dict[str, object]:
     """A saved mesh through :func:`clean_mesh`, then, with ``simplify`` > 0, through :func:`simplify_mesh`, and back into a file
     (``dst_ply`` may be ``src_ply``): what one runs while tuning the threshold or the cell, without the fusion.  With ``simplify``
     alone (both clean-up options at 0) the file goes through :func:`simplify_mesh` only, as in :func:`mesh_scan`.  ``sample`` > 0
-    also writes the sampled surface of the mesh written to ``surface_ply``, as :func:`mesh_scan` does.
-    -> {"vertices", "faces", "mesh"[, "clean"][, "simplify"][, "sample"]} as :func:`mesh_scan`."""
+    also writes the sampled surface of the mesh written to ``surface_ply``, as :func:`mesh_scan` does.  ``smooth`` > 0 sends it
+    through :func:`smooth_mesh` before the simplification, as :func:`mesh_scan` does; with ``smooth`` alone, or with ``smooth`` and
+    ``simplify``, the clean-up is skipped as with ``simplify`` alone.
+    -> {"vertices", "faces", "mesh"[, "clean"][, "smooth"][, "simplify"][, "sample"]} as :func:`mesh_scan`."""
     simplify = _check_simplify(simplify, placement, "clean_file")
     sample = _check_sample(sample, surface_ply, "clean_file")
+    smooth = _check_smooth(smooth, smooth_lambda, smooth_mu, smooth_max_move, "clean_file")
     dev = torch.device(device)
     v, c, f = (torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in read_mesh_ply(src_ply))
-    clean = (min_component, keep_largest) if simplify == 0 or int(min_component) > 0 or int(keep_largest) > 0 else None
-    return _finish({"vertices": v, "colors": c, "faces": f}, dst_ply, clean, simplify, placement, sample, surface_ply)
+    alone = simplify == 0 and smooth is None
+    clean = (min_component, keep_largest) if alone or int(min_component) > 0 or int(keep_largest) > 0 else None
+    return _finish({"vertices": v, "colors": c, "faces": f}, dst_ply, clean, smooth, simplify, placement, sample, surface_ply)
 
 
 def format_mesh(info: Dict[str, object]) -> str:
@@ -854,6 +1007,12 @@ def format_mesh(info: Dict[str, object]) -> str:
         c = info["clean"]
         text += (f"; removed {c['components'][0] - c['components'][1]} of {c['components'][0]} components and "
                  f"{c['faces'][0] - c['faces'][1]} of {c['faces'][0]} faces (the largest has {c['largest']})")
+    if "smooth" in info:
+        s = info["smooth"]
+        text += (f"; smoothed {s['iterations']} iterations (lambda {s['lam']:g}, mu {s['mu']:g}): {s['boundary']} boundary, "
+                 f"{s['isolated']} isolated vertices, largest move {s['max_move']:.6g}")
+        if s.get("limit", 0) > 0:
+            text += f", {s['clamped']} clamped to {s['limit']:g}"
     if "simplify" in info:
         s = info["simplify"]
         text += (f"; simplified {s['vertices'][0]} -> {s['vertices'][1]} vertices and {s['faces'][0]} -> {s['faces'][1]} faces "
@@ -866,7 +1025,7 @@ def format_mesh(info: Dict[str, object]) -> str:
 
 # ---------------------------------------------------------------------------------------------------------------------- CLI
 def add_mesh_args(ap: argparse.ArgumentParser, required: bool = False) -> None:
-    """The options of DESIGN §1.9, §1.11, §1.12, §1.13 and §1.14, shared with ``infer --fuse``."""
+    """The options of DESIGN §1.9 and §1.11 to §1.15, shared with ``infer --fuse``."""
     ap.add_argument("--mesh_voxel", type=float, default=None, required=required, metavar="SIZE",
                     help="write <outdir>/<scan>_mesh.ply: a triangle mesh from a TSDF volume with this lattice spacing (world units)")
     ap.add_argument("--mesh_trunc", type=float, default=None, metavar="T",
@@ -883,6 +1042,15 @@ def add_mesh_args(ap: argparse.ArgumentParser, required: bool = False) -> None:
     ap.add_argument("--mesh_simplify_placement", default="quadric", choices=list(PLACEMENTS),
                     help="--mesh_simplify: a cell's vertex at the minimiser of its faces' quadric error (edges and corners "
                          "survive) or at the mean of its vertices")
+    ap.add_argument("--mesh_smooth", type=int, default=None, metavar="ITER",
+                    help="--mesh_voxel: smooth the mesh before it is simplified and written: ITER iterations (1..1000) of the "
+                         "lambda|mu filter, which moves the vertices and nothing else")
+    ap.add_argument("--mesh_smooth_lambda", type=float, default=None, metavar="L",
+                    help="--mesh_smooth: the step towards the neighbours' mean, in (0, 1] (default 0.5)")
+    ap.add_argument("--mesh_smooth_mu", type=float, default=None, metavar="M",
+                    help="--mesh_smooth: the step back that keeps the volume, in [-1, 0] (default -0.53; 0: plain Laplacian)")
+    ap.add_argument("--mesh_smooth_max_move", type=float, default=None, metavar="D",
+                    help="--mesh_smooth: no vertex ends farther than D (world units) from where it was (default: no limit)")
     ap.add_argument("--mesh_sample", type=float, default=None, metavar="SPACING",
                     help="--mesh_voxel: also write <outdir>/<scan>_surface.ply, the surface of the mesh written as a cloud: the "
                          "centroids of every face's sub-triangles with edges of at most SPACING (world units)")
@@ -915,8 +1083,8 @@ def check_weight_args(ap: argparse.ArgumentParser, args, allowed: bool) -> float
 
 
 def check_clean_args(ap: argparse.ArgumentParser, args, allowed: bool) -> None:
-    """ap.error for a negative clean-up option, a non-positive --mesh_simplify or --mesh_sample, or for one given where no mesh is
-    made (``allowed`` false)."""
+    """ap.error for a negative clean-up option, a non-positive --mesh_simplify or --mesh_sample, bad --mesh_smooth values, one of
+    --mesh_smooth's options without it, or for any of them given where no mesh is made (``allowed`` false)."""
     if args.mesh_min_component < 0 or args.mesh_keep_largest < 0:
         ap.error(f"--mesh_min_component and --mesh_keep_largest must be >= 0, got {args.mesh_min_component} and "
                  f"{args.mesh_keep_largest}")
@@ -932,6 +1100,26 @@ def check_clean_args(ap: argparse.ArgumentParser, args, allowed: bool) -> None:
             ap.error(str(e))
         if not allowed:
             ap.error(f"--{option} {does} the mesh of --mesh_voxel: give --mesh_voxel SIZE (or, in mesh, --from_mesh FILE) as well")
+    given = [name for name in ("mesh_smooth", "mesh_smooth_lambda", "mesh_smooth_mu", "mesh_smooth_max_move")
+             if getattr(args, name) is not None]
+    if given and not allowed:
+        ap.error(f"--{', --'.join(given)}: these options smooth the mesh of --mesh_voxel: give --mesh_voxel SIZE (or, in mesh, "
+                 "--from_mesh FILE) as well")
+    if given and args.mesh_smooth is None:
+        ap.error(f"--{', --'.join(given)} belong to --mesh_smooth ITER")
+    if given:
+        try:
+            check_smooth(args.mesh_smooth, *smooth_args(args)[1:], what="--mesh_smooth")
+        except ValueError as e:
+            ap.error(str(e))
+
+
+def smooth_args(args):
+    """The parsed --mesh_smooth options -> (smooth, smooth_lambda, smooth_mu, smooth_max_move) for :func:`mesh_scan`: 0 iterations
+    without --mesh_smooth, the defaults for what was not given."""
+    return (args.mesh_smooth or 0, 0.5 if args.mesh_smooth_lambda is None else args.mesh_smooth_lambda,
+            -0.53 if args.mesh_smooth_mu is None else args.mesh_smooth_mu,
+            0.0 if args.mesh_smooth_max_move is None else args.mesh_smooth_max_move)
 
 
 def main(argv=None) -> Dict[str, Dict[str, object]]:
@@ -951,7 +1139,7 @@ def main(argv=None) -> Dict[str, Dict[str, object]]:
     add_mesh_args(ap)
     ap.add_argument("--from_mesh", default=None, metavar="FILE",
                     help="instead of --mesh_voxel: clean this saved mesh ({scan} is replaced) with --mesh_min_component / "
-                         "--mesh_keep_largest, simplify it with --mesh_simplify, and write <outdir>/<scan>_mesh.ply, without any "
+                         "--mesh_keep_largest, smooth it with --mesh_smooth, simplify it with --mesh_simplify, and write <outdir>/<scan>_mesh.ply, without any "
                          "fusion")
     args = ap.parse_args(argv)
     if args.mesh_voxel is None and args.from_mesh is None and args.mesh_sample is not None:
@@ -973,7 +1161,8 @@ def main(argv=None) -> Dict[str, Dict[str, object]]:
             out[scan] = clean_file(args.from_mesh.format(scan=scan), os.path.join(args.outdir, f"{scan}_mesh.ply"),
                                    args.mesh_min_component, args.mesh_keep_largest, device=args.device,
                                    simplify=args.mesh_simplify or 0.0, placement=args.mesh_simplify_placement,
-                                   sample=args.mesh_sample or 0.0, surface_ply=os.path.join(args.outdir, f"{scan}_surface.ply"))
+                                   sample=args.mesh_sample or 0.0, surface_ply=os.path.join(args.outdir, f"{scan}_surface.ply"),
+                                   **dict(zip(SMOOTH_KEYS, smooth_args(args))))
             print(f"{scan}_mesh.ply: {format_mesh(out[scan])}", flush=True)
         return out
     for scan in scans:
@@ -983,7 +1172,8 @@ def main(argv=None) -> Dict[str, Dict[str, object]]:
                          keep_largest=args.mesh_keep_largest, simplify=args.mesh_simplify or 0.0,
                          placement=args.mesh_simplify_placement, sample=args.mesh_sample or 0.0,
                          surface_ply=os.path.join(args.outdir, f"{scan}_surface.ply"), weight=args.mesh_weight,
-                         interp=args.mesh_interp, interp_jump=interp_jump, conf=_floats(args.conf, 3, "--conf"),
+                         interp=args.mesh_interp, interp_jump=interp_jump, **dict(zip(SMOOTH_KEYS, smooth_args(args))),
+                         conf=_floats(args.conf, 3, "--conf"),
                          thres_disp=args.thres_disp, thres_view=args.thres_view, dist_base=args.dyn_dist_base,
                          rel_base=args.dyn_rel_base, n_views=tuple(int(v) for v in _floats(args.dyn_views, 2, "--dyn_views")))
         out[scan] = info

@@ -884,6 +884,60 @@ int cds_mesh_simplify_gather(const float* positions, const unsigned* colors, lon
                              float* vertices_out, unsigned char* colors_out, int* faces_out, void* stream);
 
 /*
+ * Smoothing of a triangle mesh: the Taubin lambda|mu filter with uniform weights (csrc/mesh_smooth.hip).  Only the
+ * vertex positions change; faces, colours, counts and order stay bit for bit.
+ *
+ * Inputs.  vertices float32 [V][3], all finite; faces int32 [F][3]; iterations in 1..1000; lam in (0, 1]; mu in [-1, 0];
+ *   max_move >= 0, finite.
+ * 1. Valid faces and edges.  A face is valid when its three indices are in [0, V); another is skipped.  A valid face has three
+ *      edge slots (0,1), (1,2), (2,0); a slot whose two corners are equal is dropped.  The multiplicity of the undirected edge
+ *      {i,j} is the number of slots over all valid faces that hold it.
+ * 2. Boundary.  An edge of multiplicity 1 is a boundary edge; a vertex with at least one boundary edge is a boundary vertex.
+ * 3. Neighbours.  N(i) of an interior vertex: the distinct j with an edge {i,j}.  N(i) of a boundary vertex: only the j whose
+ *      edge {i,j} is a boundary edge, so an open border relaxes along itself and is never pulled inward.  A vertex with an empty
+ *      N(i) (in no face, or only in slots that were dropped) is ISOLATED and keeps its bits.
+ * 4. One step with the factor s (Jacobi: every vertex reads the positions from before the step).  Per coordinate,
+ *      m_i = (sum over j in N(i), ascending j, of (double)p_j) / (double)|N(i)|, the sum sequential in fp64 from +0.0;
+ *      p_i' = (float)((double)p_i + s * (m_i - (double)p_i)), in that operation order: one round-to-nearest-even cast per step,
+ *      no contraction (-ffp-contract=off).  Positions are fp32 between steps.
+ * 5. One iteration: a step with lam, then, unless mu == 0, a step with mu.  mu == 0 is the plain Laplacian filter.
+ * 6. max_move = D > 0, once after the last iteration, against the input positions p0: d = (double)p - (double)p0,
+ *      n2 = (dx dx + dy dy) + dz dz; where n2 > D D: p = (float)(p0 + d * (D / sqrt(n2))) per coordinate.  D == 0: no limit.
+ * 7. Statistics.  n2 of rule 6, taken before the clamp, per vertex; the caller takes its maximum (a maximum does not depend
+ *      on the order) and counts the clamped, boundary and isolated vertices.
+ *
+ * The adjacency is a CSR with slack: start int32 [V + 1], the exclusive prefix sum of the entries each vertex receives (two per
+ * kept slot, one at either end); vertex v owns nbr[start[v] .. start[v + 1]) and, after cds_mesh_adj_finish, its first deg[v]
+ * entries are N(v), ascending.  n_entries = start[V] <= 6 F.
+ * cds_mesh_adj_small: CDS_MESH_ADJ_SMALL.
+ * cds_mesh_adj_count: count int32 [V], zeroed by the caller: the entries of each vertex (integer atomics).
+ * cds_mesh_adj_fill: cursor int32 [V], zeroed by the caller; writes the other end of every kept slot into the segment of each end.
+ *   The order inside a segment is the hardware's; cds_mesh_adj_finish removes it.  An entry past its segment is not written.
+ * cds_mesh_adj_finish: one thread per vertex sorts its segment when it has at most CDS_MESH_ADJ_SMALL entries (the caller has
+ *   sorted every longer segment ascending: there are few, and one sort of just their entries serves them all), reads the
+ *   multiplicity of {v,j} off the run of j, applies rules 2 and 3 in place and writes deg int32 [V] and flags uint8 [V]
+ *   (CDS_MESH_ADJ_BOUNDARY | CDS_MESH_ADJ_ISOLATED).  A vertex whose offsets lie outside [0, n_entries] is written as isolated.
+ * cds_mesh_smooth_step_f32: rule 4 from `in` to `out`, float32 [V][3] each, in != out.  A vertex with deg 0, with a segment outside
+ *   [start[v], start[v + 1]] or with a neighbour outside [0, V) copies its bits.
+ * cds_mesh_smooth_limit_f32: rules 6 and 7.  original: p0; vertices: p, clamped in place; move2_out fp64 [V]; clamped_out uint8 [V].
+ *   CDS_EINVAL: a count < 0 or >= 2^31; 3 n_faces 2 >= 2^31 entries; n_entries > 6 n_faces; in == out or original == vertices; a
+ *   factor that is not finite; max_move negative or not finite; a null required pointer (an empty input returns 0 first).
+ */
+#define CDS_MESH_ADJ_SMALL 64
+#define CDS_MESH_ADJ_BOUNDARY 1
+#define CDS_MESH_ADJ_ISOLATED 2
+int cds_mesh_adj_small(void);
+int cds_mesh_adj_count(const int* faces, long long n_faces, long long n_vertices, int* count, void* stream);
+int cds_mesh_adj_fill(const int* faces, long long n_faces, long long n_vertices, const int* start, int* cursor, int* nbr,
+                      long long n_entries, void* stream);
+int cds_mesh_adj_finish(long long n_vertices, const int* start, int* nbr, long long n_entries, int* deg, unsigned char* flags,
+                        void* stream);
+int cds_mesh_smooth_step_f32(const float* in, float* out, long long n_vertices, const int* start, const int* deg, const int* nbr,
+                             double factor, void* stream);
+int cds_mesh_smooth_limit_f32(const float* original, float* vertices, long long n_vertices, double max_move, double* move2_out,
+                              unsigned char* clamped_out, void* stream);
+
+/*
  * Surface samples of a triangle mesh: a dense, deterministic point set from the faces (csrc/mesh_sample.hip).
  *
  * Inputs.  vertices float32 [V][3]; colors uint8 [V][3]; faces int32 [F][3], every index in [0, V) (the host refuses another

@@ -979,8 +979,8 @@ extern "C" int cds_conv3d_sf16_f32(const float* x, const void* weight_split, con
   const int r = cds_conv3d_zmg_dispatch(x, weight_split, bias, out, Cin, Cout, D, H, W, stride == CDS_SBF_PAIR ? 1 : stride,
                                         stride == CDS_SBF_PAIR, act, st, in_bound, w_inv_scale, out_bound);
   if (r != CDS_ZMG_UNSUPPORTED) return r;
-  // the tiled kernels in split-f16: the deep layers (conv5 32 -> 64 stride 2; conv4 32 -> 32 and conv6 64 -> 64 where the volume is too
-  // small for the z-march or CDS_ZMG_DEEP=0)
+  // the tiled kernels in split-f16: the deep layers (conv4 32 -> 32, conv5 32 -> 64 stride 2 and conv6 64 -> 64) where the volume is
+  // too small for the z-march or CDS_ZMG_DEEP=0
   const int mb = (Cout + 15) / 16;
   // few tiles (the cascade stages' deep layers): one 16-cout block per workgroup, mb workgroups per tile (CDS_SBF_YSPLIT=0: never)
   const int s_ = stride, Do = (D - 1) / s_ + 1, Ho = (H - 1) / s_ + 1, Wo = (W - 1) / s_ + 1;

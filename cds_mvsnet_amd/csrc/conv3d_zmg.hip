@@ -5,8 +5,9 @@
 // the weights of every K-step stream through the consumer waves' vector-memory queue.  Here a workgroup owns a column of
 // TXO x TYO output voxels and MARCHES along z (the layout conv0's conv3d_sbf_zm_kernel introduced, generalised):
 //   * the staged input is a RING of z-planes in LDS ([plane][8-channel slice][row][x] x 48 B, the [term][8] bf16 position
-//     format of sbf_common.hpp); every input plane is loaded, split and stored ONCE per column: 1.33 (stride 1, 32 x 8) or
-//     9.1-9.3 (stride 2) staged positions per output voxel and no re-read along z;
+//     format of sbf_common.hpp; split-f16 configurations may ask for two 16-byte term planes per slice instead: ZG::P32);
+//     every input plane is loaded, split and stored ONCE per column: 1.33 (stride 1, 32 x 8) or 9.1-9.3 (stride 2) staged
+//     positions per output voxel and no re-read along z;
 //   * ONE workgroup barrier per G output planes whatever the channel count: all slices of a plane are resident together;
 //   * the weights never move: the four consumer waves split the K dimension (8-channel rounds) and the 16-cout blocks between
 //     them, so every wave keeps the <= 27 weight vectors of ITS (round, cout block) in registers for the whole kernel
@@ -37,7 +38,7 @@ __device__ __attribute__((aligned(32))) float g_zmg_zeros[8];   // what an out-o
 // workgroups of a column stages the whole input ring and computes MB / YS cout blocks: Cout = 64).  PF_: K-steps the LDS operand
 // reads run ahead of their MFMAs (2: a wave with ONE N-tile per step has only three MFMAs to cover an LDS round trip).
 template <int S_, int RD_, int MB_, bool PAIR_, int TXO_, int TYO_, int G_, int NG_, int CW_ = 4, bool F16_ = false, int RPW_ = 1,
-          int YS_ = 1, int PF_ = 1>
+          int YS_ = 1, int PF_ = 1, bool P32_ = false>
 struct ZG {
   static constexpr int S = S_, RD = RD_, MB = MB_, TXO = TXO_, TYO = TYO_, G = G_, NG = NG_;
   static constexpr bool F16 = F16_;
@@ -58,7 +59,14 @@ struct ZG {
   static constexpr int IX = (TXO - 1) * S + 3, IY = (TYO - 1) * S + 3;
   static constexpr int IXH = DEINT ? (IX + 1) / 2 : 0;            // x parities de-interleaved (stride 2, pair columns)
   static constexpr int IXP = DEINT ? 2 * IXH : IX;
-  static constexpr int SLICEB = IY * IXP * POSB, PLANEB = RD * SLICEB;
+  // P32_ (split-f16 only): 32-byte positions, term-planar inside a slice ([term][row][x] x 16 B) instead of the 48-byte
+  // [term 0 | term 1 | unused] position: the ring shrinks by a third (conv5: 163 200 -> 108 800 B, which is what lets a stride-2
+  // column of 32 input channels fit at all), 16 lanes on 16 consecutive x still read 16 different 16-byte bank groups, and the tap
+  // offsets stay compile-time constants.  PB = bytes from a position to its x neighbour, TB = from its term 0 to its term 1.
+  static constexpr bool P32 = P32_;
+  static_assert(!P32_ || F16_, "the 32-byte position holds two terms");
+  static constexpr int PB = P32_ ? 16 : POSB, TB = P32_ ? IY * IXP * 16 : 16;
+  static constexpr int SLICEB = IY * IXP * (P32_ ? 32 : POSB), PLANEB = RD * SLICEB;
   static constexpr int NINIT = 3 - S;                             // planes below the first stage's new ones
   static constexpr int NRES = S * (G - 1) + 3, NNEW = S * G, R = NRES + NNEW;
   static constexpr int RINGB = R * PLANEB;
@@ -76,7 +84,7 @@ struct ZG {
   static constexpr int tap_kz(int t, int gg) { return tap_of(t, gg) / (3 * KW); }
   static constexpr int tap_off(int t, int gg) {                   // byte offset of the tap inside a slice
     const int tap = tap_of(t, gg), ky = (tap / KW) % 3, kx = tap % KW;
-    return (ky * IXP + (DEINT ? ((kx & 1) * IXH + (kx >> 1)) : kx)) * POSB;
+    return (ky * IXP + (DEINT ? ((kx & 1) * IXH + (kx >> 1)) : kx)) * PB;
   }
   static constexpr int LDSB = RINGB + 2 * XCH1;
   static_assert(LDSB <= 160 * 1024, "LDS budget");
@@ -137,7 +145,7 @@ __global__ __launch_bounds__(Cfg::THREADS, 1) void conv3d_zmg_kernel(const float
       const int gy = gy0 + row, gx = gx0 + c;
       const bool exists = p < Cfg::NITEM && c < Cfg::IX;
       s_pl[h] = pl;
-      s_dst[h] = rd * Cfg::SLICEB + (row * Cfg::IXP + q) * POSB;
+      s_dst[h] = rd * Cfg::SLICEB + (row * Cfg::IXP + q) * Cfg::PB;
       s_off[h] = ((long long)gy * W + gx) * Cin + rd * 8;
       if (exists && (unsigned)gy < (unsigned)H && (unsigned)gx < (unsigned)W) okmask |= 1u << h;
       if (!exists) s_pl[h] = -1;
@@ -163,7 +171,8 @@ __global__ __launch_bounds__(Cfg::THREADS, 1) void conv3d_zmg_kernel(const float
         if (h + 1 == PPT && s_pl[h] < 0) continue;                 // only the last item of a thread can be missing
         int slot = slot0 + (s_pl[h] < 0 ? 0 : s_pl[h]);
         slot = slot >= R ? slot - R : slot;
-        if (F16) split_store8_f16(lds + slot * Cfg::PLANEB + s_dst[h], va[set][h], vb[set][h], xs);
+        if (Cfg::P32) split_store8_f16_planar(lds + slot * Cfg::PLANEB + s_dst[h], Cfg::TB, va[set][h], vb[set][h], xs);
+        else if (F16) split_store8_f16(lds + slot * Cfg::PLANEB + s_dst[h], va[set][h], vb[set][h], xs);
         else split_store8(lds + slot * Cfg::PLANEB + s_dst[h], va[set][h], vb[set][h]);
       }
     };
@@ -176,12 +185,10 @@ __global__ __launch_bounds__(Cfg::THREADS, 1) void conv3d_zmg_kernel(const float
       const int gz = zin0 + pl, gy = gy0 + row, gx = gx0 + c;
       const bool ok = c < Cfg::IX && (unsigned)gz < (unsigned)D && (unsigned)gy < (unsigned)H && (unsigned)gx < (unsigned)W;
       const float* __restrict__ src = ok ? x + (((long long)gz * H + gy) * W + gx) * Cin + rd * 8 : g_zmg_zeros;
-      if (F16)
-        split_store8_f16(lds + pl * Cfg::PLANEB + rd * Cfg::SLICEB + (row * Cfg::IXP + q) * POSB, *reinterpret_cast<const float4*>(src),
-                         *reinterpret_cast<const float4*>(src + 4), xs);
-      else
-        split_store8(lds + pl * Cfg::PLANEB + rd * Cfg::SLICEB + (row * Cfg::IXP + q) * POSB, *reinterpret_cast<const float4*>(src),
-                     *reinterpret_cast<const float4*>(src + 4));
+      unsigned char* dst = lds + pl * Cfg::PLANEB + rd * Cfg::SLICEB + (row * Cfg::IXP + q) * Cfg::PB;
+      if (Cfg::P32) split_store8_f16_planar(dst, Cfg::TB, *reinterpret_cast<const float4*>(src), *reinterpret_cast<const float4*>(src + 4), xs);
+      else if (F16) split_store8_f16(dst, *reinterpret_cast<const float4*>(src), *reinterpret_cast<const float4*>(src + 4), xs);
+      else split_store8(dst, *reinterpret_cast<const float4*>(src), *reinterpret_cast<const float4*>(src + 4));
     }
     issue(0, 0);
     if (nstages > 1) issue(1, 1);
@@ -221,8 +228,8 @@ __global__ __launch_bounds__(Cfg::THREADS, 1) void conv3d_zmg_kernel(const float
 #endif
   // byte offset of this lane inside a slice: its slice (round k), first row of its part, voxel j; PAIR: + the x' of its lane group
   // (x' = 0, 2, 1, 3: de-interleaved parity plane + half index), the (kz, ky) of a K-step being uniform
-  const int lane_base = k * Cfg::RPW * Cfg::SLICEB + (part * Cfg::ROWS * S * Cfg::IXP + j) * POSB +
-                        (PAIR ? (((g & 1) * 2 + (g >> 1)) & 1) * Cfg::IXH * POSB + ((((g & 1) * 2 + (g >> 1))) >> 1) * POSB : 0);
+  const int lane_base = k * Cfg::RPW * Cfg::SLICEB + (part * Cfg::ROWS * S * Cfg::IXP + j) * Cfg::PB +
+                        (PAIR ? (((g & 1) * 2 + (g >> 1)) & 1) * Cfg::IXH * Cfg::PB + ((((g & 1) * 2 + (g >> 1))) >> 1) * Cfg::PB : 0);
   // this wave's weights: [round k RPW + rr][K-step][cout block][term][lane]
   constexpr int RPW = Cfg::RPW;
   const int mbg = (Cfg::YS > 1 ? blockIdx.y * Cfg::MBS : 0) + mbi;   // cout block in the layer
@@ -244,6 +251,15 @@ __global__ __launch_bounds__(Cfg::THREADS, 1) void conv3d_zmg_kernel(const float
   const int oy0 = ty_i * Cfg::TYO + part * Cfg::ROWS;
   const int ox0 = tx_i * Cfg::TXO + (PAIR ? 2 * j + (g >> 1) : j);
   float* const obase = out + ((size_t)((size_t)z0 * Ho + oy0) * Wo + ox0) * Cout + co;   // this lane's voxel of N-tile 0, stage 0
+  // P32 configurations (168-register budget, 112 of them weights): the same address as a wave-uniform 64-bit part (SGPRs) + a 32-bit
+  // lane offset inside the column's first row, instead of 64-bit per-lane addresses that the compiler keeps in VGPRs across the stage
+  // loop (the no-K-split conv2 spilled four registers for them)
+  float* const obase_u = out + ((size_t)((size_t)z0 * Ho + oy0) * Wo + tx_i * Cfg::TXO) * Cout;
+  const unsigned olane = (unsigned)((ox0 - tx_i * Cfg::TXO) * Cout + co);
+  auto out_ptr = [&](int pl, int r, int xt) -> float* {
+    const size_t o = ((size_t)((size_t)pl * Ho + r) * Wo + xt * XW) * Cout;
+    return Cfg::P32 ? obase_u + o + olane : obase + o;
+  };
   bool lane_ok[Cfg::XT];
 #pragma unroll
   for (int xt = 0; xt < Cfg::XT; ++xt) lane_ok[xt] = ox0 + xt * XW < Wo && co < Cout;
@@ -257,7 +273,7 @@ __global__ __launch_bounds__(Cfg::THREADS, 1) void conv3d_zmg_kernel(const float
       o.x = fmaxf(o.x, 0.f); o.y = fmaxf(o.y, 0.f); o.z = fmaxf(o.z, 0.f); o.w = fmaxf(o.w, 0.f);
     }
     if (F16) amax = fmaxf(fmaxf(amax, fmaxf(fabsf(o.x), fabsf(o.y))), fmaxf(fabsf(o.z), fabsf(o.w)));
-    sbf_store4(obase + ((size_t)((size_t)(st * G + i) * Ho + r) * Wo + xt * XW) * Cout, o);
+    sbf_store4(out_ptr(st * G + i, r, xt), o);
   };
   unsigned char* xch = lds + Cfg::RINGB;                 // [buffer][sender wave][N-tile of its partner's half][lane] x 16 B
   constexpr int NH = NTW / 2;
@@ -277,7 +293,7 @@ __global__ __launch_bounds__(Cfg::THREADS, 1) void conv3d_zmg_kernel(const float
       o.x = fmaxf(o.x, 0.f); o.y = fmaxf(o.y, 0.f); o.z = fmaxf(o.z, 0.f); o.w = fmaxf(o.w, 0.f);
     }
     if (F16) amax = fmaxf(fmaxf(amax, fmaxf(fabsf(o.x), fabsf(o.y))), fmaxf(fabsf(o.z), fabsf(o.w)));
-    sbf_store4(obase + ((size_t)((size_t)(st * G + i) * Ho + r) * Wo + xt * XW) * Cout, o);
+    sbf_store4(out_ptr(st * G + i, r, xt), o);
   };
   const int xgrp = (wave / Cfg::KSPL) * NTW;            // first exchange slot row of this wave's (cout block, row part)
   // finish stage sp: bias / ReLU / store of this wave's outputs.  K split: N-tiles [k NH, (k + 1) NH) = round 0's partial sum +
@@ -345,10 +361,10 @@ __global__ __launch_bounds__(Cfg::THREADS, 1) void conv3d_zmg_kernel(const float
       for (int q = 0; q < NG; ++q) {
         const int n = grp * NG + q, i = n % G, rx = n / G, xt = rx % Cfg::XT, r = rx / Cfg::XT;
         // PAIR: K-step t = (kz, ky) = (t / 3, t % 3)
-        const unsigned char* b = lds + (PAIR ? vpl[PAIR ? S * i + t / 3 : 0] + (t % 3) * Cfg::IXP * POSB : vaddr[PAIR ? 0 : t][PAIR ? 0 : i]) +
-                                 (r * S * Cfg::IXP + xt * 16) * POSB + rr * Cfg::SLICEB;
+        const unsigned char* b = lds + (PAIR ? vpl[PAIR ? S * i + t / 3 : 0] + (t % 3) * Cfg::IXP * Cfg::PB : vaddr[PAIR ? 0 : t][PAIR ? 0 : i]) +
+                                 (r * S * Cfg::IXP + xt * 16) * Cfg::PB + rr * Cfg::SLICEB;
         bd[buf][q][0].u = *reinterpret_cast<const uint4*>(b);
-        bd[buf][q][1].u = *reinterpret_cast<const uint4*>(b + 16);
+        bd[buf][q][1].u = *reinterpret_cast<const uint4*>(b + Cfg::TB);
         if (!F16) bd[buf][q][NT - 1].u = *reinterpret_cast<const uint4*>(b + 32);
       }
     };
@@ -454,17 +470,20 @@ int cds_conv3d_zmg_dispatch(const float* x, const void* wsp, const float* bias, 
       if (Cin == 32) return launch_zmg<ZG<1, 4, 1, true, 32, 3, 1, 3, 4, true>>(x, wsp, bias, out, Cout, D, H, W, act, st, in_bound, w_inv, out_bound);
       return CDS_ZMG_UNSUPPORTED;
     }
+    // conv2: both rounds of weights in one wave like conv3 below (no exchange through LDS, no finalising step), on the 32-byte ring
+    // with the uniform-base output address: 162 VGPRs, no scratch (with 64-bit per-lane output addresses: 168 and 2-4 spilled);
+    // profiles/zmarch_conv5.md: 325-338 -> 306-316 us in the M1 step
     if (stride == 1 && Cin == 16 && Cout == 16)
-      return launch_zmg<ZG<1, 2, 1, false, 32, 8, 1, 1, 8, true>>(x, wsp, bias, out, Cout, D, H, W, act, st, in_bound, w_inv, out_bound);
+      return launch_zmg<ZG<1, 2, 1, false, 32, 8, 1, 1, 8, true, 2, 1, 1, true>>(x, wsp, bias, out, Cout, D, H, W, act, st, in_bound, w_inv, out_bound);
     if (stride == 2 && Cin == 8 && Cout == 16)
       return launch_zmg<ZG<2, 1, 1, false, 16, 8, 1, 1, 8, true>>(x, wsp, bias, out, Cout, D, H, W, act, st, in_bound, w_inv, out_bound);
     // conv3: both rounds of weights in one wave (RPW = 2: 112 registers of two fp16 terms, 162 VGPRs) instead of the K split over wave
     // pairs that three bf16 terms need: no exchange through LDS and no finalising step (profiles/zmarch_conv7.md: 180-183 -> 157-162 us)
     if (stride == 2 && Cin == 16 && Cout == 32)
       return launch_zmg<ZG<2, 2, 2, false, 16, 4, 1, 1, 8, true, 2>>(x, wsp, bias, out, Cout, D, H, W, act, st, in_bound, w_inv, out_bound);
-    // The deep stride-1 layers (conv4 32 -> 32, conv6 64 -> 64).  CDS_ZMG_DEEP (A/B knob): 0 = tiled kernels, 1 = z-march where
-    // columns x segments fill the 256 CUs (the few tiles of the cascade stages' deep layers stay on the tiled kernels and their
-    // cout split), 2 = z-march whatever the size.
+    // The deep layers (conv4 32 -> 32, conv5 32 -> 64 stride 2, conv6 64 -> 64).  CDS_ZMG_DEEP (A/B knob): 0 = tiled kernels,
+    // 1 = z-march where columns x segments fill the 256 CUs (the few tiles of the cascade stages' deep layers stay on the tiled
+    // kernels and their cout split), 2 = z-march whatever the size.
     const int deep = cds_env_is("CDS_ZMG", '0') ? 0 : cds_env_int("CDS_ZMG_DEEP", 1);
     const int min_wgs = deep == 2 ? 0 : 256;
     // conv4: K split over four waves x two cout blocks, 16 x 4 columns (ring 81 KB + 2 x 32 KB exchange)
@@ -475,6 +494,12 @@ int cds_conv3d_zmg_dispatch(const float* x, const void* wsp, const float* bias, 
     // wave for a K split over eight waves with one cout block per workgroup (ring 108 KB + 2 x 16 KB exchange)
     if (deep > 0 && stride == 1 && Cin == 64 && Cout == 64)
       return launch_zmg<ZG<1, 8, 4, false, 16, 2, 1, 1, 8, true, 2, 2>>(x, wsp, bias, out, Cout, D, H, W, act, st, in_bound, w_inv, out_bound, min_wgs);
+    // conv5 (32 -> 64, stride 2): 16 x 2 output columns on the 32-byte ring (5 planes of 4 slices x 5 x 34 positions = 108 800 B; at
+    // 48 bytes per position 163 200 B: no stride-2 column of 32 channels fits), K split in two with two rounds of weights per wave
+    // x the four cout blocks = 8 consumer waves of 84 MFMAs per stage (2 x 8 KB exchange), 167 VGPRs; operand reads two K-steps
+    // ahead (PF = 2) would spill 14 of them.  profiles/zmarch_conv5.md: 133-139 us tiled -> 68-80 us in the M1 step
+    if (deep > 0 && stride == 2 && Cin == 32 && Cout == 64)
+      return launch_zmg<ZG<2, 4, 4, false, 16, 2, 1, 1, 8, true, 2, 1, 1, true>>(x, wsp, bias, out, Cout, D, H, W, act, st, in_bound, w_inv, out_bound, min_wgs);
     return CDS_ZMG_UNSUPPORTED;
   }
   const bool off = cds_env_is("CDS_ZMG", '0');   // A/B knob: 0 = tiled kernels only

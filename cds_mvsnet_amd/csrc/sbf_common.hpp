@@ -111,6 +111,16 @@ __device__ __forceinline__ void split_store8_f16(unsigned char* dst, const float
   d4[0] = make_uint4(h[0], h[1], h[2], h[3]);
   d4[1] = make_uint4(l[0], l[1], l[2], l[3]);
 }
+// the same split for a term-planar image: the hi terms at dst, the lo terms term_off bytes further (16 B each; conv3d_zmg.hip, P32)
+__device__ __forceinline__ void split_store8_f16_planar(unsigned char* dst, int term_off, const float4& a, const float4& b, float s) {
+  uint32_t h[4], l[4];
+  split2_f16(a.x, a.y, s, h[0], l[0]);
+  split2_f16(a.z, a.w, s, h[1], l[1]);
+  split2_f16(b.x, b.y, s, h[2], l[2]);
+  split2_f16(b.z, b.w, s, h[3], l[3]);
+  *reinterpret_cast<uint4*>(dst) = make_uint4(h[0], h[1], h[2], h[3]);
+  *reinterpret_cast<uint4*>(dst + term_off) = make_uint4(l[0], l[1], l[2], l[3]);
+}
 // scale of a tensor whose magnitudes are bounded by B: the power of two s with B s in (2^14, 2^15]; B = 0 / not finite -> 1
 __device__ __forceinline__ float sf16_scale(float B) {
   if (!(B > 0.f) || !(B < 3.0e38f)) return 1.0f;

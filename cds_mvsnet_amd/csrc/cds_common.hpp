@@ -58,6 +58,17 @@ static inline int cds_allow_lds(const void* kernel, int bytes, std::atomic<unsig
   return 0;
 }
 
+// Launch of a kernel that may need the opt-in: attr_bytes > 0 = the dynamic-LDS limit to set for Kernel on this device first (the
+// per-device mask is a static of this template: one per kernel instantiation), 0 = the kernel stays below 64 KB.
+template <auto Kernel, class... A>
+static inline int cds_launch_lds(int attr_bytes, dim3 grid, dim3 block, int lds_bytes, hipStream_t st, A... args) {
+  static std::atomic<unsigned long long> lds_ok{0};
+  if (attr_bytes > 0)
+    if (int e_lds = cds_allow_lds(reinterpret_cast<const void*>(Kernel), attr_bytes, lds_ok)) return e_lds;
+  hipLaunchKernelGGL(Kernel, grid, block, lds_bytes, st, args...);
+  return cds_launch_status();
+}
+
 // Bijective XCD-aware remap of a linear workgroup id (guide T1): the dispatcher places block b on
 // XCD b % 8, so consecutive logical tiles are handed to the same XCD to share its private L2.
 __device__ __forceinline__ int cds_xcd_remap(int bid, int nwg) {

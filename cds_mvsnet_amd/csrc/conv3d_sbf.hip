@@ -346,17 +346,10 @@ __global__ __launch_bounds__((FCfg<S, MB, TX_, TZ_, PAIR, WRES_>::THREADS)) void
               const int oz = oz0 + tz, ox = PAIR ? ox0 + txr * 32 + 2 * j + (g >> 1) : ox0 + txr * 16 + j;
               if (oz >= Do || ox >= Wo) continue;
               const size_t base = ((size_t)((size_t)oz * Ho + oy) * Wo + ox) * Cout + co;
-              float4 o = F16 ? make_float4(acc[mb][tl].x * out_mul + bv.x, acc[mb][tl].y * out_mul + bv.y, acc[mb][tl].z * out_mul + bv.z,
-                                           acc[mb][tl].w * out_mul + bv.w)
-                             : make_float4(acc[mb][tl].x + bv.x, acc[mb][tl].y + bv.y, acc[mb][tl].z + bv.z, acc[mb][tl].w + bv.w);
-              if (act == CDS_ACT_RELU) {
-                o.x = fmaxf(o.x, 0.f); o.y = fmaxf(o.y, 0.f); o.z = fmaxf(o.z, 0.f); o.w = fmaxf(o.w, 0.f);
-              }
-              if (skip) {
-                const float4 s4 = *reinterpret_cast<const float4*>(skip + base);
-                o.x = s4.x + o.x; o.y = s4.y + o.y; o.z = s4.z + o.z; o.w = s4.w + o.w;
-              }
-              if (F16) amax = fmaxf(fmaxf(amax, fmaxf(fabsf(o.x), fabsf(o.y))), fmaxf(fabsf(o.z), fabsf(o.w)));
+              float4 o = F16 ? sf16_rescale4(acc[mb][tl], out_mul, bv) : sbf_add4(sbf_f4(acc[mb][tl]), bv);
+              if (act == CDS_ACT_RELU) o = sbf_relu4(o);
+              if (skip) o = sbf_add4(*reinterpret_cast<const float4*>(skip + base), o);
+              if (F16) amax = sbf_amax4(amax, o);
               sbf_store4(out + base, o);
             }
           }
@@ -384,15 +377,10 @@ int launch_fwd(const float* x, const void* wsp, const float* b, const float* ski
   // (a sweep of 4 / 8 / 16 / 32 / 64 at M1 moves single layers by a few percent either way: conv4 likes 8-16, conv6 likes 1)
   int tpw = max(1, min(32, ntiles / (256 * 6)));
   const int nwg = cds_ceil_div(ntiles, tpw);
-  auto kern = conv3d_sbf_kernel<S, MB, TX, TZ, PAIR, WRES_, F16>;
   constexpr int lds_bytes = 2 * Cfg::LDSB;
-  if (lds_bytes > 64 * 1024) {
-    static std::atomic<unsigned long long> lds_ok{0};   // per instantiation
-    if (int e_lds = cds_allow_lds(reinterpret_cast<const void*>(kern), lds_bytes, lds_ok)) return e_lds;
-  }
-  hipLaunchKernelGGL(kern, dim3(nwg, ysplit), dim3(Cfg::THREADS), lds_bytes, st, x, reinterpret_cast<const uint4*>(wsp), b, skip, out, Cin,
-                     Cout, D, H, W, Do, Ho, Wo, act, tx, ty, ntiles, tpw, in_bound, w_inv, out_bound);
-  return cds_launch_status();
+  return cds_launch_lds<conv3d_sbf_kernel<S, MB, TX, TZ, PAIR, WRES_, F16>>(
+      lds_bytes > 64 * 1024 ? lds_bytes : 0, dim3(nwg, ysplit), dim3(Cfg::THREADS), lds_bytes, st, x, reinterpret_cast<const uint4*>(wsp), b,
+      skip, out, Cin, Cout, D, H, W, Do, Ho, Wo, act, tx, ty, ntiles, tpw, in_bound, w_inv, out_bound);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -619,16 +607,10 @@ __global__ __launch_bounds__(256, (MERGE ? CDS_DECONV_SBF_MINW : (MB == 1 ? CDS_
             if (ax >= W) continue;
             const size_t base = (rowbase + 2 * ax + px) * Cout + co;
             const f32x4 a = acc[c][mb][q];
-            float4 o = F16 ? make_float4(a.x * out_mul + bv.x, a.y * out_mul + bv.y, a.z * out_mul + bv.z, a.w * out_mul + bv.w)
-                           : make_float4(a.x + bv.x, a.y + bv.y, a.z + bv.z, a.w + bv.w);
-            if (act == CDS_ACT_RELU) {
-              o.x = fmaxf(o.x, 0.f); o.y = fmaxf(o.y, 0.f); o.z = fmaxf(o.z, 0.f); o.w = fmaxf(o.w, 0.f);
-            }
-            if (skip) {
-              const float4 s4 = SKIP_PF ? skv[SKIP_PF ? c : 0][q] : *reinterpret_cast<const float4*>(skip + base);
-              o.x = s4.x + o.x; o.y = s4.y + o.y; o.z = s4.z + o.z; o.w = s4.w + o.w;
-            }
-            if (F16) amax = fmaxf(fmaxf(amax, fmaxf(fabsf(o.x), fabsf(o.y))), fmaxf(fabsf(o.z), fabsf(o.w)));
+            float4 o = F16 ? sf16_rescale4(a, out_mul, bv) : sbf_add4(sbf_f4(a), bv);
+            if (act == CDS_ACT_RELU) o = sbf_relu4(o);
+            if (skip) o = sbf_add4(SKIP_PF ? skv[SKIP_PF ? c : 0][q] : *reinterpret_cast<const float4*>(skip + base), o);
+            if (F16) amax = sbf_amax4(amax, o);
             acc[c][mb][q] = (f32x4){o.x, o.y, o.z, o.w};
           }
         }
@@ -879,14 +861,9 @@ __global__ __launch_bounds__((DWSCfg<CYT>::THREADS), CDS_DWS_MINW) void deconv3d
             if (ax >= W) continue;
             const size_t base = (rowbase + 2 * ax + px) * Cout + co;
             const f32x4 a = acc[c][q];
-            float4 o = make_float4(a.x + bv.x, a.y + bv.y, a.z + bv.z, a.w + bv.w);
-            if (act == CDS_ACT_RELU) {
-              o.x = fmaxf(o.x, 0.f); o.y = fmaxf(o.y, 0.f); o.z = fmaxf(o.z, 0.f); o.w = fmaxf(o.w, 0.f);
-            }
-            if (skip) {
-              const float4 s4 = skv[c][q];
-              o.x = s4.x + o.x; o.y = s4.y + o.y; o.z = s4.z + o.z; o.w = s4.w + o.w;
-            }
+            float4 o = sbf_add4(sbf_f4(a), bv);
+            if (act == CDS_ACT_RELU) o = sbf_relu4(o);
+            if (skip) o = sbf_add4(skv[c][q], o);
             if (out_planar) {
               const size_t ovol = (size_t)(2 * D) * Ho * Wo;
               float* po = out + (size_t)co * ovol + (rowbase + 2 * ax + px);
@@ -916,11 +893,9 @@ int launch_deconv_ws_t(const float* x, const void* wsp, const float* b, const fl
   int tpw = max(1, min(16, ntiles / (256 * (CYT == 8 ? 1 : 2) * 8)));
   const int nwg = cds_ceil_div(ntiles, tpw);
   const int lds_bytes = (Cin >> 3) * DTab<true>::NKS * 3 * 1024 + 2 * Cfg::LDSB;
-  static std::atomic<unsigned long long> lds_ok{0};
-  if (int e_lds = cds_allow_lds(reinterpret_cast<const void*>(deconv3d_sbf_ws_kernel<CYT>), 160 * 1024, lds_ok)) return e_lds;
-  hipLaunchKernelGGL(deconv3d_sbf_ws_kernel<CYT>, dim3(nwg), dim3(Cfg::THREADS), lds_bytes, st, x, reinterpret_cast<const uint4*>(wsp), b,
-                     skip, out, Cin, Cout, D, H, W, act, out_planar, tx, ty, ntiles, tpw);
-  return cds_launch_status();
+  return cds_launch_lds<deconv3d_sbf_ws_kernel<CYT>>(160 * 1024, dim3(nwg), dim3(Cfg::THREADS), lds_bytes, st, x,
+                                                     reinterpret_cast<const uint4*>(wsp), b, skip, out, Cin, Cout, D, H, W, act, out_planar,
+                                                     tx, ty, ntiles, tpw);
 }
 
 int launch_deconv_ws(const float* x, const void* wsp, const float* b, const float* skip, float* out, int Cin, int Cout, int D, int H,

@@ -1,9 +1,10 @@
-// K4, z-marching form of the split-bf16 3x3x3 convolutions for Cin = 8 / 16 and stride 1 / 2.
+// K4, z-marching form of the 3x3x3 convolutions of CostRegNet, split-bf16 and split-f16: conv0 to conv3 and the three stride-1
+// layers to 8 channels (the "pair" layers: Cin = 8 / 16 / 32) in both arithmetics, conv4 to conv6 in split-f16.
 //
 // What the tiled kernels of conv3d_sbf.hip pay (measured in rounds 2 / 3): a TX x 4 x TZ tile stages 2.4 input positions per
 // output voxel at stride 1 and 11.6 at stride 2 (8 is the minimum), every 8-channel round of a tile is its own barrier stage, and
 // the weights of every K-step stream through the consumer waves' vector-memory queue.  Here a workgroup owns a column of
-// TXO x TYO output voxels and MARCHES along z (the layout conv0's conv3d_sbf_zm_kernel introduced, generalised):
+// TXO x TYO output voxels and MARCHES along z:
 //   * the staged input is a RING of z-planes in LDS ([plane][8-channel slice][row][x] x 48 B, the [term][8] bf16 position
 //     format of sbf_common.hpp; split-f16 configurations may ask for two 16-byte term planes per slice instead: ZG::P32);
 //     every input plane is loaded, split and stored ONCE per column: 1.33 (stride 1, 32 x 8) or 9.1-9.3 (stride 2) staged
@@ -15,7 +16,7 @@
 //     partial sums of half of their N-tiles through a double-buffered LDS area across the stage barrier and add them in a
 //     fixed order (round 0 + round 1), so results do not depend on timing;
 //   * the four producer waves issue unconditional loads: an out-of-volume position reads a 32-byte zero block in global memory
-//     (a two-instruction address select) instead of the exec-masked branch per position of the first z-marching kernel.
+//     (a two-instruction address select) instead of an exec-masked branch per position.
 // Same arithmetic, operand layout and weight packing (ops.split_pack_conv3d / split_pack_conv3d_pair) as the tiled kernels;
 // reached through cds_conv3d_sbf_f32 (conv3d_sbf.hip), which keeps the tiled kernels for the shapes not covered here.
 // Reference: models/module.py:80-116 (Conv3d + BatchNorm3d + ReLU), :270-315 (CostRegNet).
@@ -28,25 +29,97 @@ namespace {
 
 __device__ __attribute__((aligned(32))) float g_zmg_zeros[8];   // what an out-of-volume position loads
 
-// CW_ = 4: one consumer wave per SIMD (256-register budget); CW_ = 8: two per SIMD, 12 waves per workgroup, 168 registers: one
+// What a configuration may set (ZGDefaults); a layer's configuration is a struct that derives from it and names what differs.
+// S: stride.  RD: 8-channel rounds of the input (Cin / 8).  MB: 16-cout blocks.  PAIR: Cout = 8, an MFMA column is a pair of x
+// neighbours (ops.split_pack_conv3d_pair).  TXO x TYO: output voxels of a column.  G: output planes per stage.  NG: N-tiles per K-step.
+// CW = 4: one consumer wave per SIMD (256-register budget); CW = 8: two per SIMD, 12 waves per workgroup, 168 registers: one
 // MFMA-issuing wave per SIMD sustains one v_mfma_f32_16x16x32_bf16 per 10.0 ns, two sustain one per 8.1 ns (scripts/ubench), and the
 // second wave's K-loop covers the first one's exchange / epilogue / barrier time.
-// F16_: split-f16 arithmetic (two fp16 terms per operand, three products per K-step, tensor scales from device bounds: sbf_common.hpp)
+// F16: split-f16 arithmetic (two fp16 terms per operand, three products per K-step, tensor scales from device bounds: sbf_common.hpp)
 // instead of split-bf16 (three bf16 terms, six products); same staging geometry, term 2 of a position / weight vector unused.
-// RPW_: 8-channel rounds a consumer wave keeps (the K dimension is split over RD / RPW waves; the deep layers' Cin = 32 / 64 would
-// otherwise need more consumer waves than a workgroup has).  YS_: the cout blocks are split over gridDim.y (every one of the YS
-// workgroups of a column stages the whole input ring and computes MB / YS cout blocks: Cout = 64).  PF_: K-steps the LDS operand
+// RPW: 8-channel rounds a consumer wave keeps (the K dimension is split over RD / RPW waves; the deep layers' Cin = 32 / 64 would
+// otherwise need more consumer waves than a workgroup has).  YS: the cout blocks are split over gridDim.y (every one of the YS
+// workgroups of a column stages the whole input ring and computes MB / YS cout blocks: Cout = 64).  PF: K-steps the LDS operand
 // reads run ahead of their MFMAs (2: a wave with ONE N-tile per step has only three MFMAs to cover an LDS round trip).
-template <int S_, int RD_, int MB_, bool PAIR_, int TXO_, int TYO_, int G_, int NG_, int CW_ = 4, bool F16_ = false, int RPW_ = 1,
-          int YS_ = 1, int PF_ = 1, bool P32_ = false>
+// P32 (split-f16 only): 32-byte positions, term-planar inside a slice ([term][row][x] x 16 B) instead of the 48-byte
+// [term 0 | term 1 | unused] position: the ring shrinks by a third (conv5: 163 200 -> 108 800 B, which is what lets a stride-2
+// column of 32 input channels fit at all), 16 lanes on 16 consecutive x still read 16 different 16-byte bank groups, and the tap
+// offsets stay compile-time constants.
+struct ZGDefaults {
+  static constexpr int S = 1, RD = 1, MB = 1, TXO = 16, TYO = 8, G = 1, NG = 1, CW = 8, RPW = 1, YS = 1, PF = 1;
+  static constexpr bool PAIR = false, F16 = false, P32 = false;
+};
+// the split-f16 sibling of a split-bf16 configuration that differs in nothing else
+template <class P>
+struct ZgF16 : P {
+  static constexpr bool F16 = true;
+};
+
+// Consumer waves per SIMD as measured at the M1 / cascade shapes (profiles/r04_zmarch.md): two for everything but the 16 -> 8 and
+// 32 -> 8 pair layers.
+struct ZgPair8 : ZGDefaults {    // 8 -> 8 (conv0 at 8 channels): three output planes per stage
+  static constexpr bool PAIR = true;
+  static constexpr int TXO = 32, G = 3;
+};
+struct ZgPair16 : ZGDefaults {   // 16 -> 8 (conv0 of the 16-channel cascade stage)
+  static constexpr bool PAIR = true;
+  static constexpr int RD = 2, TXO = 32, NG = 4, CW = 4;
+};
+struct ZgPair32 : ZGDefaults {   // 32 -> 8 (conv0 of the 32-channel cascade stage): K split in four, the ring leaves room for three output rows per stage
+  static constexpr bool PAIR = true;
+  static constexpr int RD = 4, TXO = 32, TYO = 3, NG = 3, CW = 4;
+};
+struct ZgConv1 : ZGDefaults {    // 8 -> 16, stride 2
+  static constexpr int S = 2;
+};
+struct ZgConv2 : ZGDefaults {    // 16 -> 16 (split-bf16: K split over wave pairs)
+  static constexpr int RD = 2, TXO = 32;
+};
+struct ZgConv3 : ZGDefaults {    // 16 -> 32, stride 2 (split-bf16: K split over wave pairs)
+  static constexpr int S = 2, RD = 2, MB = 2, TYO = 4;
+};
+// conv2, split-f16: both rounds of weights in one wave like conv3 below (no exchange through LDS, no finalising step), on the 32-byte
+// ring with the uniform-base output address: 162 VGPRs, no scratch (with 64-bit per-lane output addresses: 168 and 2-4 spilled);
+// profiles/zmarch_conv5.md: 325-338 -> 306-316 us in the M1 step
+struct ZgConv2F16 : ZgF16<ZgConv2> {
+  static constexpr int RPW = 2;
+  static constexpr bool P32 = true;
+};
+// conv3, split-f16: both rounds of weights in one wave (RPW = 2: 112 registers of two fp16 terms, 162 VGPRs) instead of the K split
+// over wave pairs that three bf16 terms need: no exchange through LDS and no finalising step (profiles/zmarch_conv7.md: 180-183 ->
+// 157-162 us)
+struct ZgConv3F16 : ZgF16<ZgConv3> {
+  static constexpr int RPW = 2;
+};
+// conv4 (32 -> 32): K split over four waves x two cout blocks, 16 x 4 columns (ring 81 KB + 2 x 32 KB exchange)
+struct ZgConv4F16 : ZgF16<ZGDefaults> {
+  static constexpr int RD = 4, MB = 2, TYO = 4, PF = 2;
+};
+// conv5 (32 -> 64, stride 2): 16 x 2 output columns on the 32-byte ring (5 planes of 4 slices x 5 x 34 positions = 108 800 B; at
+// 48 bytes per position 163 200 B: no stride-2 column of 32 channels fits), K split in two with two rounds of weights per wave
+// x the four cout blocks = 8 consumer waves of 84 MFMAs per stage (2 x 8 KB exchange), 167 VGPRs; operand reads two K-steps
+// ahead (PF = 2) would spill 14 of them.  profiles/zmarch_conv5.md: 133-139 us tiled -> 68-80 us in the M1 step
+struct ZgConv5F16 : ZgF16<ZGDefaults> {
+  static constexpr int S = 2, RD = 4, MB = 4, TYO = 2, RPW = 2;
+  static constexpr bool P32 = true;
+};
+// conv6 (64 -> 64): two rounds of weights per wave (K split over four waves), two cout blocks per workgroup and two workgroups
+// (gridDim.y) per 16 x 2 column: the input is staged twice from L2 / the memory-side cache, against four times and stages of 42
+// MFMAs per wave for a K split over eight waves with one cout block per workgroup (ring 108 KB + 2 x 16 KB exchange)
+struct ZgConv6F16 : ZgF16<ZGDefaults> {
+  static constexpr int RD = 8, MB = 4, TYO = 2, RPW = 2, YS = 2;
+};
+
+// The geometry that follows from a configuration P.
+template <class P>
 struct ZG {
-  static constexpr int S = S_, RD = RD_, MB = MB_, TXO = TXO_, TYO = TYO_, G = G_, NG = NG_;
-  static constexpr bool F16 = F16_;
-  static constexpr int NT = F16_ ? 2 : 3;                          // terms per operand
-  static constexpr bool PAIR = PAIR_, DEINT = PAIR_ || S_ == 2;
-  static constexpr int CW = CW_, PW = 4, THREADS = (CW + PW) * 64;
-  static constexpr int RPW = RPW_, YS = YS_, PF = PF_;
-  static_assert(PF == 1 || (PF == 2 && 2 * NG_ * (F16_ ? 2 : 3) <= 15), "operand prefetch distance (lgkmcnt is a 4-bit count)");
+  static constexpr int S = P::S, RD = P::RD, MB = P::MB, TXO = P::TXO, TYO = P::TYO, G = P::G, NG = P::NG;
+  static constexpr bool F16 = P::F16;
+  static constexpr int NT = F16 ? 2 : 3;                           // terms per operand
+  static constexpr bool PAIR = P::PAIR, DEINT = PAIR || S == 2;
+  static constexpr int CW = P::CW, PW = 4, THREADS = (CW + PW) * 64;
+  static constexpr int RPW = P::RPW, YS = P::YS, PF = P::PF;
+  static_assert(PF == 1 || (PF == 2 && 2 * NG * NT <= 15), "operand prefetch distance (lgkmcnt is a 4-bit count)");
   static_assert(RD % RPW == 0 && MB % YS == 0, "rounds per wave / cout split");
   static constexpr int KSPL = RD / RPW, MBS = MB / YS;            // wave = (RPW rounds, cout block, row part)
   static_assert(CW % (KSPL * MBS) == 0 && (KSPL == 1 || KSPL == 2 || KSPL == 4), "consumer waves");
@@ -59,14 +132,11 @@ struct ZG {
   static constexpr int IX = (TXO - 1) * S + 3, IY = (TYO - 1) * S + 3;
   static constexpr int IXH = DEINT ? (IX + 1) / 2 : 0;            // x parities de-interleaved (stride 2, pair columns)
   static constexpr int IXP = DEINT ? 2 * IXH : IX;
-  // P32_ (split-f16 only): 32-byte positions, term-planar inside a slice ([term][row][x] x 16 B) instead of the 48-byte
-  // [term 0 | term 1 | unused] position: the ring shrinks by a third (conv5: 163 200 -> 108 800 B, which is what lets a stride-2
-  // column of 32 input channels fit at all), 16 lanes on 16 consecutive x still read 16 different 16-byte bank groups, and the tap
-  // offsets stay compile-time constants.  PB = bytes from a position to its x neighbour, TB = from its term 0 to its term 1.
-  static constexpr bool P32 = P32_;
-  static_assert(!P32_ || F16_, "the 32-byte position holds two terms");
-  static constexpr int PB = P32_ ? 16 : POSB, TB = P32_ ? IY * IXP * 16 : 16;
-  static constexpr int SLICEB = IY * IXP * (P32_ ? 32 : POSB), PLANEB = RD * SLICEB;
+  // PB = bytes from a position to its x neighbour, TB = from its term 0 to its term 1
+  static constexpr bool P32 = P::P32;
+  static_assert(!P32 || F16, "the 32-byte position holds two terms");
+  static constexpr int PB = P32 ? 16 : POSB, TB = P32 ? IY * IXP * 16 : 16;
+  static constexpr int SLICEB = IY * IXP * (P32 ? 32 : POSB), PLANEB = RD * SLICEB;
   static constexpr int NINIT = 3 - S;                             // planes below the first stage's new ones
   static constexpr int NRES = S * (G - 1) + 3, NNEW = S * G, R = NRES + NNEW;
   static constexpr int RINGB = R * PLANEB;
@@ -263,16 +333,17 @@ __global__ __launch_bounds__(Cfg::THREADS, 1) void conv3d_zmg_kernel(const float
   bool lane_ok[Cfg::XT];
 #pragma unroll
   for (int xt = 0; xt < Cfg::XT; ++xt) lane_ok[xt] = ox0 + xt * XW < Wo && co < Cout;
-  auto store_tile = [&](int n, int st, const f32x4& a) {
+  // the epilogue of N-tile n of stage st.  in_x(xt): is this lane's voxel of x run xt inside the volume - from the table where n is a
+  // compile-time constant, computed where it is known only at run time (K split in four: n = 4 j + k)
+  auto in_x_ct = [&](int xt) { return lane_ok[xt]; };
+  auto in_x_rt = [&](int xt) { return ox0 + xt * XW < Wo && co < Cout; };
+  auto store_tile = [&](int n, int st, const f32x4& a, auto in_x) {
     const int i = n % G, rx = n / G, xt = rx % Cfg::XT, r = rx / Cfg::XT;
     if (z0 + st * G + i >= z1 || oy0 + r >= Ho) return;            // wave-uniform
-    if (!lane_ok[xt]) return;
-    float4 o = F16 ? make_float4(a.x * out_mul + bv.x, a.y * out_mul + bv.y, a.z * out_mul + bv.z, a.w * out_mul + bv.w)
-                   : make_float4(a.x + bv.x, a.y + bv.y, a.z + bv.z, a.w + bv.w);
-    if (act == CDS_ACT_RELU) {
-      o.x = fmaxf(o.x, 0.f); o.y = fmaxf(o.y, 0.f); o.z = fmaxf(o.z, 0.f); o.w = fmaxf(o.w, 0.f);
-    }
-    if (F16) amax = fmaxf(fmaxf(amax, fmaxf(fabsf(o.x), fabsf(o.y))), fmaxf(fabsf(o.z), fabsf(o.w)));
+    if (!in_x(xt)) return;
+    float4 o = F16 ? sf16_rescale4(a, out_mul, bv) : sbf_add4(sbf_f4(a), bv);
+    if (act == CDS_ACT_RELU) o = sbf_relu4(o);
+    if (F16) amax = sbf_amax4(amax, o);
     sbf_store4(out_ptr(st * G + i, r, xt), o);
   };
   unsigned char* xch = lds + Cfg::RINGB;                 // [buffer][sender wave][N-tile of its partner's half][lane] x 16 B
@@ -282,19 +353,6 @@ __global__ __launch_bounds__(Cfg::THREADS, 1) void conv3d_zmg_kernel(const float
   // exchange buffer too instead of staying in registers across the next K-loop
   constexpr bool KEEP4 = Cfg::RPW == 1;
   f32x4 keep[Cfg::KSPL == 2 ? NH : Cfg::NFIN];          // this wave's partial sums of the N-tiles it finalises, across the barrier
-  // K split in four: N-tile n known only at run time (n = 4 j + k)
-  auto store_tile_rt = [&](int n, int st, const f32x4& a) {
-    const int i = n % G, rx = n / G, xt = rx % Cfg::XT, r = rx / Cfg::XT;
-    if (z0 + st * G + i >= z1 || oy0 + r >= Ho) return;            // wave-uniform
-    if (!(ox0 + xt * XW < Wo && co < Cout)) return;
-    float4 o = F16 ? make_float4(a.x * out_mul + bv.x, a.y * out_mul + bv.y, a.z * out_mul + bv.z, a.w * out_mul + bv.w)
-                   : make_float4(a.x + bv.x, a.y + bv.y, a.z + bv.z, a.w + bv.w);
-    if (act == CDS_ACT_RELU) {
-      o.x = fmaxf(o.x, 0.f); o.y = fmaxf(o.y, 0.f); o.z = fmaxf(o.z, 0.f); o.w = fmaxf(o.w, 0.f);
-    }
-    if (F16) amax = fmaxf(fmaxf(amax, fmaxf(fabsf(o.x), fabsf(o.y))), fmaxf(fabsf(o.z), fabsf(o.w)));
-    sbf_store4(out_ptr(st * G + i, r, xt), o);
-  };
   const int xgrp = (wave / Cfg::KSPL) * NTW;            // first exchange slot row of this wave's (cout block, row part)
   // finish stage sp: bias / ReLU / store of this wave's outputs.  K split: N-tiles [k NH, (k + 1) NH) = round 0's partial sum +
   // round 1's (the partner's half arrived through exchange buffer sp & 1 before the stage barrier)
@@ -304,7 +362,7 @@ __global__ __launch_bounds__(Cfg::THREADS, 1) void conv3d_zmg_kernel(const float
 #pragma unroll
       for (int m = 0; m < NH; ++m) {
         const f32x4 o = *reinterpret_cast<const f32x4*>(src + m * 1024);
-        store_tile(k * NH + m, sp, k == 0 ? keep[m] + o : o + keep[m]);
+        store_tile(k * NH + m, sp, k == 0 ? keep[m] + o : o + keep[m], in_x_ct);
       }
     } else if (Cfg::KSPL == 4) {
 #pragma unroll
@@ -315,11 +373,11 @@ __global__ __launch_bounds__(Cfg::THREADS, 1) void conv3d_zmg_kernel(const float
         f32x4 total = KEEP4 && k == 0 ? keep[jf] : *reinterpret_cast<const f32x4*>(src);
 #pragma unroll
         for (int kk = 1; kk < 4; ++kk) total = total + (KEEP4 && kk == k ? keep[jf] : *reinterpret_cast<const f32x4*>(src + kk * 1024));
-        store_tile_rt(n, sp, total);
+        store_tile(n, sp, total, in_x_rt);
       }
     } else {
 #pragma unroll
-      for (int n = 0; n < NTW; ++n) store_tile(n, sp, acc[n]);
+      for (int n = 0; n < NTW; ++n) store_tile(n, sp, acc[n], in_x_ct);
     }
   };
   __syncthreads();                                     // #0
@@ -439,9 +497,10 @@ inline int zmg_pick_nseg(int cols, int Do, int G) {
   return best;
 }
 
-template <class Cfg>
+template <class P>
 int launch_zmg(const float* x, const void* wsp, const float* b, float* out, int Cout, int D, int H, int W, int act, hipStream_t st,
                const float* in_bound = nullptr, float w_inv = 1.f, float* out_bound = nullptr, int min_wgs = 0) {
+  using Cfg = ZG<P>;
   constexpr int S = Cfg::S;
   const int Do = (D - 1) / S + 1, Ho = (H - 1) / S + 1, Wo = (W - 1) / S + 1;
   const int tx = cds_ceil_div(Wo, Cfg::TXO), ty = cds_ceil_div(Ho, Cfg::TYO);
@@ -449,12 +508,9 @@ int launch_zmg(const float* x, const void* wsp, const float* b, float* out, int 
   const int zseg = cds_ceil_div(cds_ceil_div(Do, nseg), Cfg::G) * Cfg::G;
   nseg = cds_ceil_div(Do, zseg);
   if (min_wgs > 0 && tx * ty * nseg * Cfg::YS < min_wgs) return CDS_ZMG_UNSUPPORTED;   // too few columns to fill the chip
-  auto kern = conv3d_zmg_kernel<Cfg>;
-  static std::atomic<unsigned long long> lds_ok{0};     // per instantiation
-  if (int e_lds = cds_allow_lds(reinterpret_cast<const void*>(kern), Cfg::LDSB, lds_ok)) return e_lds;
-  hipLaunchKernelGGL(kern, dim3(tx * ty * nseg, Cfg::YS), dim3(Cfg::THREADS), Cfg::LDSB, st, x, reinterpret_cast<const uint4*>(wsp), b,
-                     out, Cout, D, H, W, Do, Ho, Wo, act, tx, ty, zseg, in_bound, w_inv, out_bound);
-  return cds_launch_status();
+  return cds_launch_lds<conv3d_zmg_kernel<Cfg>>(Cfg::LDSB, dim3(tx * ty * nseg, Cfg::YS), dim3(Cfg::THREADS), Cfg::LDSB, st, x,
+                                                reinterpret_cast<const uint4*>(wsp), b, out, Cout, D, H, W, Do, Ho, Wo, act, tx, ty, zseg,
+                                                in_bound, w_inv, out_bound);
 }
 
 }  // namespace
@@ -463,59 +519,31 @@ int launch_zmg(const float* x, const void* wsp, const float* b, float* out, int 
 // pair != 0: Cout == 8 with the pair-packed weights (ops.split_pack_conv3d_pair), stride 1.
 int cds_conv3d_zmg_dispatch(const float* x, const void* wsp, const float* bias, float* out, int Cin, int Cout, int D, int H, int W,
                             int stride, int pair, int act, hipStream_t st, const float* in_bound, float w_inv, float* out_bound) {
-  if (in_bound) {   // split-f16 arithmetic: the same six shapes, scales from device bounds (cds_conv3d_sf16_f32)
-    if (pair) {
-      if (Cin == 8) return launch_zmg<ZG<1, 1, 1, true, 32, 8, 3, 1, 8, true>>(x, wsp, bias, out, Cout, D, H, W, act, st, in_bound, w_inv, out_bound);
-      if (Cin == 16) return launch_zmg<ZG<1, 2, 1, true, 32, 8, 1, 4, 4, true>>(x, wsp, bias, out, Cout, D, H, W, act, st, in_bound, w_inv, out_bound);
-      if (Cin == 32) return launch_zmg<ZG<1, 4, 1, true, 32, 3, 1, 3, 4, true>>(x, wsp, bias, out, Cout, D, H, W, act, st, in_bound, w_inv, out_bound);
-      return CDS_ZMG_UNSUPPORTED;
-    }
-    // conv2: both rounds of weights in one wave like conv3 below (no exchange through LDS, no finalising step), on the 32-byte ring
-    // with the uniform-base output address: 162 VGPRs, no scratch (with 64-bit per-lane output addresses: 168 and 2-4 spilled);
-    // profiles/zmarch_conv5.md: 325-338 -> 306-316 us in the M1 step
-    if (stride == 1 && Cin == 16 && Cout == 16)
-      return launch_zmg<ZG<1, 2, 1, false, 32, 8, 1, 1, 8, true, 2, 1, 1, true>>(x, wsp, bias, out, Cout, D, H, W, act, st, in_bound, w_inv, out_bound);
-    if (stride == 2 && Cin == 8 && Cout == 16)
-      return launch_zmg<ZG<2, 1, 1, false, 16, 8, 1, 1, 8, true>>(x, wsp, bias, out, Cout, D, H, W, act, st, in_bound, w_inv, out_bound);
-    // conv3: both rounds of weights in one wave (RPW = 2: 112 registers of two fp16 terms, 162 VGPRs) instead of the K split over wave
-    // pairs that three bf16 terms need: no exchange through LDS and no finalising step (profiles/zmarch_conv7.md: 180-183 -> 157-162 us)
-    if (stride == 2 && Cin == 16 && Cout == 32)
-      return launch_zmg<ZG<2, 2, 2, false, 16, 4, 1, 1, 8, true, 2>>(x, wsp, bias, out, Cout, D, H, W, act, st, in_bound, w_inv, out_bound);
-    // The deep layers (conv4 32 -> 32, conv5 32 -> 64 stride 2, conv6 64 -> 64).  CDS_ZMG_DEEP (A/B knob): 0 = tiled kernels,
-    // 1 = z-march where columns x segments fill the 256 CUs (the few tiles of the cascade stages' deep layers stay on the tiled
-    // kernels and their cout split), 2 = z-march whatever the size.
-    const int deep = cds_env_is("CDS_ZMG", '0') ? 0 : cds_env_int("CDS_ZMG_DEEP", 1);
-    const int min_wgs = deep == 2 ? 0 : 256;
-    // conv4: K split over four waves x two cout blocks, 16 x 4 columns (ring 81 KB + 2 x 32 KB exchange)
-    if (deep > 0 && stride == 1 && Cin == 32 && Cout == 32)
-      return launch_zmg<ZG<1, 4, 2, false, 16, 4, 1, 1, 8, true, 1, 1, 2>>(x, wsp, bias, out, Cout, D, H, W, act, st, in_bound, w_inv, out_bound, min_wgs);
-    // conv6: two rounds of weights per wave (K split over four waves), two cout blocks per workgroup and two workgroups (gridDim.y)
-    // per 16 x 2 column: the input is staged twice from L2 / the memory-side cache, against four times and stages of 42 MFMAs per
-    // wave for a K split over eight waves with one cout block per workgroup (ring 108 KB + 2 x 16 KB exchange)
-    if (deep > 0 && stride == 1 && Cin == 64 && Cout == 64)
-      return launch_zmg<ZG<1, 8, 4, false, 16, 2, 1, 1, 8, true, 2, 2>>(x, wsp, bias, out, Cout, D, H, W, act, st, in_bound, w_inv, out_bound, min_wgs);
-    // conv5 (32 -> 64, stride 2): 16 x 2 output columns on the 32-byte ring (5 planes of 4 slices x 5 x 34 positions = 108 800 B; at
-    // 48 bytes per position 163 200 B: no stride-2 column of 32 channels fits), K split in two with two rounds of weights per wave
-    // x the four cout blocks = 8 consumer waves of 84 MFMAs per stage (2 x 8 KB exchange), 167 VGPRs; operand reads two K-steps
-    // ahead (PF = 2) would spill 14 of them.  profiles/zmarch_conv5.md: 133-139 us tiled -> 68-80 us in the M1 step
-    if (deep > 0 && stride == 2 && Cin == 32 && Cout == 64)
-      return launch_zmg<ZG<2, 4, 4, false, 16, 2, 1, 1, 8, true, 2, 1, 1, true>>(x, wsp, bias, out, Cout, D, H, W, act, st, in_bound, w_inv, out_bound, min_wgs);
-    return CDS_ZMG_UNSUPPORTED;
-  }
-  const bool off = cds_env_is("CDS_ZMG", '0');   // A/B knob: 0 = tiled kernels only
-  if (off) return CDS_ZMG_UNSUPPORTED;
-  // Consumer waves per SIMD as measured at the M1 / cascade shapes (profiles/r04_zmarch.md): two for everything but the 16 -> 8 pair layer
+  const bool f16 = in_bound != nullptr;   // split-f16 arithmetic, scales from device bounds (cds_conv3d_sf16_f32)
+  // A/B knob CDS_ZMG=0: tiled kernels only (split-f16: for the deep layers only); read where it decides, a getenv is not free
+  auto off = [] { return cds_env_is("CDS_ZMG", '0'); };
+  if (!f16 && off()) return CDS_ZMG_UNSUPPORTED;
+  auto run = [&](auto p, int min_wgs = 0) {
+    return launch_zmg<decltype(p)>(x, wsp, bias, out, Cout, D, H, W, act, st, in_bound, w_inv, out_bound, min_wgs);
+  };
   if (pair) {
-    if (Cin == 8) return launch_zmg<ZG<1, 1, 1, true, 32, 8, 3, 1, 8>>(x, wsp, bias, out, Cout, D, H, W, act, st);
-    if (Cin == 16) return launch_zmg<ZG<1, 2, 1, true, 32, 8, 1, 4>>(x, wsp, bias, out, Cout, D, H, W, act, st);
-    if (Cin == 32) return launch_zmg<ZG<1, 4, 1, true, 32, 3, 1, 3>>(x, wsp, bias, out, Cout, D, H, W, act, st);
+    if (Cin == 8) return f16 ? run(ZgF16<ZgPair8>()) : run(ZgPair8());
+    if (Cin == 16) return f16 ? run(ZgF16<ZgPair16>()) : run(ZgPair16());
+    if (Cin == 32) return f16 ? run(ZgF16<ZgPair32>()) : run(ZgPair32());
     return CDS_ZMG_UNSUPPORTED;
   }
-  if (stride == 1) {
-    if (Cin == 16 && Cout == 16) return launch_zmg<ZG<1, 2, 1, false, 32, 8, 1, 1, 8>>(x, wsp, bias, out, Cout, D, H, W, act, st);
-    return CDS_ZMG_UNSUPPORTED;
-  }
-  if (Cin == 8 && Cout == 16) return launch_zmg<ZG<2, 1, 1, false, 16, 8, 1, 1, 8>>(x, wsp, bias, out, Cout, D, H, W, act, st);
-  if (Cin == 16 && Cout == 32) return launch_zmg<ZG<2, 2, 2, false, 16, 4, 1, 1, 8>>(x, wsp, bias, out, Cout, D, H, W, act, st);
+  if (stride == 2 && Cin == 8 && Cout == 16) return f16 ? run(ZgF16<ZgConv1>()) : run(ZgConv1());
+  if (stride == 1 && Cin == 16 && Cout == 16) return f16 ? run(ZgConv2F16()) : run(ZgConv2());
+  if (stride == 2 && Cin == 16 && Cout == 32) return f16 ? run(ZgConv3F16()) : run(ZgConv3());
+  if (!f16) return CDS_ZMG_UNSUPPORTED;
+  // The deep layers (conv4 32 -> 32, conv5 32 -> 64 stride 2, conv6 64 -> 64), split-f16 only.  CDS_ZMG_DEEP (A/B knob): 0 = tiled
+  // kernels, 1 = z-march where columns x segments fill the 256 CUs (the few tiles of the cascade stages' deep layers stay on the
+  // tiled kernels and their cout split), 2 = z-march whatever the size.
+  const int deep = off() ? 0 : cds_env_int("CDS_ZMG_DEEP", 1);
+  const int min_wgs = deep == 2 ? 0 : 256;
+  if (deep <= 0) return CDS_ZMG_UNSUPPORTED;
+  if (stride == 1 && Cin == 32 && Cout == 32) return run(ZgConv4F16(), min_wgs);
+  if (stride == 2 && Cin == 32 && Cout == 64) return run(ZgConv5F16(), min_wgs);
+  if (stride == 1 && Cin == 64 && Cout == 64) return run(ZgConv6F16(), min_wgs);
   return CDS_ZMG_UNSUPPORTED;
 }

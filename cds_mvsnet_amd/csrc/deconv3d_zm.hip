@@ -12,7 +12,7 @@
 // 8-channel rounds of a plane resident, exact three-way bf16 split done by the 4 producer waves on the way in): one barrier per cell
 // plane; every input cell is read from HBM once per column (+ the one-cell halo on the high sides).  Each SIMD holds one pz = 0 and
 // one pz = 1 consumer wave (1 : 2 matrix work) and a producer.
-#include "sbf_common.hpp"
+#include "zm_common.hpp"
 
 namespace {
 
@@ -27,7 +27,6 @@ struct DZC {
   static constexpr int CW = 8, PW = 4, THREADS = (CW + PW) * 64;
   static constexpr int LDS = NSLOT * SLOTB;
   static constexpr int NITEM = IY * IX * ROUNDS;
-  static constexpr int IPT = (NITEM + PW * 64 - 1) / (PW * 64);
 };
 
 // The producer waves of a column (X0, Y0) marching over the cell planes [a0, a1): load, split and deposit plane a + 2 while the
@@ -35,41 +34,11 @@ struct DZC {
 template <class C, bool F16>
 __device__ __forceinline__ void dzm_produce(const float* __restrict__ x, unsigned char* lds, int ptid, int X0, int Y0, int D, int H, int W,
                                             int a0, int a1, float xs) {
-  constexpr int ROUNDS = C::ROUNDS, Cin = 8 * ROUNDS;
   __builtin_amdgcn_s_setprio(3);               // A/B at M1: producers at 0 / 1 / 3: 355 / 351 / 345 us
-  int s_src[C::IPT], s_dst[C::IPT];
-#pragma unroll
-  for (int h = 0; h < C::IPT; ++h) {
-    const int it = h * C::PW * 64 + ptid;
-    const int rd = it % ROUNDS, p = it / ROUNDS;
-    const int row = p / C::IX, c = p - row * C::IX;
-    const int gy = Y0 + row, gx = X0 + c;
-    const bool ok = it < C::NITEM && gy < H && gx < W;
-    s_src[h] = ok ? ((gy * W + gx) * Cin + rd * 8) : -1;
-    s_dst[h] = it < C::NITEM ? rd * C::ROUNDB + (row * C::IXP + c) * POSB : -1;
-  }
-  float4 va[C::IPT], vb[C::IPT];
-  auto issue = [&](int plane) {
-    const bool pok = plane < D;
-    const float* __restrict__ xp = x + (size_t)min(plane, D - 1) * H * W * Cin;
-#pragma unroll
-    for (int h = 0; h < C::IPT; ++h) {
-      const bool ok = pok && s_src[h] >= 0;
-      const float* src = xp + (ok ? s_src[h] : 0);
-      const float4 a = *reinterpret_cast<const float4*>(src), b = *reinterpret_cast<const float4*>(src + 4);
-      va[h] = ok ? a : make_float4(0.f, 0.f, 0.f, 0.f);
-      vb[h] = ok ? b : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-  };
-  auto deposit = [&](int plane) {
-    unsigned char* base = lds + (plane % C::NSLOT) * C::SLOTB;
-#pragma unroll
-    for (int h = 0; h < C::IPT; ++h)
-      if (s_dst[h] >= 0) {
-        if (F16) split_store8_f16(base + s_dst[h], va[h], vb[h], xs);
-        else split_store8(base + s_dst[h], va[h], vb[h]);
-      }
-  };
+  ZmCellStage<C, C::PW * 64, F16, false> stage;
+  stage.init(ptid, X0, Y0, H, W);
+  auto issue = [&](int plane) { stage.issue(x, plane, D, H, W); };
+  auto deposit = [&](int plane) { stage.deposit(lds + (plane % C::NSLOT) * C::SLOTB, xs); };
   issue(a0);
   deposit(a0);
   issue(a0 + 1);
@@ -98,12 +67,10 @@ __global__ __launch_bounds__((DZC<ROUNDS>::THREADS), 3) void deconv3d_zm_kernel(
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wg = cds_xcd_remap(blockIdx.x, gridDim.x);
-  const int col = wg % ncols, seg = wg / ncols;
-  const int tx_i = col % tiles_x, ty_i = col / tiles_x;
-  const int a0 = seg * seg_len, a1 = min(D, a0 + seg_len);
+  const ZmColumn zc = zm_column(tiles_x, ncols, seg_len, D);
+  const int a0 = zc.a0, a1 = zc.a1;
   if (a0 >= a1) return;
-  const int X0 = tx_i * C::TX, Y0 = ty_i * C::TY;
+  const int X0 = zc.tx_i * C::TX, Y0 = zc.ty_i * C::TY;
   const int Ho = 2 * H, Wo = 2 * W;
 
   if (wave >= C::CW) {
@@ -175,12 +142,10 @@ __global__ __launch_bounds__((DZC<ROUNDS>::THREADS), 3) void deconv3d_zm_kernel(
       // order with respect to each other -> a wait for a load with a younger store in flight is a full drain)
       asm volatile("" ::"v"(skn.x), "v"(skn.y), "v"(skn.z), "v"(skn.w));
       if (x_ok) {
-        const f32x4 r = acc[0];
-        float4 o = F16 ? make_float4(r.x * out_mul + bv.x, r.y * out_mul + bv.y, r.z * out_mul + bv.z, r.w * out_mul + bv.w)
-                       : make_float4(r.x, r.y, r.z, r.w);
-        if (act == CDS_ACT_RELU) o = make_float4(fmaxf(o.x, 0.f), fmaxf(o.y, 0.f), fmaxf(o.z, 0.f), fmaxf(o.w, 0.f));
-        if (skip) o = make_float4(sk.x + o.x, sk.y + o.y, sk.z + o.z, sk.w + o.w);
-        if (F16) amax = fmaxf(fmaxf(amax, fmaxf(fabsf(o.x), fabsf(o.y))), fmaxf(fabsf(o.z), fabsf(o.w)));
+        float4 o = F16 ? sf16_rescale4(acc[0], out_mul, bv) : sbf_f4(acc[0]);   // split-bf16: the bias rode in the accumulator
+        if (act == CDS_ACT_RELU) o = sbf_relu4(o);
+        if (skip) o = sbf_add4(sk, o);
+        if (F16) amax = sbf_amax4(amax, o);
         sbf_store4(out + zbase + row_off(n), o);
       }
     }
@@ -210,13 +175,11 @@ __global__ __launch_bounds__((DZC<8, 4>::THREADS), 3) void deconv3d_zm64_kernel(
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wg = cds_xcd_remap(blockIdx.x, gridDim.x);
-  const int mbtot = gridDim.y, mb0 = blockIdx.y;      // this workgroup's 16-cout block
-  const int col = wg % ncols, seg = wg / ncols;
-  const int tx_i = col % tiles_x, ty_i = col / tiles_x;
-  const int a0 = seg * seg_len, a1 = min(D, a0 + seg_len);
+  const ZmColumn zc = zm_column(tiles_x, ncols, seg_len, D);
+  const int a0 = zc.a0, a1 = zc.a1;
   if (a0 >= a1) return;
-  const int X0 = tx_i * C::TX, Y0 = ty_i * C::TY;
+  const int mbtot = gridDim.y, mb0 = blockIdx.y;      // this workgroup's 16-cout block
+  const int X0 = zc.tx_i * C::TX, Y0 = zc.ty_i * C::TY;
   const int Ho = 2 * H, Wo = 2 * W;
 
   if (wave >= C::CW) {
@@ -295,31 +258,16 @@ __global__ __launch_bounds__((DZC<8, 4>::THREADS), 3) void deconv3d_zm64_kernel(
       }
       asm volatile("" ::"v"(skn.x), "v"(skn.y), "v"(skn.z), "v"(skn.w));   // the next row's residual arrives before this row's store
       if (x_ok) {
-        const f32x4 r = acc[0];
-        float4 o = make_float4(r.x * out_mul + bv.x, r.y * out_mul + bv.y, r.z * out_mul + bv.z, r.w * out_mul + bv.w);
-        if (act == CDS_ACT_RELU) o = make_float4(fmaxf(o.x, 0.f), fmaxf(o.y, 0.f), fmaxf(o.z, 0.f), fmaxf(o.w, 0.f));
-        if (skip) o = make_float4(sk.x + o.x, sk.y + o.y, sk.z + o.z, sk.w + o.w);
-        amax = fmaxf(fmaxf(amax, fmaxf(fabsf(o.x), fabsf(o.y))), fmaxf(fabsf(o.z), fabsf(o.w)));
+        float4 o = sf16_rescale4(acc[0], out_mul, bv);
+        if (act == CDS_ACT_RELU) o = sbf_relu4(o);
+        if (skip) o = sbf_add4(sk, o);
+        amax = sbf_amax4(amax, o);
         sbf_store4(out + zbase + row_off(n), o);
       }
     }
     __syncthreads();
   }
   sf16_publish_bound(amax, out_bound);
-}
-
-// z segments per column: whole rounds of 256 single-resident workgroups against the planes a segment spends priming its ring
-int dzm_pick_nseg(int wgs_per_seg, int D) {
-  int best = 1;
-  double best_cost = 1e30;
-  for (int n = 1; n <= min(D, 24); ++n) {
-    const int len = cds_ceil_div(D, n);
-    const int n_eff = cds_ceil_div(D, len);
-    const double cost = (double)cds_ceil_div(wgs_per_seg * n_eff, 256) * (len + 1.5);
-    if (cost < best_cost - 1e-9) { best_cost = cost; best = n; }
-  }
-  const int nseg_e = cds_env_int("CDS_DZM_NSEG", 0);   // A/B and test knob, read per launch
-  return nseg_e > 0 ? min(nseg_e, D) : best;
 }
 
 }  // namespace
@@ -335,14 +283,12 @@ int cds_deconv3d_zm64_dispatch(const float* x, const void* wsp, const float* bia
   using C = DZC<8, 4>;
   const int tiles_x = cds_ceil_div(W, C::TX), tiles_y = cds_ceil_div(H, C::TY);
   const int ncols = tiles_x * tiles_y;
-  const int seg_len = cds_ceil_div(D, dzm_pick_nseg(ncols * 2, D));
+  const int seg_len = cds_ceil_div(D, zm_pick_nseg(ncols * 2, D, 24, "CDS_DZM_NSEG"));
   const int nseg = cds_ceil_div(D, seg_len);
   if (deep == 1 && ncols * nseg * 2 < 256) return CDS_ZMG_UNSUPPORTED;
-  static std::atomic<unsigned long long> lds_ok{0};
-  if (int e_lds = cds_allow_lds(reinterpret_cast<const void*>(deconv3d_zm64_kernel), 160 * 1024, lds_ok)) return e_lds;
-  hipLaunchKernelGGL(deconv3d_zm64_kernel, dim3(ncols * nseg, 2), dim3(C::THREADS), C::LDS + DZM64_W1L * 2 * 1024, st, x, reinterpret_cast<const uint4*>(wsp),
-                     bias, skip, out, D, H, W, tiles_x, ncols, seg_len, act, in_bound, w_inv, out_bound);
-  return cds_launch_status();
+  return cds_launch_lds<deconv3d_zm64_kernel>(160 * 1024, dim3(ncols * nseg, 2), dim3(C::THREADS), C::LDS + DZM64_W1L * 2 * 1024, st, x,
+                                              reinterpret_cast<const uint4*>(wsp), bias, skip, out, D, H, W, tiles_x, ncols, seg_len, act,
+                                              in_bound, w_inv, out_bound);
 }
 
 // ConvTranspose3d k3 s2 p1 op1 (+bias +ReLU +residual) 32 -> 16 in split-bf16 arithmetic, channels-last: x [D][H][W][32] ->
@@ -355,22 +301,15 @@ static int dzm_entry(const float* x, const void* weight_cls, const float* bias, 
   hipStream_t st = (hipStream_t)stream;
   const int tiles_x = cds_ceil_div(W, C::TX), tiles_y = cds_ceil_div(H, C::TY);
   const int ncols = tiles_x * tiles_y;
-  const int seg_len = cds_ceil_div(D, dzm_pick_nseg(ncols, D));
+  const int seg_len = cds_ceil_div(D, zm_pick_nseg(ncols, D, 24, "CDS_DZM_NSEG"));
   const int nseg = cds_ceil_div(D, seg_len);
-  if (in_bound) {
-    static std::atomic<unsigned long long> lds_ok_h{0};
-    if (int e_lds = cds_allow_lds(reinterpret_cast<const void*>(deconv3d_zm_kernel<4, true>), 160 * 1024, lds_ok_h)) return e_lds;
-    hipLaunchKernelGGL((deconv3d_zm_kernel<4, true>), dim3(ncols * nseg), dim3(C::THREADS), C::LDS, st, x,
-                       reinterpret_cast<const uint4*>(weight_cls), bias, skip, out, D, H, W, tiles_x, ncols, seg_len, act, in_bound, w_inv,
-                       out_bound);
-    return cds_launch_status();
-  }
-  static std::atomic<unsigned long long> lds_ok{0};
-  if (int e_lds = cds_allow_lds(reinterpret_cast<const void*>(deconv3d_zm_kernel<4, false>), 160 * 1024, lds_ok)) return e_lds;
-  hipLaunchKernelGGL((deconv3d_zm_kernel<4, false>), dim3(ncols * nseg), dim3(C::THREADS), C::LDS, st, x,
-                     reinterpret_cast<const uint4*>(weight_cls), bias, skip, out, D, H, W, tiles_x, ncols, seg_len, act, nullptr, 1.0f,
-                     nullptr);
-  return cds_launch_status();
+  // split-f16 where the caller gave the input's bound (the split-bf16 entry passes no bounds and w_inv = 1; its kernel reads none of them)
+  auto launch = [&](auto f16) {
+    return cds_launch_lds<deconv3d_zm_kernel<4, decltype(f16)::value>>(160 * 1024, dim3(ncols * nseg), dim3(C::THREADS), C::LDS, st, x,
+                                                                       reinterpret_cast<const uint4*>(weight_cls), bias, skip, out, D, H, W,
+                                                                       tiles_x, ncols, seg_len, act, in_bound, w_inv, out_bound);
+  };
+  return in_bound ? launch(std::true_type()) : launch(std::false_type());
 }
 
 extern "C" int cds_deconv3d_zm_f32(const float* x, const void* weight_cls, const float* bias, const float* skip, float* out,

@@ -33,7 +33,7 @@
 // order: ky in the MFMA chain, kx centre / left / right, then the three planes in arrival order - independent of timing.
 // y layout (MF): [row][term][x parity][slot = (x >> 1) ^ 8 (x & 1)][8 fp16]: the 16-byte operand reads of 16 consecutive x (even
 // origin) touch 16 different 16-byte bank groups, the consumers' 8-byte stores (x = 2 j + px) are 2-way.
-#include "sbf_common.hpp"
+#include "zm_common.hpp"
 
 namespace {
 
@@ -54,8 +54,6 @@ struct DPZ {
   static constexpr int LDS = WB + 2 * SLOTB + 2 * YB;
   static constexpr int PR = 3;                       // output rows per prob lane: PW * PR = 2 * CYR
   static constexpr int NITEM = IY * IX * ROUNDS;     // (cell, round) staging items of one plane
-  static constexpr int IPT = (NITEM + PW * 64 - 1) / (PW * 64);      // per producer thread (prologue of a segment)
-  static constexpr int IPC = (NITEM + CW * 64 - 1) / (CW * 64);      // per consumer thread (inside the march)
   // prob on the matrix cores: x tiles of 16 read positions at origin MSTEP * t, whole outputs in lanes 2 .. 13
   static constexpr int MT = 5, MSTEP = 12;
   static constexpr int YTERMB = YROWB / 2, YPARB = YTERMB / 2;       // y plane: [row][term][x parity][slot][8] fp16
@@ -110,10 +108,8 @@ __global__ __launch_bounds__(DPZ::THREADS, 3) void deconv_prob_zm_kernel(
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wg = cds_xcd_remap(blockIdx.x, gridDim.x);
-  const int col = wg % ncols, seg = wg / ncols;
-  const int tx_i = col % tiles_x, ty_i = col / tiles_x;
-  const int a0 = seg * seg_len, a1 = min(D, a0 + seg_len);
+  const ZmColumn zc = zm_column(tiles_x, ncols, seg_len, D);
+  const int tx_i = zc.tx_i, ty_i = zc.ty_i, a0 = zc.a0, a1 = zc.a1;
   if (a0 >= a1) return;
   const int X0 = tx_i * C::CXR - 1, Y0 = ty_i * C::CYR - 1;     // first computed cell
   const int Do = 2 * D, Ho = 2 * H, Wo = 2 * W;
@@ -130,39 +126,10 @@ __global__ __launch_bounds__(DPZ::THREADS, 3) void deconv_prob_zm_kernel(
     __builtin_amdgcn_s_setprio(2);
     const int ptid = tid - C::CW * 64;
     // ---- staging of input cell planes ----
-    int s_src[C::IPT], s_dst[C::IPT];
-#pragma unroll
-    for (int h = 0; h < C::IPT; ++h) {
-      const int it = h * C::PW * 64 + ptid;
-      const int rd = it & 1, p = it >> 1;
-      const int row = p / C::IX, c = p - row * C::IX;
-      const int gy = Y0 + row, gx = X0 + c;
-      const bool ok = it < C::NITEM && gy >= 0 && gy < H && gx >= 0 && gx < W;
-      s_src[h] = ok ? ((gy * W + gx) * 16 + rd * 8) : -1;
-      s_dst[h] = it < C::NITEM ? rd * C::ROUNDB + (row * C::IXP + c) * POSB : -1;
-    }
-    float4 va[C::IPT], vb[C::IPT];
-    auto issue = [&](int plane) {
-      const bool pok = plane < D;
-      const float* __restrict__ xp = x + (size_t)min(plane, D - 1) * H * W * 16;
-#pragma unroll
-      for (int h = 0; h < C::IPT; ++h) {
-        const bool ok = pok && s_src[h] >= 0;
-        const float* src = xp + (ok ? s_src[h] : 0);
-        const float4 a = *reinterpret_cast<const float4*>(src), b = *reinterpret_cast<const float4*>(src + 4);
-        va[h] = ok ? a : make_float4(0.f, 0.f, 0.f, 0.f);
-        vb[h] = ok ? b : make_float4(0.f, 0.f, 0.f, 0.f);
-      }
-    };
-    auto deposit = [&](int plane) {
-      unsigned char* base = inring + (plane & 1) * C::SLOTB;
-#pragma unroll
-      for (int h = 0; h < C::IPT; ++h)
-        if (s_dst[h] >= 0) {
-          if (F16) split_store8_f16(base + s_dst[h], va[h], vb[h], xs);
-          else split_store8(base + s_dst[h], va[h], vb[h]);
-        }
-    };
+    ZmCellStage<C, C::PW * 64, F16, true> stage;    // (the prologue of a segment; inside the march the consumers stage)
+    stage.init(ptid, X0, Y0, H, W);
+    auto issue = [&](int plane) { stage.issue(x, plane, D, H, W); };
+    auto deposit = [&](int plane) { stage.deposit(inring + (plane & 1) * C::SLOTB, xs); };
     if constexpr (MF) {
       // ---- prob on the matrix cores: wave = 3 output rows x MT x tiles; lane = (group g, read position n) ----
       const int n = lane & 15, g = lane >> 4, rg = wave - C::CW;
@@ -410,10 +377,11 @@ __global__ __launch_bounds__(DPZ::THREADS, 3) void deconv_prob_zm_kernel(
     for (int py = 0; py < 2; ++py)
 #pragma unroll
       for (int q = 0; q < C::NT; ++q) {
+        // split-f16: back to the layer's scale, then the BN shift (split-bf16: it rode in the accumulator).  sf16_rescale4 written as
+        // whole-vector operations: with the componentwise form the compiler turns the border selects below into exec-masked branches
         f32x4 a = acc[py][q];
-        if (F16) a = a * out_mul + (f32x4){bv.x, bv.y, bv.z, bv.w};      // split-f16: back to the layer's scale, then the BN shift
-        const float4 s4 = sk[py][q];
-        float4 o = make_float4(s4.x + fmaxf(a.x, 0.f), s4.y + fmaxf(a.y, 0.f), s4.z + fmaxf(a.z, 0.f), s4.w + fmaxf(a.w, 0.f));
+        if (F16) a = a * out_mul + (f32x4){bv.x, bv.y, bv.z, bv.w};
+        float4 o = sbf_add4(sk[py][q], sbf_relu4(sbf_f4(a)));
         if (border && sk_off[py][q] < 0) o = make_float4(0.f, 0.f, 0.f, 0.f);
         if constexpr (MF) {
           uint32_t h0, l0, h1, l1;
@@ -431,17 +399,8 @@ __global__ __launch_bounds__(DPZ::THREADS, 3) void deconv_prob_zm_kernel(
   // t / 2 - 1, which nobody reads after the barrier before) and split + stored after the half-step's epilogue, in the ~2000 cycles
   // the consumers used to spend at that barrier waiting for the prob waves.  (The prob waves did this until round 5: 1600-1700
   // cycles of every even half-step on the kernel's critical chain; probe without any staging: 975 vs 1170 us.) ----
-  int c_src[C::IPC], c_dst[C::IPC];
-#pragma unroll
-  for (int h = 0; h < C::IPC; ++h) {
-    const int it = h * C::CW * 64 + tid;
-    const int rd = it & 1, p = it >> 1;
-    const int row = p / C::IX, c = p - row * C::IX;
-    const int gy = Y0 + row, gx = X0 + c;
-    const bool ok = it < C::NITEM && gy >= 0 && gy < H && gx >= 0 && gx < W;
-    c_src[h] = ok ? ((gy * W + gx) * 16 + rd * 8) : -1;
-    c_dst[h] = it < C::NITEM ? rd * C::ROUNDB + (row * C::IXP + c) * POSB : -1;
-  }
+  ZmCellStage<C, C::CW * 64, F16, true> stage;
+  stage.init(tid, X0, Y0, H, W);
   if (qs & 1) load_skip(sk1, qs); else load_skip(sk0, qs);
   __syncthreads();                                // #0
   for (int t = qs; t <= te; ++t) {
@@ -455,20 +414,7 @@ __global__ __launch_bounds__(DPZ::THREADS, 3) void deconv_prob_zm_kernel(
           acc[py][q] = F16 ? (f32x4){0.f, 0.f, 0.f, 0.f} : (f32x4){bv.x, bv.y, bv.z, bv.w};
       if (!(t & 1)) {
         // ---- z parity 0: plane 2 a from cell plane a ----
-        float4 va[C::IPC], vb[C::IPC];
-        {
-          const int plane = a + 1;
-          const bool pok = plane < D;
-          const float* __restrict__ xp = x + (size_t)min(plane, D - 1) * H * W * 16;
-#pragma unroll
-          for (int h = 0; h < C::IPC; ++h) {
-            const bool ok = pok && c_src[h] >= 0;
-            const float* src = xp + (ok ? c_src[h] : 0);
-            const float4 la = *reinterpret_cast<const float4*>(src), lb = *reinterpret_cast<const float4*>(src + 4);
-            va[h] = ok ? la : make_float4(0.f, 0.f, 0.f, 0.f);
-            vb[h] = ok ? lb : make_float4(0.f, 0.f, 0.f, 0.f);
-          }
-        }
+        stage.issue(x, a + 1, D, H, W);
         load_skip(sk1, t + 1);
         BV w0[3], w1[3], b0[C::NT][3], b1[C::NT][3];
         load_b(b0, cur + b_h1);
@@ -485,15 +431,7 @@ __global__ __launch_bounds__(DPZ::THREADS, 3) void deconv_prob_zm_kernel(
         DPZ_TERMS(acc[0], w0, b1);
         DPZ_TERMS(acc[1], w1, b1);
         epilogue(sk0, 0);
-        {
-          unsigned char* base = inring + ((a + 1) & 1) * C::SLOTB;
-#pragma unroll
-          for (int h = 0; h < C::IPC; ++h)
-            if (c_dst[h] >= 0) {
-              if (F16) split_store8_f16(base + c_dst[h], va[h], vb[h], xs);
-              else split_store8(base + c_dst[h], va[h], vb[h]);
-            }
-        }
+        stage.deposit(inring + ((a + 1) & 1) * C::SLOTB, xs);
       } else {
         // ---- z parity 1: plane 2 a + 1 from cell planes a (kz = 2) and a + 1 (kz = 0) ----
         load_skip(sk0, t + 1);
@@ -535,42 +473,16 @@ static int dpz_entry(const float* x, const void* weight_split, const float* bias
   hipStream_t st = (hipStream_t)stream;
   const int tiles_x = cds_ceil_div(W, C::CXR), tiles_y = cds_ceil_div(H, C::CYR);
   const int ncols = tiles_x * tiles_y;
-  // z segments: whole rounds of the 256 single-resident workgroups, each segment pays ~1.5 extra half-steps of priming
-  const char* nseg_e = getenv("CDS_DPZ_NSEG");   // A/B and test knob, read per launch
-  const int nseg_env = nseg_e ? atoi(nseg_e) : 0;
-  int best = 1;
-  double best_cost = 1e30;
-  for (int n = 1; n <= min(D, 16); ++n) {
-    const int len = cds_ceil_div(D, n);
-    const int n_eff = cds_ceil_div(D, len);
-    const double cost = (double)cds_ceil_div(ncols * n_eff, 256) * (2.0 * len + 3.0);
-    if (cost < best_cost - 1e-9) { best_cost = cost; best = n; }
-  }
-  if (nseg_env > 0) best = min(nseg_env, D);
-  const int seg_len = cds_ceil_div(D, best);
+  const int seg_len = cds_ceil_div(D, zm_pick_nseg(ncols, D, 16, "CDS_DPZ_NSEG"));
   const int nseg = cds_ceil_div(D, seg_len);
-  if (skip_bound) {
-    static std::atomic<unsigned long long> lds_ok_m{0};
-    if (int e_lds = cds_allow_lds(reinterpret_cast<const void*>(deconv_prob_zm_kernel<true, true>), 160 * 1024, lds_ok_m)) return e_lds;
-    hipLaunchKernelGGL((deconv_prob_zm_kernel<true, true>), dim3(ncols * nseg), dim3(C::THREADS), C::LDS, st, x,
-                       reinterpret_cast<const uint4*>(weight_split), bias, skip, prob_table, out, D, H, W, tiles_x, ncols, seg_len, in_bound,
-                       w_inv, skip_bound, y_gain, p_inv);
-    return cds_launch_status();
-  }
-  if (in_bound) {
-    static std::atomic<unsigned long long> lds_ok_h{0};
-    if (int e_lds = cds_allow_lds(reinterpret_cast<const void*>(deconv_prob_zm_kernel<true, false>), 160 * 1024, lds_ok_h)) return e_lds;
-    hipLaunchKernelGGL((deconv_prob_zm_kernel<true, false>), dim3(ncols * nseg), dim3(C::THREADS), C::LDS, st, x,
-                       reinterpret_cast<const uint4*>(weight_split), bias, skip, prob_table, out, D, H, W, tiles_x, ncols, seg_len, in_bound,
-                       w_inv, nullptr, 0.f, 1.f);
-    return cds_launch_status();
-  }
-  static std::atomic<unsigned long long> lds_ok{0};
-  if (int e_lds = cds_allow_lds(reinterpret_cast<const void*>(deconv_prob_zm_kernel<false, false>), 160 * 1024, lds_ok)) return e_lds;
-  hipLaunchKernelGGL((deconv_prob_zm_kernel<false, false>), dim3(ncols * nseg), dim3(C::THREADS), C::LDS, st, x,
-                     reinterpret_cast<const uint4*>(weight_split), bias, skip, prob_table, out, D, H, W, tiles_x, ncols, seg_len, nullptr, 1.0f,
-                     nullptr, 0.f, 1.f);
-  return cds_launch_status();
+  // the form follows from the bounds the caller gave (the forms without them ignore the arguments that go with them)
+  auto launch = [&](auto f16, auto mf) {
+    return cds_launch_lds<deconv_prob_zm_kernel<decltype(f16)::value, decltype(mf)::value>>(
+        160 * 1024, dim3(ncols * nseg), dim3(C::THREADS), C::LDS, st, x, reinterpret_cast<const uint4*>(weight_split), bias, skip, prob_table,
+        out, D, H, W, tiles_x, ncols, seg_len, in_bound, w_inv, skip_bound, y_gain, p_inv);
+  };
+  if (skip_bound) return launch(std::true_type(), std::true_type());
+  return in_bound ? launch(std::true_type(), std::false_type()) : launch(std::false_type(), std::false_type());
 }
 
 extern "C" int cds_deconv_prob_zm_f32(const float* x, const void* weight_split, const float* bias, const float* skip,

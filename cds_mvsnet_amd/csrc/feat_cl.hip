@@ -632,14 +632,9 @@ int launch_dynconv_cl(const float* x, const float* aff, const void* wsp, const f
                       hipStream_t st) {
   using C = DCfg<CIN, K0, K1, K2, MODE>;
   const int tx = cds_ceil_div(W, TX), ty = cds_ceil_div(H, TY);
-  auto kern = dynconv_cl_kernel<CIN, K0, K1, K2, MODE, F16>;
-  if (C::LDSB > 64 * 1024) {
-    static std::atomic<unsigned long long> lds_ok{0};   // per instantiation
-    if (int e = cds_allow_lds(reinterpret_cast<const void*>(kern), C::LDSB, lds_ok)) return e;
-  }
-  hipLaunchKernelGGL(kern, dim3(tx * ty * N), dim3(256), (size_t)C::LDSB, st, x, aff, reinterpret_cast<const uint4*>(wsp), bias, ep, N,
-                     H, W, tx, ty);
-  return cds_launch_status();
+  return cds_launch_lds<dynconv_cl_kernel<CIN, K0, K1, K2, MODE, F16>>(C::LDSB > 64 * 1024 ? C::LDSB : 0, dim3(tx * ty * N), dim3(256),
+                                                                       C::LDSB, st, x, aff, reinterpret_cast<const uint4*>(wsp), bias, ep,
+                                                                       N, H, W, tx, ty);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------

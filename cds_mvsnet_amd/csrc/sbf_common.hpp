@@ -167,5 +167,22 @@ __device__ __forceinline__ void sbf_store4(float* p, const float4& o) {
 #endif
 }
 
+// The pieces of an epilogue, four values (one lane's couts of an N-tile) at a time.  Every kernel strings them together in its own
+// order (residual before or after the bound, bias in the accumulator or added here); each operation is separately rounded.
+__device__ __forceinline__ float4 sbf_f4(const f32x4& a) { return make_float4(a.x, a.y, a.z, a.w); }
+__device__ __forceinline__ float4 sbf_add4(const float4& a, const float4& b) {
+  return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w);
+}
+// split-f16: the accumulator back at the layer's scale (mul is a power of two: exact), then the BN shift / bias
+__device__ __forceinline__ float4 sf16_rescale4(const f32x4& a, float mul, const float4& b) {
+  return make_float4(a.x * mul + b.x, a.y * mul + b.y, a.z * mul + b.z, a.w * mul + b.w);
+}
+__device__ __forceinline__ float4 sbf_relu4(const float4& o) {
+  return make_float4(fmaxf(o.x, 0.f), fmaxf(o.y, 0.f), fmaxf(o.z, 0.f), fmaxf(o.w, 0.f));
+}
+// running maximum of the magnitudes a lane stores (what sf16_publish_bound reduces)
+__device__ __forceinline__ float sbf_amax4(float amax, const float4& o) {
+  return fmaxf(fmaxf(amax, fmaxf(fabsf(o.x), fabsf(o.y))), fmaxf(fabsf(o.z), fabsf(o.w)));
+}
 
 }  // namespace

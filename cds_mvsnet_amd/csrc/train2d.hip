@@ -182,12 +182,8 @@ int launch_wgrad2d(const float* g, const TX* xin, float* dw, int N, int Co, int 
   if (per < 1) per = 1;
   const dim3 grid(cds_ceil_div(ntiles * N, per), cds_ceil_div(Co, 16), cds_ceil_div(Cin, CB));
   const int ldsb = Cfg::LDS_FLOATS * (int)sizeof(float);
-  static std::atomic<unsigned long long> ok{0};
-  if (ldsb > 64 * 1024)
-    if (int e = cds_allow_lds((const void*)conv2d_wgrad_mfma_kernel<K, S, CB, TX>, ldsb, ok)) return e;
-  hipLaunchKernelGGL((conv2d_wgrad_mfma_kernel<K, S, CB, TX>), grid, dim3(256), ldsb, st, g, xin, dw, N, Co, Cin, Ho, Wo, H, W, pad, tx,
-                     ntiles, per);
-  return cds_launch_status();
+  return cds_launch_lds<conv2d_wgrad_mfma_kernel<K, S, CB, TX>>(ldsb > 64 * 1024 ? ldsb : 0, grid, dim3(256), ldsb, st, g, xin, dw, N, Co,
+                                                                Cin, Ho, Wo, H, W, pad, tx, ntiles, per);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------

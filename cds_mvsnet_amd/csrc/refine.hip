@@ -33,6 +33,9 @@ __global__ __launch_bounds__(256) void deconv2d_k3s2_kernel(const float* __restr
   if (p >= H * W) return;
   const int y = p / W, xx = p - y * W;
   const bool xr = xx + 1 < W, yd = y + 1 < H;
+  // per output and input channel the taps are summed first and that sum is added to the accumulator: the accumulator is then a Cin-term
+  // chain.  One fmaf chain over every tap (4 Cin terms at the odd-odd output) carried twice the rounding error of the blocked sums of a
+  // GEMM-based transposed convolution at Cin = 32 (tests/test_refine_kernels_gpu.py)
   float acc[4][CO];
 #pragma unroll
   for (int q = 0; q < 4; ++q)
@@ -49,14 +52,9 @@ __global__ __launch_bounds__(256) void deconv2d_k3s2_kernel(const float* __restr
 #pragma unroll
     for (int c = 0; c < CO; ++c) {
       acc[0][c] = fmaf(i00, w[4 * CO + c], acc[0][c]);
-      acc[1][c] = fmaf(i01, w[3 * CO + c], acc[1][c]);
-      acc[1][c] = fmaf(i00, w[5 * CO + c], acc[1][c]);
-      acc[2][c] = fmaf(i10, w[1 * CO + c], acc[2][c]);
-      acc[2][c] = fmaf(i00, w[7 * CO + c], acc[2][c]);
-      acc[3][c] = fmaf(i11, w[0 * CO + c], acc[3][c]);
-      acc[3][c] = fmaf(i10, w[2 * CO + c], acc[3][c]);
-      acc[3][c] = fmaf(i01, w[6 * CO + c], acc[3][c]);
-      acc[3][c] = fmaf(i00, w[8 * CO + c], acc[3][c]);
+      acc[1][c] += fmaf(i00, w[5 * CO + c], i01 * w[3 * CO + c]);
+      acc[2][c] += fmaf(i00, w[7 * CO + c], i10 * w[1 * CO + c]);
+      acc[3][c] += fmaf(i00, w[8 * CO + c], fmaf(i01, w[6 * CO + c], fmaf(i10, w[2 * CO + c], i11 * w[0 * CO + c])));
     }
   }
   const int Wo = 2 * W;

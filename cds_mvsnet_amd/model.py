@@ -82,6 +82,12 @@ def _pack2d(w: Tensor) -> Tensor:
     return p.contiguous()
 
 
+def _pack_deconv2d(w: Tensor) -> Tensor:
+    """ConvTranspose2d weight [Cin,Cout,3,3] -> [Cin,9,Cout] (cout fastest), the operand of ops.deconv2d_k3s2."""
+    cin, cout = w.shape[:2]
+    return w.permute(0, 2, 3, 1).reshape(cin, 9, cout).contiguous()
+
+
 class _Packed:
     """Lazily built cache of the folded / packed weights of one holder module, one entry per device.
 
@@ -492,7 +498,7 @@ class Refinement(_PackedHolder):
             out[name + ".b"] = shift.contiguous()
         scale, shift = _bn_fold(self.bn)
         w = self.deconv.weight.detach() * scale.view(1, -1, 1, 1)          # [Cin,Cout,3,3]
-        out["deconv.w"] = w.permute(0, 2, 3, 1).reshape(8, 9, 8).contiguous()
+        out["deconv.w"] = _pack_deconv2d(w)
         out["deconv.b"] = shift.contiguous()
         out["res.w"] = _pack2d(self.res.weight.detach())
         return out

@@ -211,9 +211,13 @@ def test_softargmin_conf(tag, dev, ops):
     depth, conf, prob = ops.softargmin_conf(g["prob_pre"].to(dev), g["hyp"].to(dev), want_prob=True)
     assert (prob.cpu() - g["prob"]).abs().max() < 1e-6
     assert (depth.cpu() - g["depth"]).abs().max() < 5e-4
-    # the gathered window index is floor(sum p*idx): a 1-ulp difference can flip it for isolated pixels
-    bad = ((conf.cpu() - g["conf"]).abs() > 1e-5).float().mean()
-    assert bad <= 0.01, bad
+    # the gathered window index is floor(sum p*idx): where the float64 index is within rounding of an integer either neighbouring
+    # window is right, and EVERY pixel must match one of the two (tests/regress_ref.py; bound: 4 planes x the prob tolerance above)
+    import regress_ref as R
+    p64, _, i64 = R.softargmin64(g["prob_pre"], g["hyp"])
+    c0, c1 = R.conf_candidates(p64, i64, R.conf_eps(p64.shape[0]))
+    c = conf.cpu().double()
+    assert bool((torch.minimum((c - c0).abs(), (c - c1).abs()) <= 4e-6).all())
     # edge rows: peaks at d=0 / d=D-1 (window clipped by the zero padding) must match exactly enough
     assert (conf.cpu()[:5, :8] - g["conf"][:5, :8]).abs().max() < 1e-5
 

@@ -180,6 +180,10 @@ SIGNATURES = {
     "cds_grid_hash_build": [P, L, L, P, P, I, P],
     "cds_nn_query_f32": [P, P, L, P, P, P, P, P, P, I, P, F, P, P],
     "cds_thin_round_f32": [P, P, L, P, P, I, P, F, P, P, P],
+    "cds_knn_mean_f64": [P, P, L, P, P, P, P, P, P, I, P, I, F, P, P, P],
+    "cds_knn_mean_wg_f64": [P, P, L, P, P, P, P, P, P, I, P, I, F, P, P, I, P],
+    "cds_radius_count_f32": [P, P, L, P, P, P, P, P, P, I, P, F, I, P, P],
+    "cds_outlier_stats_f64": [P, L, P, L, P, P],
     "cds_transform_points_f32": [P, L, P, P, P],
     "cds_nn_index_f32": [P, P, L, P, P, P, P, P, P, I, P, F, P, P, P],
     "cds_icp_sums_f64": [P, P, L, P, P, P, P, P, P, P, I, P, F, P, L, P, P, P, P],

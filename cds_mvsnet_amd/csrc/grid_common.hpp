@@ -194,6 +194,88 @@ __device__ __forceinline__ Nearest nn_walk(const GridView& g, float qx, float qy
   return n;
 }
 
+// The walk of nn_walk<false> for a sink that keeps more than one candidate (the k nearest: cloud_outlier.hip).  The sink has
+//   float bound() const   a region whose points are all at least this far (squared) cannot change it: the pruning threshold,
+//                         nn_walk's best2 (an equal candidate changes nothing, so >= prunes, as prunable<false>)
+//   void add(float d2)    one candidate, d2 = dx*dx + dy*dy + dz*dz as scan_points
+// Same cells in the same order, same bounds; nn_walk itself is untouched so that its callers keep their bits.
+template <class Sink>
+__device__ __forceinline__ void sink_points(const float4* __restrict__ pts, int b, int e, float qx, float qy, float qz, Sink& s) {
+  for (int j = b; j < e; ++j) {
+    const float4 p = pts[j];
+    const float dx = p.x - qx, dy = p.y - qy, dz = p.z - qz;
+    s.add(dx * dx + dy * dy + dz * dz);
+  }
+}
+
+template <class Sink>
+__device__ __forceinline__ void knn_walk(const GridView& g, float qx, float qy, float qz, Sink& s) {
+  const Frame& f = g.f;
+  const int ncx = (f.nx + 7) >> 3, ncy = (f.ny + 7) >> 3, ncz = (f.nz + 7) >> 3;
+  const float fx = cell_of(qx, f.ox, f.h), fy = cell_of(qy, f.oy, f.h), fz = cell_of(qz, f.oz, f.h);
+  const bool inside = fx >= 0.0f && fx < (float)f.nx && fy >= 0.0f && fy < (float)f.ny && fz >= 0.0f && fz < (float)f.nz;
+  int ix = 0, iy = 0, iz = 0;
+  if (inside) {
+    // 1. the 27 fine cells around the query
+    ix = (int)fx; iy = (int)fy; iz = (int)fz;
+    for (int z = max(iz - 1, 0); z <= min(iz + 1, f.nz - 1); ++z)
+      for (int y = max(iy - 1, 0); y <= min(iy + 1, f.ny - 1); ++y)
+        for (int x = max(ix - 1, 0); x <= min(ix + 1, f.nx - 1); ++x) {
+          const int c = find(g.t, fine_key(x, y, z));
+          if (c >= 0) sink_points(g.pts, g.cell_start[c], g.cell_start[c + 1], qx, qy, qz, s);
+        }
+    float lb = INFINITY;
+    if (ix - 1 > 0) lb = fminf(lb, qx - (f.ox + (float)(ix - 1) * f.h));
+    if (ix + 2 < f.nx) lb = fminf(lb, f.ox + (float)(ix + 2) * f.h - qx);
+    if (iy - 1 > 0) lb = fminf(lb, qy - (f.oy + (float)(iy - 1) * f.h));
+    if (iy + 2 < f.ny) lb = fminf(lb, f.oy + (float)(iy + 2) * f.h - qy);
+    if (iz - 1 > 0) lb = fminf(lb, qz - (f.oz + (float)(iz - 1) * f.h));
+    if (iz + 2 < f.nz) lb = fminf(lb, f.oz + (float)(iz + 2) * f.h - qz);
+    lb -= f.slop;
+    if (lb > 0.0f && lb * lb >= s.bound()) return;
+  }
+  // 2. rings of coarse cells around the query's (clamped) coarse cell, nearest first
+  const int ccx = clamp_cell(floorf(fx * 0.125f), ncx), ccy = clamp_cell(floorf(fy * 0.125f), ncy),
+            ccz = clamp_cell(floorf(fz * 0.125f), ncz);
+  const float hw = 8.0f * f.h;
+  for (int R = 0;; ++R) {
+    if (R > 0) {
+      float lb = INFINITY;
+      if (ccx + R < ncx) lb = fminf(lb, slab_dist(qx, f.ox, f.h, ccx + R));
+      if (ccx - R >= 0) lb = fminf(lb, slab_dist(qx, f.ox, f.h, ccx - R));
+      if (ccy + R < ncy) lb = fminf(lb, slab_dist(qy, f.oy, f.h, ccy + R));
+      if (ccy - R >= 0) lb = fminf(lb, slab_dist(qy, f.oy, f.h, ccy - R));
+      if (ccz + R < ncz) lb = fminf(lb, slab_dist(qz, f.oz, f.h, ccz + R));
+      if (ccz - R >= 0) lb = fminf(lb, slab_dist(qz, f.oz, f.h, ccz - R));
+      if (lb == INFINITY) break;                      // the grid is exhausted
+      lb -= f.slop;
+      if (lb > 0.0f && lb * lb >= s.bound()) break;
+    }
+    for (int cz = max(ccz - R, 0); cz <= min(ccz + R, ncz - 1); ++cz)
+      for (int cy = max(ccy - R, 0); cy <= min(ccy + R, ncy - 1); ++cy) {
+        const bool row = abs(cz - ccz) == R || abs(cy - ccy) == R;
+        const int x0 = row ? max(ccx - R, 0) : ccx - R, x1 = row ? min(ccx + R, ncx - 1) : ccx + R;
+        const int step = row || R == 0 ? 1 : 2 * R;
+        for (int cx = x0; cx <= x1; cx += step) {
+          if (cx < 0 || cx >= ncx) continue;
+          if (box_d2(qx, qy, qz, f.ox + (float)(8 * cx) * f.h, f.oy + (float)(8 * cy) * f.h, f.oz + (float)(8 * cz) * f.h, hw,
+                     f.slop) >= s.bound())
+            continue;
+          const int c = find(g.t, coarse_bits(cx, cy, cz) | kCoarse);
+          if (c < 0) continue;
+          for (int fc = g.coarse_start[c]; fc < g.coarse_start[c + 1]; ++fc) {
+            int x, y, z;
+            decode_fine(g.cell_keys[fc], x, y, z);
+            if (inside && abs(x - ix) <= 1 && abs(y - iy) <= 1 && abs(z - iz) <= 1) continue;   // done in step 1
+            if (box_d2(qx, qy, qz, f.ox + (float)x * f.h, f.oy + (float)y * f.h, f.oz + (float)z * f.h, f.h, f.slop) >= s.bound())
+              continue;
+            sink_points(g.pts, g.cell_start[fc], g.cell_start[fc + 1], qx, qy, qz, s);
+          }
+        }
+      }
+  }
+}
+
 inline bool read_frame(const float* fh, Frame& f) {
   if (!fh) return false;
   f.ox = fh[0]; f.oy = fh[1]; f.oz = fh[2]; f.h = fh[3]; f.slop = fh[4];

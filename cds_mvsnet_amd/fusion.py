@@ -28,6 +28,10 @@ normal of its reference view's depth map (``cds_depth_normals_f32``; it faces th
 in which a surface seen by ten views is written ten times, is merged to one point per occupied voxel (``cds_voxel_merge_f32``).
 With either option the views' points stay on the device until the scan is merged and are downloaded once.
 
+``--outlier_nb K [--outlier_std 2.0]`` and ``--outlier_radius r --outlier_min_nb n`` (``--outlier_max_dist d``) remove the cloud's
+outliers on the device before it is written, after the merge when both are given (:func:`pointcloud.remove_outliers`,
+DESIGN §1.16); ``--from_ply "<out>/{scan}.ply"`` does that to saved clouds, without the fusion and without ``--testpath``.
+
 ``filter_depth(collect=...)`` hands the same pass to a later stage: per reference view the fused depth, the mask, the image, the
 camera and the kept points, on the device.  :mod:`cds_mvsnet_amd.mesh` builds a triangle mesh from them.
 """
@@ -189,7 +193,9 @@ def filter_depth(pair_folder: str, scan_folder: str, plyfilename: str, conf: Seq
                  rel_base: float = DYN_REL_BASE, n_views: Sequence[int] = DYN_VIEWS, normals: bool = False,
                  normal_radius: int = 2, normal_jump: float = 0.01, normal_min_pts: int = 6,
                  merge_voxel: Optional[float] = None, merge_min_points: int = 1,
-                 collect: Optional[List[dict]] = None) -> Dict[str, float]:
+                 collect: Optional[List[dict]] = None, outlier_nb: int = 0, outlier_std: float = 2.0,
+                 outlier_radius: float = 0.0, outlier_min_nb: int = 0,
+                 outlier_max_dist: Optional[float] = None) -> Dict[str, float]:
     """The reference's ``filter_depth`` for one scan: -> PLY at ``plyfilename`` and mean photo/geo/final mask rates.
     ``method="dynamic"`` fuses with :func:`fuse_view_dynamic` (``conf``, ``dist_base``, ``rel_base``, ``n_views``;
     ``thres_disp`` / ``thres_view`` are not used) and also returns ``admitted_at``: {n: share of the reference pixels
@@ -203,6 +209,12 @@ def filter_depth(pair_folder: str, scan_folder: str, plyfilename: str, conf: Seq
     ``points`` then counts the merged cloud and ``merged_from`` the points that went in.  With either option the views' points
     stay on the device until the scan is done; with neither, nothing changes.
 
+    ``outlier_nb`` > 0 and / or ``outlier_radius`` > 0 (with ``outlier_std``, ``outlier_min_nb``, ``outlier_max_dist``): the
+    cloud goes through :func:`pointcloud.remove_outliers` on the device before it is written, after the voxel
+    merge when both are asked for; colours and normals follow the mask, ``points`` counts what is written and the keys of
+    ``remove_outliers``'s ``info`` are added, with ``outliers_removed``.  It cleans the written cloud only: with
+    ``plyfilename`` None it is a ValueError, and what ``collect`` receives is never filtered.
+
     ``collect``: a list that receives, per reference view and in ``pair.txt`` order, what a later stage needs of the same pass
     (:func:`cds_mvsnet_amd.mesh.mesh_scan`), all on the device: {"depth" [h,w] the fused depth, "mask" bool [h,w] the
     fusion mask, "image" uint8 [h,w,3], "cam" [2,4,4] (CPU), "points" [k,3] the kept world points, "conf" [h,w] the view's
@@ -212,12 +224,18 @@ def filter_depth(pair_folder: str, scan_folder: str, plyfilename: str, conf: Seq
         raise ValueError(f"filter_depth: method must be 'normal' or 'dynamic', got {method!r}")
     if plyfilename is None and collect is None:
         raise ValueError("filter_depth: plyfilename is None and nothing is collected")
-    cloud = bool(normals) or merge_voxel is not None
+    from .pointcloud import check_outlier_args
+    check_outlier_args(outlier_nb, outlier_std, outlier_radius, outlier_min_nb, outlier_max_dist)
+    outliers = dict(nb_neighbors=outlier_nb, std_ratio=outlier_std, radius=outlier_radius, min_neighbors=outlier_min_nb,
+                    max_dist=outlier_max_dist) if outlier_nb > 0 or outlier_radius > 0 else None
+    if outliers is not None and plyfilename is None:
+        raise ValueError("filter_depth: the outlier removal cleans the cloud that is written; plyfilename is None")
+    cloud = bool(normals) or merge_voxel is not None or outliers is not None
     if merge_voxel is not None and not (float(merge_voxel) > 0 and np.isfinite(float(merge_voxel))):
         raise ValueError(f"filter_depth: merge_voxel must be positive, got {merge_voxel}")
     pairs = read_pair_file(os.path.join(pair_folder, "pair.txt"))
     cache: Dict[int, tuple] = {}
-    dev_pts: List[torch.Tensor] = []       # the device-resident path of normals / merge_voxel: per view [k,3] points,
+    dev_pts: List[torch.Tensor] = []       # the device-resident path of normals / merge_voxel / outliers: per view [k,3] points,
     dev_col: List[torch.Tensor] = []       # uint8 colours, normals and two counts (kept by the fusion, kept with a normal)
     dev_nrm: List[torch.Tensor] = []
     dev_cnt: List[torch.Tensor] = []
@@ -279,7 +297,7 @@ def filter_depth(pair_folder: str, scan_folder: str, plyfilename: str, conf: Seq
                 "mean_final_mask": float(np.mean(rates)) if rates else (float(np.mean(cnt[:, 0] / cnt[:, 2])) if len(cnt) else 0.0)}
     elif cloud:
         info = _finish_cloud(plyfilename, dev_pts, dev_col, dev_nrm if normals else None, dev_cnt, merge_voxel,
-                             merge_min_points, device, verbose, scan_folder)
+                             merge_min_points, device, verbose, scan_folder, outliers)
     else:
         p_all = np.concatenate(pts_all, 0) if pts_all else np.zeros((0, 3), np.float32)
         c_all = np.concatenate(col_all, 0) if col_all else np.zeros((0, 3), np.uint8)
@@ -292,8 +310,9 @@ def filter_depth(pair_folder: str, scan_folder: str, plyfilename: str, conf: Seq
 
 
 def _finish_cloud(plyfilename, dev_pts, dev_col, dev_nrm, dev_cnt, merge_voxel, merge_min_points, device, verbose,
-                  scan_folder) -> Dict[str, float]:
-    """The end of the device-resident path of :func:`filter_depth`: concatenate the views, merge once, download once."""
+                  scan_folder, outliers=None) -> Dict[str, float]:
+    """The end of the device-resident path of :func:`filter_depth`: concatenate the views, merge once, remove outliers
+    (``outliers``: the keyword arguments of :func:`pointcloud.remove_outliers`, or None), download once."""
     from .pointcloud import merge_voxels
     pts = torch.cat(dev_pts) if dev_pts else torch.zeros((0, 3), dtype=torch.float32, device=device)
     col = torch.cat(dev_col) if dev_col else torch.zeros((0, 3), dtype=torch.uint8, device=device)
@@ -313,8 +332,21 @@ def _finish_cloud(plyfilename, dev_pts, dev_col, dev_nrm, dev_cnt, merge_voxel, 
         info["merged_from"] = info["points"]
         pts, col, nrm = m["points"], m["colors"], m["normals"]
         info["points"] = int(pts.shape[0])
+    if outliers is not None:
+        pts, col, nrm = clean_cloud(pts, col, nrm, outliers, info)
     write_ply(plyfilename, pts.cpu().numpy(), col.cpu().numpy(), None if nrm is None else nrm.cpu().numpy())
     return info
+
+
+def clean_cloud(pts, col, nrm, outliers: dict, info: dict):
+    """:func:`pointcloud.remove_outliers` with the keyword arguments ``outliers`` on a cloud on the device (points [N,3],
+    colours, normals or None) -> what stays, rows in input order and bit for bit; ``info`` receives the filter's figures,
+    ``outliers_removed`` and the new ``points``."""
+    from .pointcloud import remove_outliers
+    keep = remove_outliers(pts, info=info, **outliers)
+    info["outliers_removed"] = int(pts.shape[0]) - int(keep.sum())
+    info["points"] = int(pts.shape[0]) - info["outliers_removed"]
+    return pts[keep], col[keep], None if nrm is None else nrm[keep]
 
 
 # --------------------------------------------------------------------------------------------------------------- CLI
@@ -345,6 +377,63 @@ def format_cloud(info: Dict[str, float]) -> str:
     return text + (f", merged from {info['merged_from']}" if "merged_from" in info else "")
 
 
+def add_outlier_args(ap: argparse.ArgumentParser) -> None:
+    """The options of DESIGN §1.16, shared by the fusion command lines."""
+    ap.add_argument("--outlier_nb", type=int, default=0, metavar="K",
+                    help="statistical outlier removal: drop a point whose mean distance to its K nearest neighbours exceeds "
+                         "the cloud's mean + --outlier_std standard deviations (0 = off, at most 63)")
+    ap.add_argument("--outlier_std", type=float, default=2.0, metavar="R", help="--outlier_nb: the multiple of the deviation")
+    ap.add_argument("--outlier_radius", type=float, default=0.0, metavar="r",
+                    help="radius outlier removal: drop a point with fewer than --outlier_min_nb others within r (0 = off)")
+    ap.add_argument("--outlier_min_nb", type=int, default=0, metavar="n", help="--outlier_radius: neighbours a point needs")
+    ap.add_argument("--outlier_max_dist", type=float, default=None, metavar="d",
+                    help="--outlier_nb: cap on every neighbour distance (default: 16 cells of the search grid)")
+
+
+def outlier_kwargs(args: argparse.Namespace, ap: Optional[argparse.ArgumentParser] = None) -> dict:
+    """The arguments of :func:`add_outlier_args` as keyword arguments of :func:`filter_depth` / ``gipuma.filter_scan``.  With
+    ``ap``, a bad combination ends the program through ``ap.error`` (status 2) with a message that names the flag."""
+    if ap is not None:
+        from .pointcloud import KNN_MAX_K
+        if not 0 <= args.outlier_nb <= KNN_MAX_K - 1:
+            ap.error(f"--outlier_nb must be in 0..{KNN_MAX_K - 1}, got {args.outlier_nb}")
+        if not (args.outlier_std >= 0 and np.isfinite(args.outlier_std)):
+            ap.error(f"--outlier_std must be finite and >= 0, got {args.outlier_std}")
+        if not (args.outlier_radius >= 0 and np.isfinite(args.outlier_radius)):
+            ap.error(f"--outlier_radius must be finite and >= 0, got {args.outlier_radius}")
+        if args.outlier_min_nb < 0:
+            ap.error(f"--outlier_min_nb must be >= 0, got {args.outlier_min_nb}")
+        if args.outlier_radius > 0 and args.outlier_min_nb < 1:
+            ap.error("--outlier_radius needs --outlier_min_nb >= 1")
+        if args.outlier_min_nb > 0 and not args.outlier_radius > 0:
+            ap.error("--outlier_min_nb belongs to --outlier_radius")
+        if args.outlier_max_dist is not None and not args.outlier_max_dist > 0:
+            ap.error(f"--outlier_max_dist must be positive, got {args.outlier_max_dist}")
+        if args.outlier_max_dist is not None and args.outlier_nb == 0:
+            ap.error("--outlier_max_dist belongs to --outlier_nb")
+    return dict(outlier_nb=args.outlier_nb, outlier_std=args.outlier_std, outlier_radius=args.outlier_radius,
+                outlier_min_nb=args.outlier_min_nb, outlier_max_dist=args.outlier_max_dist)
+
+
+def format_outliers(info: Dict[str, float]) -> str:
+    """", outliers removed 1234 (threshold 0.00321)" for the keys the options of DESIGN §1.16 add; "" without them."""
+    if "outliers_removed" not in info:
+        return ""
+    t = info.get("threshold")
+    return f", outliers removed {info['outliers_removed']}" + (f" (threshold {t:.6g})" if t is not None else "")
+
+
+def clean_ply(src: str, dst: str, device: str = "cuda", **outliers) -> Dict[str, float]:
+    """Re-clean a saved cloud without the fusion: :func:`read_ply_full` -> :func:`pointcloud.remove_outliers` (keyword
+    arguments ``outliers``) -> :func:`write_ply`, normals kept when present.  -> {"points", "outliers_removed", mu, ...}."""
+    p, c, nrm = read_ply_full(src)
+    info: Dict[str, float] = {}
+    pts, col, nrm = clean_cloud(torch.from_numpy(np.ascontiguousarray(p)).to(device), torch.from_numpy(np.ascontiguousarray(c)).to(device),
+                                None if nrm is None else torch.from_numpy(np.ascontiguousarray(nrm)).to(device), outliers, info)
+    write_ply(dst, pts.cpu().numpy(), col.cpu().numpy(), None if nrm is None else nrm.cpu().numpy())
+    return info
+
+
 def _floats(text: str, n: int, what: str) -> List[float]:
     vals = [float(v) for v in text.split(",")]
     if len(vals) != n:
@@ -359,7 +448,7 @@ def format_admitted(admitted_at: Dict[int, float]) -> str:
 
 def parse_args(argv=None) -> argparse.Namespace:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--testpath", required=True, help="the scenes: <testpath>/<scan>/pair.txt")
+    ap.add_argument("--testpath", default=None, help="the scenes: <testpath>/<scan>/pair.txt (not needed with --from_ply)")
     ap.add_argument("--outdir", required=True, help="the infer output folder: <outdir>/<scan>/{depth_est,confidence,cams,images}")
     ap.add_argument("--testlist", required=True, help="text file with one scan name per line")
     ap.add_argument("--filter_method", default="normal", choices=["normal", "dynamic"])
@@ -371,7 +460,16 @@ def parse_args(argv=None) -> argparse.Namespace:
     ap.add_argument("--dyn_views", default="2,10", help="dynamic: n_min,n_max")
     ap.add_argument("--device", default="cuda")
     add_cloud_args(ap)
+    add_outlier_args(ap)
+    ap.add_argument("--from_ply", default=None, metavar="PATTERN",
+                    help="no fusion: read the saved cloud PATTERN with {scan} filled in, remove its outliers (--outlier_*) and write "
+                         "<outdir>/<scan>.ply (normals kept when the file has them)")
     args = ap.parse_args(argv)
+    args.outliers = outlier_kwargs(args, ap)
+    if args.from_ply is not None and not (args.outlier_nb > 0 or args.outlier_radius > 0):
+        ap.error("--from_ply removes outliers from a saved cloud: give --outlier_nb and / or --outlier_radius")
+    if args.from_ply is None and args.testpath is None:
+        ap.error("--testpath is required (without --from_ply)")
     args.conf = _floats(args.conf, 3, "--conf")
     args.dyn_views = tuple(int(v) for v in _floats(args.dyn_views, 2, "--dyn_views"))
     return args
@@ -383,14 +481,23 @@ def main(argv=None) -> Dict[str, Dict[str, float]]:
         scans = [ln.strip() for ln in f if ln.strip()]
     out = {}
     for scan in scans:
+        if args.from_ply is not None:
+            o = args.outliers
+            os.makedirs(args.outdir, exist_ok=True)
+            info = clean_ply(args.from_ply.format(scan=scan), os.path.join(args.outdir, f"{scan}.ply"), args.device,
+                             nb_neighbors=o["outlier_nb"], std_ratio=o["outlier_std"], radius=o["outlier_radius"],
+                             min_neighbors=o["outlier_min_nb"], max_dist=o["outlier_max_dist"])
+            out[scan] = info
+            print(f"{scan}.ply: {info['points']} points{format_outliers(info)}", flush=True)
+            continue
         info = filter_depth(os.path.join(args.testpath, scan), os.path.join(args.outdir, scan),
                             os.path.join(args.outdir, f"{scan}.ply"), conf=args.conf, thres_disp=args.thres_disp,
                             thres_view=args.thres_view, device=args.device, method=args.filter_method,
                             dist_base=args.dyn_dist_base, rel_base=args.dyn_rel_base, n_views=args.dyn_views,
-                            **cloud_kwargs(args))
+                            **cloud_kwargs(args), **args.outliers)
         out[scan] = info
         extra = f", admitted at {format_admitted(info['admitted_at'])}" if "admitted_at" in info else ""
-        extra += format_cloud(info)
+        extra += format_cloud(info) + format_outliers(info)
         print(f"{scan}.ply: {info['points']} points, final mask {info['mean_final_mask']:.3f}{extra}", flush=True)
     return out
 

@@ -162,10 +162,14 @@ def load_scan(scan_folder: str) -> Dict[str, np.ndarray]:
 def filter_scan(scan_folder: str, plyfilename: str, prob_threshold: Sequence[float] = (0.0, 0.0, 0.0),
                 disp_threshold: float = 0.2, num_consistent: int = 3, depth_min: float = DEPTH_MIN,
                 depth_max: float = DEPTH_MAX, device: str = "cuda", merge_voxel: Optional[float] = None,
-                merge_min_points: int = 1) -> Dict[str, int]:
+                merge_min_points: int = 1, outlier_nb: int = 0, outlier_std: float = 2.0, outlier_radius: float = 0.0,
+                outlier_min_nb: int = 0, outlier_max_dist: Optional[float] = None) -> Dict[str, int]:
     """Fuse one ``infer`` scan folder into a PLY at ``plyfilename`` (steps 1-4). -> {"points", "views"}.  ``merge_voxel``: the
     emitted cloud is merged to one point per occupied voxel of that side, voxels with fewer than ``merge_min_points`` points
-    dropped (:func:`pointcloud.merge_voxels`); the dict then also has "merged_from"."""
+    dropped (:func:`pointcloud.merge_voxels`); the dict then also has "merged_from".  ``outlier_*``: the cloud,
+    merged or not, goes through :func:`pointcloud.remove_outliers` as in :func:`fusion.filter_depth`."""
+    from .pointcloud import check_outlier_args
+    check_outlier_args(outlier_nb, outlier_std, outlier_radius, outlier_min_nb, outlier_max_dist)
     s = load_scan(scan_folder)
     out = fuse_views(torch.from_numpy(s["depths"]).to(device), torch.from_numpy(s["confs"]).to(device), s["cams"],
                      torch.from_numpy(s["images"]).to(device), prob_threshold, disp_threshold, num_consistent, depth_min,
@@ -175,6 +179,12 @@ def filter_scan(scan_folder: str, plyfilename: str, prob_threshold: Sequence[flo
         from .pointcloud import merge_voxels
         out = merge_voxels(out["points"], out["colors"], float(merge_voxel), min_points=merge_min_points)
         info = {"points": int(out["points"].shape[0]), "views": info["views"], "merged_from": info["points"]}
+    if outlier_nb > 0 or outlier_radius > 0:
+        from .fusion import clean_cloud
+        pts, col, _ = clean_cloud(out["points"], out["colors"], None,
+                                  dict(nb_neighbors=outlier_nb, std_ratio=outlier_std, radius=outlier_radius,
+                                       min_neighbors=outlier_min_nb, max_dist=outlier_max_dist), info)
+        out = {"points": pts, "colors": col}
     write_ply(plyfilename, out["points"].cpu().numpy(), out["colors"].cpu().numpy())
     return info
 
@@ -246,9 +256,11 @@ def parse_args(argv=None) -> argparse.Namespace:
     ap.add_argument("--num_consistent", type=int, default=3)
     ap.add_argument("--export_fusibile", action="store_true",
                     help="also write fusibile's inputs (depth_est/*_prob_filtered.pfm, points_mvsnet/)")
-    from .fusion import add_cloud_args
+    from .fusion import add_cloud_args, add_outlier_args, outlier_kwargs
     add_cloud_args(ap, normals=False)          # normals are not implemented for this method
+    add_outlier_args(ap)
     args = ap.parse_args(argv)
+    args.outliers = outlier_kwargs(args, ap)
     args.prob_threshold = _thresholds(args.prob_threshold)
     return args
 
@@ -263,9 +275,12 @@ def main(argv=None) -> Dict[str, Dict[str, int]]:
         if args.export_fusibile:
             export_fusibile_inputs(folder, args.prob_threshold)
         out[scan] = filter_scan(folder, os.path.join(args.outdir, f"{scan}.ply"), args.prob_threshold, args.disp_threshold,
-                                args.num_consistent, merge_voxel=args.merge_voxel, merge_min_points=args.merge_min_points)
+                                args.num_consistent, merge_voxel=args.merge_voxel, merge_min_points=args.merge_min_points,
+                                **args.outliers)
         merged = f", merged from {out[scan]['merged_from']}" if "merged_from" in out[scan] else ""
-        print(f"{scan}.ply: {out[scan]['points']} points from {out[scan]['views']} views{merged}", flush=True)
+        from .fusion import format_outliers
+        print(f"{scan}.ply: {out[scan]['points']} points from {out[scan]['views']} views{merged}{format_outliers(out[scan])}",
+              flush=True)
     return out
 
 

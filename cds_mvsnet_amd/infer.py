@@ -11,7 +11,9 @@ the reference views `idx % world == rank` (independent depth maps, no collective
 with `--filter_method gipuma`, the gipuma-style one (gipuma.py; `--prob_threshold`, `--disp_threshold`, `--num_consistent`),
 or, with `--filter_method dynamic`, the dynamic consistency check (fusion.py; `--conf`, `--dyn_dist_base`, `--dyn_rel_base`,
 `--dyn_views`).  `--normals` (`--normal_radius`, `--normal_jump`, `--normal_min_pts`; not for gipuma) adds each point's oriented
-normal and `--merge_voxel SIZE` (`--merge_min_points K`) merges the scan to one point per occupied voxel.
+normal and `--merge_voxel SIZE` (`--merge_min_points K`) merges the scan to one point per occupied voxel (DESIGN.md §1.8);
+`--outlier_nb K` (`--outlier_std R`, `--outlier_max_dist d`) and `--outlier_radius r --outlier_min_nb n` then remove the cloud's
+outliers, for every fusion method.
 `--mesh_voxel SIZE` (`--mesh_trunc T`, `--mesh_min_weight N`; not for gipuma) also writes `<out>/<scan>_mesh.ply`, a triangle mesh
 from the same fusion pass (mesh.py); `--mesh_min_component N` / `--mesh_keep_largest K` drop its small connected
 components first and `--mesh_simplify CELL` (`--mesh_simplify_placement quadric|mean`) then merges the vertices
@@ -228,7 +230,7 @@ def run(args) -> float:
     print(f"[{rank}] average time ({what}): {avg:.4f} s over {len(times)} depth maps")
     if args.fuse:
         # step 2 of the reference's test.py (pcd_filter, test.py:386-396): scans are independent -> shard over ranks
-        from .fusion import cloud_kwargs, filter_depth, format_admitted, format_cloud
+        from .fusion import cloud_kwargs, filter_depth, format_admitted, format_cloud, format_outliers
         from .gipuma import filter_scan
         from .mesh import SMOOTH_KEYS, format_mesh, mesh_scan, smooth_args
 
@@ -266,22 +268,23 @@ def run(args) -> float:
                 info = filter_scan(os.path.join(args.outdir, scan), os.path.join(args.outdir, f"{scan}.ply"),
                                    prob_threshold=[float(p) for p in args.prob_threshold.split(",")],
                                    disp_threshold=args.disp_threshold, num_consistent=args.num_consistent, device=str(dev),
-                                   merge_voxel=args.merge_voxel, merge_min_points=args.merge_min_points)
-                print(f"[{rank}] {scan}.ply: {info['points']} points from {info['views']} views{format_cloud(info)} (gipuma)",
+                                   merge_voxel=args.merge_voxel, merge_min_points=args.merge_min_points, **args.outliers)
+                print(f"[{rank}] {scan}.ply: {info['points']} points from {info['views']} views{format_cloud(info)}"
+                      f"{format_outliers(info)} (gipuma)",
                       flush=True)
                 continue
             if args.filter_method == "dynamic":
                 # the dynamic consistency check: one setting for every scene, thresholds graded by view count
                 info = fuse(scan, conf=[float(c) for c in args.conf.split(",")], device=str(dev), method="dynamic",
                             dist_base=args.dyn_dist_base, rel_base=args.dyn_rel_base,
-                            n_views=[int(v) for v in args.dyn_views.split(",")], **cloud_kwargs(args))
+                            n_views=[int(v) for v in args.dyn_views.split(",")], **cloud_kwargs(args), **args.outliers)
                 print(f"[{rank}] {scan}.ply: {info['points']} points, final mask {info['mean_final_mask']:.3f}, admitted at "
-                      f"{format_admitted(info['admitted_at'])}{format_cloud(info)} (dynamic)", flush=True)
+                      f"{format_admitted(info['admitted_at'])}{format_cloud(info)}{format_outliers(info)} (dynamic)", flush=True)
                 continue
             info = fuse(scan, conf=[float(c) for c in args.conf.split(",")], thres_disp=args.thres_disp,
-                        thres_view=args.thres_view, device=str(dev), **cloud_kwargs(args))
-            print(f"[{rank}] {scan}.ply: {info['points']} points, final mask {info['mean_final_mask']:.3f}{format_cloud(info)}",
-                  flush=True)
+                        thres_view=args.thres_view, device=str(dev), **cloud_kwargs(args), **args.outliers)
+            print(f"[{rank}] {scan}.ply: {info['points']} points, final mask {info['mean_final_mask']:.3f}{format_cloud(info)}"
+                  f"{format_outliers(info)}", flush=True)
     return avg
 
 
@@ -328,8 +331,9 @@ def parse_args(argv=None) -> argparse.Namespace:
     ap.add_argument("--dyn_rel_base", type=float, default=1.0 / 1300.0, help="dynamic: relative depth difference per level")
     ap.add_argument("--dyn_views", default="2,10", metavar="n_min,n_max",
                     help="dynamic: a pixel is kept when n views agree at level n for some n in this range")
-    from .fusion import add_cloud_args
+    from .fusion import add_cloud_args, add_outlier_args, outlier_kwargs
     add_cloud_args(ap)
+    add_outlier_args(ap)
     from .mesh import add_mesh_args, check_clean_args, check_voxel, check_weight_args
     add_mesh_args(ap)
     from .render import add_render_args
@@ -338,6 +342,9 @@ def parse_args(argv=None) -> argparse.Namespace:
                          "DESIGN §1.10)")
     add_render_args(ap)
     args = ap.parse_args(argv)
+    args.outliers = outlier_kwargs(args, ap)
+    if (args.outlier_nb > 0 or args.outlier_radius > 0) and not args.fuse:
+        ap.error("--outlier_nb and --outlier_radius clean the cloud of --fuse: give --fuse as well")
     if args.render_mesh and args.mesh_voxel is None:
         ap.error("--render_mesh renders the mesh of --mesh_voxel: give --fuse --mesh_voxel SIZE as well")
     if not args.render_mesh and (args.export_blended or args.save_image or args.max_rel_diff is not None or args.back != "mask"):

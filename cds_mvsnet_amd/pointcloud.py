@@ -1,6 +1,7 @@
 """Point-cloud primitives of the DTU and Tanks and Temples evaluations on the GPU: capped nearest-neighbour distances (with
 or without the index of the neighbour), greedy thinning to a minimum spacing, voxel grouping with the merge of a fused cloud
-to one attributed point per voxel (``csrc/cloud.hip``), and a PLY vertex reader.
+to one attributed point per voxel (``csrc/cloud.hip``), statistical and radius outlier removal over k-nearest
+distances and neighbour counts (``csrc/cloud_outlier.hip``), and a PLY vertex reader.
 
 The hot paths are the HIP kernels of ``csrc/pointcloud.hip`` and ``csrc/registration.hip`` (``include/cds_mvsnet_hip.h``): a
 sparse uniform grid with 64-bit cell keys and a hash table, queried one point per lane.  torch is used for device memory
@@ -260,6 +261,146 @@ def nearest_index(query: Tensor, target: Tensor, max_dist: float, grid: Optional
     check(_lib.load().cds_nn_index_f32(query.data_ptr(), order.data_ptr(), m, *_grid_args(grid), float(max_dist),
                                        dist.data_ptr(), index.data_ptr(), _stream(query)), "cds_nn_index_f32")
     return dist, index
+
+
+KNN_MAX_K = 64               # CDS_KNN_MAX_K
+_STAT_CHUNK = 4096           # CDS_STAT_CHUNK
+
+
+def knn_cell(cell: float, k: int) -> float:
+    """Fine cell side of a grid searched for k neighbours, from the :func:`default_cell` of the cloud: the 27 cells around a
+    query should hold most of its k nearest (measured, profiles/cloud_outliers.md).  Only speed depends on it."""
+    return cell * (1.5 if k <= 12 else 2.0)
+
+
+def knn_mean_distance(query: Tensor, target: Tensor, k: int, max_dist: float = math.inf, grid: Optional[PointGrid] = None,
+                      cell: Optional[float] = None, want_kth: bool = False):
+    """For every query point [M,3] the mean distance to its ``k`` nearest target points [N,3] -> float64 [M]
+    (cds_knn_mean_f64).  d2 = dx*dx + dy*dy + dz*dz in fp32; a query that is a target point counts itself at 0.
+    The k smallest d2 below ``max_dist``^2 (fp32) give the terms sqrt(d2) in fp64, summed in ascending order; each of the k
+    terms that is missing counts as ``max_dist``; the sum is divided by k.  ``max_dist = inf``: the exact k nearest, min(k, N)
+    terms (the walk then ends only when the grid is exhausted: an isolated query visits all of it).  ``want_kth``: also the
+    distance to the k-th neighbour, float32 [M] (``max_dist`` when a term is missing).  ``grid``: a PointGrid of ``target`` to
+    reuse; ``cell``: its cell side (default: :func:`knn_cell` of :func:`default_cell`)."""
+    query = _points(query, "query")
+    k = int(k)
+    if not 1 <= k <= KNN_MAX_K:
+        raise ValueError(f"knn_mean_distance: k must be in 1..{KNN_MAX_K}, got {k}")
+    if not (max_dist >= 0):
+        raise ValueError(f"knn_mean_distance: max_dist must be >= 0, got {max_dist}")
+    m = query.shape[0]
+    if grid is None:
+        target = _points(target, "target")
+        if target.shape[0] == 0:
+            raise ValueError("knn_mean_distance: no target points")
+        grid = PointGrid(target, cell if cell is not None else knn_cell(default_cell(target), k))
+    mean = torch.empty(m, dtype=torch.float64, device=query.device)
+    kth = torch.empty(m, dtype=torch.float32, device=query.device) if want_kth else None
+    if m > 0:
+        order = torch.sort(grid.keys(query), stable=True)[1]      # cell order: a wave's lanes search the same cells
+        check(_lib.load().cds_knn_mean_f64(query.data_ptr(), order.data_ptr(), m, *_grid_args(grid), k, float(max_dist),
+                                           mean.data_ptr(), kth.data_ptr() if want_kth else None, _stream(query)),
+              "cds_knn_mean_f64")
+    return (mean, kth) if want_kth else mean
+
+
+def radius_count(query: Tensor, target: Tensor, radius: float, cap: int, grid: Optional[PointGrid] = None) -> Tensor:
+    """For every query point [M,3] the number of target points [N,3] with d2 <= ``radius``^2 (fp32, d2 as everywhere here),
+    counted up to ``cap`` -> int32 [M] (cds_radius_count_f32).  A query that is a target point counts itself.  ``grid``: a
+    PointGrid of ``target`` whose cell side is at least ``radius``; by default one is built with the cell of
+    :func:`reduce_points`, just above ``radius``."""
+    query = _points(query, "query")
+    f = float(np.float32(radius))
+    if not (f > 0 and math.isfinite(f)):
+        raise ValueError(f"radius_count: radius must be positive, got {radius}")
+    if int(cap) < 1:
+        raise ValueError(f"radius_count: cap must be >= 1, got {cap}")
+    m = query.shape[0]
+    out = torch.zeros(m, dtype=torch.int32, device=query.device)
+    if grid is None:
+        target = _points(target, "target")
+        if target.shape[0] == 0:
+            return out
+        grid = PointGrid(target, None, thin_dist=f)
+    if float(grid.frame[3]) < f:
+        raise ValueError(f"radius_count: the grid's cell side {float(grid.frame[3])} is below the radius {f}")
+    if m > 0:
+        order = torch.sort(grid.keys(query), stable=True)[1]
+        check(_lib.load().cds_radius_count_f32(query.data_ptr(), order.data_ptr(), m, *_grid_args(grid), f,
+                                               min(int(cap), 2 ** 31 - 1), out.data_ptr(), _stream(query)),
+              "cds_radius_count_f32")
+    return out
+
+
+def outlier_stats(x: Tensor) -> Tensor:
+    """(mean, sample standard deviation) of ``x`` float64 [N >= 1] on the device -> float64 [2] on the device, summed in the
+    fixed order of cds_outlier_stats_f64: one value for the same input, whatever the machine does."""
+    if x.dtype != torch.float64 or x.dim() != 1 or not x.is_cuda or x.numel() < 1:
+        raise ValueError("outlier_stats: expected a non-empty float64 vector on the device")
+    x = x.contiguous()
+    chunks = (x.numel() + _STAT_CHUNK - 1) // _STAT_CHUNK
+    ws = torch.empty(chunks, dtype=torch.float64, device=x.device)
+    out = torch.empty(2, dtype=torch.float64, device=x.device)
+    check(_lib.load().cds_outlier_stats_f64(x.data_ptr(), x.numel(), ws.data_ptr(), chunks, out.data_ptr(), _stream(x)),
+          "cds_outlier_stats_f64")
+    return out
+
+
+def check_outlier_args(nb_neighbors: int = 0, std_ratio: float = 2.0, radius: float = 0.0, min_neighbors: int = 0,
+                       max_dist: Optional[float] = None) -> None:
+    """The argument rules of :func:`remove_outliers` (ValueError); the command lines call it before any work is done."""
+    if not 0 <= int(nb_neighbors) <= KNN_MAX_K - 1:
+        raise ValueError(f"remove_outliers: nb_neighbors must be in 0..{KNN_MAX_K - 1} (k = nb_neighbors + 1 <= {KNN_MAX_K}), "
+                         f"got {nb_neighbors}")
+    if not (std_ratio >= 0 and math.isfinite(std_ratio)):
+        raise ValueError(f"remove_outliers: std_ratio must be finite and >= 0, got {std_ratio}")
+    if not (radius >= 0 and math.isfinite(radius)):
+        raise ValueError(f"remove_outliers: radius must be finite and >= 0, got {radius}")
+    if int(min_neighbors) < 0:
+        raise ValueError(f"remove_outliers: min_neighbors must be >= 0, got {min_neighbors}")
+    if radius > 0 and int(min_neighbors) < 1:
+        raise ValueError("remove_outliers: radius needs min_neighbors >= 1")
+    if int(min_neighbors) > 0 and not radius > 0:
+        raise ValueError("remove_outliers: min_neighbors belongs to the radius filter, give radius > 0")
+    if max_dist is not None and not (max_dist > 0):
+        raise ValueError(f"remove_outliers: max_dist must be positive, got {max_dist}")
+    if max_dist is not None and int(nb_neighbors) == 0:
+        raise ValueError("remove_outliers: max_dist belongs to the statistical filter, give nb_neighbors > 0")
+
+
+def remove_outliers(points: Tensor, nb_neighbors: int = 0, std_ratio: float = 2.0, radius: float = 0.0,
+                    min_neighbors: int = 0, max_dist: Optional[float] = None, info: Optional[dict] = None) -> Tensor:
+    """Keep mask bool [N] of the two standard outlier filters, both judged on the input cloud [N,3]:
+
+    statistical (``nb_neighbors`` > 0): m_i = :func:`knn_mean_distance` of the cloud against itself with
+    k = nb_neighbors + 1 (the point itself at distance 0 plus nb_neighbors others); mu, sigma = :func:`outlier_stats` of m;
+    kept iff m_i <= T = mu + std_ratio * sigma (fp64).  ``max_dist`` caps every neighbour distance (default
+    16 * :func:`default_cell`): it bounds the search of an isolated point, and such a point enters mu and sigma with the cap.
+    radius (``radius`` > 0): kept iff at least ``min_neighbors`` other points lie within ``radius``
+    (:func:`radius_count` with cap = min_neighbors + 1, the point itself included).
+    With both, a point must pass both.  ``info`` receives mu, sigma, threshold (None without the statistical filter),
+    removed_statistical, removed_radius."""
+    points = _points(points, "points")
+    check_outlier_args(nb_neighbors, std_ratio, radius, min_neighbors, max_dist)
+    n = points.shape[0]
+    keep = torch.ones(n, dtype=torch.bool, device=points.device)
+    stats = {"mu": None, "sigma": None, "threshold": None, "removed_statistical": 0, "removed_radius": 0}
+    if n > 0 and int(nb_neighbors) > 0:
+        cell = default_cell(points)
+        cap = 16.0 * cell if max_dist is None else float(max_dist)
+        mean = knn_mean_distance(points, points, int(nb_neighbors) + 1, cap, cell=knn_cell(cell, int(nb_neighbors) + 1))
+        mu, sigma = outlier_stats(mean).cpu().tolist()
+        threshold = mu + float(std_ratio) * sigma
+        ok = mean <= threshold
+        stats.update(mu=mu, sigma=sigma, threshold=threshold, removed_statistical=n - int(ok.sum()))
+        keep &= ok
+    if n > 0 and radius > 0:
+        ok = radius_count(points, points, radius, int(min_neighbors) + 1) >= int(min_neighbors) + 1
+        stats["removed_radius"] = n - int(ok.sum())
+        keep &= ok
+    if info is not None:
+        info.update(stats)
+    return keep
 
 
 def thinning_order(n: int, seed: int = 0) -> Tensor:

@@ -1250,6 +1250,45 @@ int cds_polygon_crop_f32(const float* points, long long n, const double* polygon
                          double axis_max, unsigned char* keep, void* stream);
 
 /*
+ * Outlier removal for fused clouds (csrc/cloud_outlier.hip; cds_mvsnet_amd/pointcloud.py remove_outliers).  The
+ * grid arguments (pts .. frame_host) are those of cds_nn_query_f32; query [m][3] fp32, order as there.  The kernels read only
+ * their inputs and use no atomics, so every result is a function of the inputs.
+ * cds_knn_mean_f64       per query q: d2 = (dx dx + dy dy) + dz dz in fp32 to every grid point (a query that is a grid point finds
+ *                        itself at 0); the accepted candidates are the k smallest d2 among those with d2 < max_dist^2 (fp32
+ *                        product; with max_dist = +inf every point), a multiset, so ties need no rule.  terms = k, or with
+ *                        max_dist = +inf the number accepted, min(k, n).  t_j = sqrt in fp64 of the fp32 d2 for the accepted in
+ *                        ascending d2 order, then (double)max_dist for each missing term;
+ *                        mean[q] = (((0 + t_0) + t_1) + ...) / terms, one IEEE divide.  kth[q] (or NULL) = sqrtf of the largest
+ *                        accepted d2 when no term is missing, else max_dist.  1 <= k <= CDS_KNN_MAX_K, max_dist >= 0.  A query
+ *                        with fewer than k points within max_dist walks the grid until the pruning bounds pass max_dist; with
+ *                        max_dist = +inf and fewer than k grid points, the whole grid.
+ * cds_knn_mean_wg_f64    cds_knn_mean_f64 with the workgroup size as an argument, for measurements: threads = 64, 128 or 256
+ *                        (cds_knn_mean_f64 is threads = 64, one wave).  The candidate lists take k * threads * 4 bytes of LDS;
+ *                        results do not depend on it.
+ * cds_radius_count_f32   count[q] = min(number of grid points with d2 <= radius^2 (fp32), cap), cap >= 1; the scan may stop at
+ *                        cap.  Requires cell side h >= radius (CDS_EINVAL otherwise), as cds_thin_round_f32.
+ * cds_outlier_stats_f64  out[0] = mu = S(x) / n and out[1] = sigma = sqrt(S((x - mu)^2) / (n - 1)), 0 for n = 1; x [n] doubles,
+ *                        out [2] doubles on the DEVICE, n >= 1.  S sums its terms in this order: consecutive chunks of
+ *                        CDS_STAT_CHUNK = 4096 terms, the tail padded with +0.0; in a chunk lane l of 256 starts from +0.0 and
+ *                        adds terms l, l + 256, ..., l + 15 * 256 in that order; the lanes fold by lane[l] += lane[l + s] for
+ *                        s = 128, 64, ..., 1; the chunk sums are added to +0.0 in ascending chunk order.  Two passes (mu, then
+ *                        the squared deviations d * d with d = x - mu).  ws: ws_doubles >= ceil(n / CDS_STAT_CHUNK).
+ */
+#define CDS_KNN_MAX_K 64
+#define CDS_STAT_CHUNK 4096
+int cds_knn_mean_f64(const float* query, const long long* order, long long m, const float* pts, const int* cell_start,
+                     const long long* cell_keys, const int* coarse_start, const long long* table_keys, const int* table_vals,
+                     int log2_slots, const float* frame_host, int k, float max_dist, double* mean, float* kth, void* stream);
+int cds_knn_mean_wg_f64(const float* query, const long long* order, long long m, const float* pts, const int* cell_start,
+                        const long long* cell_keys, const int* coarse_start, const long long* table_keys, const int* table_vals,
+                        int log2_slots, const float* frame_host, int k, float max_dist, double* mean, float* kth, int threads,
+                        void* stream);
+int cds_radius_count_f32(const float* query, const long long* order, long long m, const float* pts, const int* cell_start,
+                         const long long* cell_keys, const int* coarse_start, const long long* table_keys, const int* table_vals,
+                         int log2_slots, const float* frame_host, float radius, int cap, int* count, void* stream);
+int cds_outlier_stats_f64(const double* x, long long n, double* ws, long long ws_doubles, double* out, void* stream);
+
+/*
  * Trajectory alignment of the Tanks and Temples protocol (csrc/ransac.hip, csrc/ransac_common.hpp): RANSAC for
  * the similarity that maps src onto dst, correspondence i <-> i (src, dst [n][3] doubles on the DEVICE), all in float64.
  * cds_ransac_similarity_f64  hypothesis h of `hypotheses` (one per lane) draws k distinct indices (CDS_RANSAC_MIN_SAMPLE <= k <=

@@ -36,6 +36,7 @@ OVERLAP_STAGE1 = os.environ.get("CDS_OVERLAP_STAGE1", "1") != "0"
 OVERLAP_STAGE2 = os.environ.get("CDS_OVERLAP_STAGE2", "0") == "1"   # A/B knob: stage 2 as well (next to the full-resolution FPN level)
 # FeatureNet on channels-last activations (csrc/feat_cl.hip, round 5); CDS_FEAT_CL=0: the planar kernels of rounds 1-4
 USE_FEAT_CL = os.environ.get("CDS_FEAT_CL", "1") != "0"
+USE_VIS_FUSED = os.environ.get("CDS_VIS_FUSED", "1") != "0"       # A/B knob: 0 = the visibility CNN as three launches (the reference)
 USE_CONV00_MFMA = os.environ.get("CDS_CONV00_MFMA", "1") != "0"   # A/B knob: 0 = conv00's branches on the VALU kernels + blend kernel
 # the stage-1 side stream inside a stream capture (fork / join become graph edges); CDS_OVERLAP_IN_CAPTURE=0: captured forwards are one chain
 OVERLAP_IN_CAPTURE = os.environ.get("CDS_OVERLAP_IN_CAPTURE", "1") != "0"
@@ -808,6 +809,10 @@ class StageNet(_PackedHolder):
         s = stage_idx
         with ops.prof("visibility_cnn"):
             if USE_FEAT_CL and f"{s}.ws1" in p and ops.USE_CONV2D_SBF:
+                if USE_VIS_FUSED:
+                    # one row-marching kernel, the two 16-channel activations stay in LDS (csrc/vis_rm.hip); bit-equal to the three below
+                    return ops.vis_cnn_rm(entropy.contiguous(), ref_nc.contiguous(), p[f"{s}.w0"], p[f"{s}.b0"], p[f"{s}.ws1"],
+                                          p[f"{s}.b1"], p[f"{s}.ws2"], p[f"{s}.b2"], p[f"{s}.hw"], p[f"{s}.b3"])
                 # channels-last activations (csrc/feat_cl.hip): layer 1 straight from the two maps, layers 2 / 3 on the matrix cores
                 x = ops.vis_layer1_cl(entropy.contiguous(), ref_nc.contiguous(), p[f"{s}.w0"], p[f"{s}.b0"])
                 x = ops.conv2d_k3_relu_cl(x, p[f"{s}.ws1"], p[f"{s}.b1"])

@@ -1365,6 +1365,26 @@ def conv2d_k3_relu_cl(x_cl: Tensor, wsplit: Tensor, bias: Optional[Tensor], head
     return out
 
 
+def vis_cnn_rm(entropy: Tensor, ref_nc: Tensor, wpk: Tensor, b0: Tensor, ws1: Tensor, b1: Tensor, ws2: Tensor, b2: Tensor,
+               head_w: Tensor, head_b: Tensor) -> Tensor:
+    """The visibility CNN (model.py:14,51) in one row-marching kernel (csrc/vis_rm.hip): entropy, ref_nc [V,h,w] -> [V,h,w], bit-equal
+    to vis_layer1_cl + 2 x conv2d_k3_relu_cl (the second with the head) on the same operands: wpk [2,9,16] / b0 [16]; ws1, ws2 =
+    split_pack_dynconv([w]) of the [16,16,3,3] layers with biases b1, b2 [16]; head_w [16], head_b [1]."""
+    V, h, w = entropy.shape
+    if tuple(ref_nc.shape) != (V, h, w) or tuple(wpk.shape) != (2, 9, 16) or any(t.numel() != 16 for t in (b0, b1, b2, head_w)) \
+            or head_b.numel() != 1:
+        raise ValueError(f"vis_cnn_rm: need entropy / ref_nc [V,h,w], weight [2,9,16], biases [16], head [16] + [1]; got "
+                         f"{tuple(entropy.shape)}, {tuple(ref_nc.shape)}, {tuple(wpk.shape)}")
+    for ws in (ws1, ws2):
+        if ws.dtype != torch.int16 or ws.numel() != 2 * 3 * 1 * 3 * 64 * 8:
+            raise ValueError("vis_cnn_rm: ws1 / ws2 must be split_pack_dynconv([w]) of a [16,16,3,3] weight")
+    out = torch.empty((V, h, w), dtype=torch.float32, device=entropy.device)
+    check(_lib.load().cds_vis_cnn_rm_f32(_dev(entropy, "entropy"), _dev(ref_nc, "ref_nc"), _dev(wpk, "weight"), _dev(b0, "b0"),
+                                         ws1.data_ptr(), _dev(b1, "b1"), ws2.data_ptr(), _dev(b2, "b2"), _dev(head_w, "head_w"),
+                                         _dev(head_b, "head_b"), out.data_ptr(), V, h, w, _stream(entropy)), "cds_vis_cnn_rm_f32")
+    return out
+
+
 def depth_fusion(ref_depth: Tensor, ref_conf: Tensor, src_depths: Tensor, src_confs: Tensor, cams: Tensor,
                  prob_thresh, dist_thresh: float, depth_thresh: float, view_thresh: float,
                  want_view_masks: bool = False):

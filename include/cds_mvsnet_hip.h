@@ -505,6 +505,13 @@ int cds_vis_layer1_cl_f32(const float* entropy, const float* ref_nc, const float
                           int W, void* stream);
 int cds_conv2d_k3_relu_cl_f32(const float* x, const void* weight_split, const float* bias, const float* head_w, const float* head_b,
                               float* out, int N, int Cin, int H, int W, void* stream);
+/* The whole visibility CNN in ONE launch (csrc/vis_rm.hip): a workgroup marches down the rows of a 60-pixel column strip, the two
+ * 16-channel activations stay in LDS rings.  Same operands as the three calls above (w0 [2][9][16] / b0 [16]; ws1, ws2 =
+ * ops.split_pack_dynconv([w]) with b1, b2 [16]; head_w [16], head_b [1]); out [V][H][W] is bit-equal to theirs.  CDS_VIS_NSEG:
+ * number of row segments per strip (A/B and test knob). */
+int cds_vis_cnn_rm_f32(const float* entropy, const float* ref_nc, const float* w0, const float* b0, const void* ws1, const float* b1,
+                       const void* ws2, const float* b2, const float* head_w, const float* head_b, float* out, int V, int H, int W,
+                       void* stream);
 int cds_instnorm_stats_cl_parts(int H, int W);
 int cds_instnorm_stats_cl_f32(const float* x, double* partial, int N, int C, int H, int W, void* stream);
 int cds_instnorm_apply_cl_f32(const float* x, const double* stats, float* out_cl, float* out_chw, int N, int C, int H, int W, int act,

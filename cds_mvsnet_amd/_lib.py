@@ -176,6 +176,11 @@ SIGNATURES = {
     "cds_mesh_sample_max_n": [],
     "cds_mesh_sample_count": [P, L, P, L, DB, P, P, P],
     "cds_mesh_sample_emit": [P, P, L, P, L, P, P, L, P, P, P, P],
+    "cds_texture_votes": [P, P, I, I, I, L, P, I, P],
+    "cds_texture_best": [P, L, I, I, P, P],
+    "cds_texture_cells": [P, L, P, L, P, I, P, L, DB, I, P, P, P],
+    "cds_texture_place": [P, P, L, L, I, P, P, P],
+    "cds_texture_fill": [P, P, L, P, L, P, P, L, P, I, P, P, P, P, L, I, I, I, P, I, P],
     "cds_grid_hash_log2_slots": [L],
     "cds_grid_keys_f32": [P, L, P, P, P],
     "cds_grid_hash_build": [P, L, L, P, P, I, P],

@@ -1,6 +1,6 @@
-// What the mesh kernels share (mesh_clean.hip, mesh_simplify.hip, mesh_smooth.hip, mesh_sample.hip, raster.hip): the launch
-// shape, the size and finiteness tests, the face loader, and the one compaction behind cds_mesh_cc_gather and
-// cds_mesh_simplify_gather.
+// What the mesh kernels share (mesh_clean.hip, mesh_simplify.hip, mesh_smooth.hip, mesh_sample.hip, raster.hip, mesh_texture.hip;
+// DESIGN §1.10-1.15, §1.17): the launch shape, the size and finiteness tests, the face loader, the rasteriser's rule 1, and the one
+// compaction behind cds_mesh_cc_gather and cds_mesh_simplify_gather.
 #pragma once
 #include "cds_common.hpp"
 
@@ -26,6 +26,37 @@ __device__ __forceinline__ bool load_face(const int* __restrict__ faces, long lo
     ok = ok && (unsigned long long)(long long)idx[k] < (unsigned long long)n_vertices;
   }
   return ok;
+}
+
+// Rule 1 of the rasteriser (include/cds_mvsnet_hip.h, "Rendering a triangle mesh"), stated once for raster.hip and
+// mesh_texture.hip.  c: the CDS_RASTER_CAM doubles of one view; X: a world point.  -> the camera-space point and the pixel
+// coordinates, bracketed as the rule writes them.
+struct ViewPoint {
+  double xc0, xc1, z, u, v;
+};
+
+__device__ __forceinline__ ViewPoint view_point(const double* __restrict__ c, double X0, double X1, double X2) {
+  ViewPoint p;
+  p.xc0 = ((c[0] * X0 + c[1] * X1) + c[2] * X2) + c[9];
+  p.xc1 = ((c[3] * X0 + c[4] * X1) + c[5] * X2) + c[10];
+  p.z = ((c[6] * X0 + c[7] * X1) + c[8] * X2) + c[11];
+  p.u = ((c[12] * p.xc0 + c[13] * p.xc1) + c[14] * p.z) / p.z;
+  p.v = (c[15] * p.xc1 + c[16] * p.z) / p.z;
+  return p;
+}
+
+constexpr int kUnusable = INT_MIN;                                       // X and Y of a vertex that rule 1 rejects
+constexpr long long kSnapLimit = 1ll << 28;
+
+// The snapped coordinates of rule 1; false, and both kUnusable, for a vertex that is not usable.
+__device__ __forceinline__ bool snap_point(const ViewPoint& p, int& X, int& Y) {
+  const double sx = floor(p.u * 256.0 + 0.5), sy = floor(p.v * 256.0 + 0.5);
+  // an infinite or NaN u fails |X| < 2^28 as well: u 256 + 0.5 keeps it
+  const bool usable = p.z > 0.0 && fabs(p.u) <= kHuge && fabs(p.v) <= kHuge && fabs(sx) < (double)kSnapLimit &&
+                      fabs(sy) < (double)kSnapLimit;
+  X = usable ? (int)sx : kUnusable;
+  Y = usable ? (int)sy : kUnusable;
+  return usable;
 }
 
 }  // namespace cds_mesh

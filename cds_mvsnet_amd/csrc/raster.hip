@@ -19,10 +19,9 @@ namespace {
 
 using cds_mesh::blocks_for;
 using cds_mesh::kThreads;
+using cds_mesh::kUnusable;
 
 constexpr int kCam = CDS_RASTER_CAM;           // doubles per camera: R 0..8, t 9..11, fx 12, s 13, cx 14, fy 15, cy 16
-constexpr int kUnusable = INT_MIN;             // X of a vertex that rule 1 rejects
-constexpr long long kSnapLimit = 1ll << 28;
 
 // Rules 2 and 3 up to the candidate box of one face in one view.
 struct FaceSetup {
@@ -124,20 +123,13 @@ __global__ __launch_bounds__(kThreads) void raster_project_kernel(const float* _
   if (i >= n_vertices) return;
   const int view = blockIdx.y;
   const double* c = cams + (long long)view * kCam;
-  const double X0 = vertices[3 * i], X1 = vertices[3 * i + 1], X2 = vertices[3 * i + 2];
-  const double xc0 = ((c[0] * X0 + c[1] * X1) + c[2] * X2) + c[9];
-  const double xc1 = ((c[3] * X0 + c[4] * X1) + c[5] * X2) + c[10];
-  const double z = ((c[6] * X0 + c[7] * X1) + c[8] * X2) + c[11];
-  const double u = ((c[12] * xc0 + c[13] * xc1) + c[14] * z) / z;
-  const double v = (c[15] * xc1 + c[16] * z) / z;
-  const double sx = floor(u * 256.0 + 0.5), sy = floor(v * 256.0 + 0.5);
-  // an infinite or NaN u fails |X| < 2^28 as well: u 256 + 0.5 keeps it
-  const bool usable = z > 0.0 && fabs(u) <= 1.7976931348623157e308 && fabs(v) <= 1.7976931348623157e308 &&
-                      fabs(sx) < (double)kSnapLimit && fabs(sy) < (double)kSnapLimit;
+  const cds_mesh::ViewPoint p = cds_mesh::view_point(c, vertices[3 * i], vertices[3 * i + 1], vertices[3 * i + 2]);   // rule 1
+  int X, Y;
+  cds_mesh::snap_point(p, X, Y);
   const long long o = (long long)view * n_vertices + i;
-  xy[2 * o] = usable ? (int)sx : kUnusable;
-  xy[2 * o + 1] = usable ? (int)sy : kUnusable;
-  xc[3 * o] = xc0; xc[3 * o + 1] = xc1; xc[3 * o + 2] = z;
+  xy[2 * o] = X;
+  xy[2 * o + 1] = Y;
+  xc[3 * o] = p.xc0; xc[3 * o + 1] = p.xc1; xc[3 * o + 2] = p.z;
 }
 
 // -------------------------------------------------------------------------------------------------------------------- faces

@@ -22,7 +22,8 @@ of every cell of that side into one, after `--mesh_smooth ITE
 of that mesh as a cloud; `--mesh_weight angle|conf|angle_conf` and `--mesh_interp` (`--mesh_interp_jump J`) weigh
 the pixels and interpolate the depth in the integration.  With `--mesh_voxel`, `--render_mesh` (`--back`, `--max_rel_diff R`, `--save_image`) renders
 that mesh into every view, `<out>/<scan>/depth_mesh/%08d.pfm`, and `--export_blended DIR` writes the tree `fit --dataset blended`
-trains from (render.py).
+trains from (render.py); `--texture` (`--texture_scale S`, `--texture_max_cell C`, `--texture_max_size N`,
+`--texture_min_px P`) textures it from the saved images, `<out>/<scan>_textured.{obj,mtl,png}` (texture.py).
 `--save_stages` also writes the three stages' own depth maps, `<out>/<scan>/depth_stage{1,2,3}/%08d.pfm`, at their resolutions
 (what evaluations/precision.py scores stage by stage; `python -m cds_mvsnet_amd.depth_eval --folders ...`).
 
@@ -254,6 +255,11 @@ def run(args) -> float:
                             max_rel_diff=args.max_rel_diff, save_image=args.save_image, device=kw.get("device", "cuda"))
                 if args.export_blended:
                     export_blended(scan, args.testpath, args.outdir, args.export_blended)
+            if args.texture:
+                # the mesh just written, from the device tensors, textured from the saved images of the scan
+                from .texture import texture_scan
+                texture_scan(os.path.join(args.outdir, scan), info["mesh"], os.path.join(args.testpath, scan),
+                             os.path.join(args.outdir, f"{scan}_textured"), device=kw.get("device", "cuda"), **args.texture_kw)
             return info["cloud"]
 
         if world > 1:  # every rank's depth maps must be on disk before any scan is fused
@@ -341,6 +347,11 @@ def parse_args(argv=None) -> argparse.Namespace:
                     help="--mesh_voxel: render the mesh into every view and write <outdir>/<scan>/depth_mesh/%%08d.pfm (render.py, "
                          "DESIGN §1.10)")
     add_render_args(ap)
+    from .texture import add_texture_args, texture_kwargs
+    ap.add_argument("--texture", action="store_true",
+                    help="--mesh_voxel: texture the mesh from the saved images and write <outdir>/<scan>_textured.{obj,mtl,png} "
+                         "(texture.py, DESIGN §1.17)")
+    add_texture_args(ap)
     args = ap.parse_args(argv)
     args.outliers = outlier_kwargs(args, ap)
     if (args.outlier_nb > 0 or args.outlier_radius > 0) and not args.fuse:
@@ -351,6 +362,9 @@ def parse_args(argv=None) -> argparse.Namespace:
         ap.error("--export_blended, --save_image, --max_rel_diff and --back belong to --render_mesh")
     if args.max_rel_diff is not None and not args.max_rel_diff >= 0:
         ap.error(f"--max_rel_diff must be >= 0, got {args.max_rel_diff}")
+    if args.texture and args.mesh_voxel is None:
+        ap.error("--texture textures the mesh of --mesh_voxel: give --fuse --mesh_voxel SIZE as well")
+    args.texture_kw = texture_kwargs(ap, args, args.texture)
     check_clean_args(ap, args, args.mesh_voxel is not None)
     args.mesh_interp_jump = check_weight_args(ap, args, args.mesh_voxel is not None)
     if args.mesh_voxel is not None:

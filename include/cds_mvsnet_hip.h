@@ -983,6 +983,79 @@ int cds_mesh_sample_emit(const float* vertices, const unsigned char* colors, lon
                          unsigned char* out_colors, int* out_face, void* stream);
 
 /*
+ * A texture atlas for a mesh from the images of a scan: one view and one square cell per face (csrc/mesh_texture.hip;
+ * DESIGN 1.17).
+ *
+ * Inputs.  vertices fp32 [n_vertices][3], colours uint8 [n_vertices][3], faces int32 [n_faces][3]; V views: per view an image
+ *   uint8 [h][w][3] (h and w the view's own) and cams [CDS_RASTER_CAM] doubles as the rasteriser above takes them; scale > 0 (texels per pixel), max_cell
+ *   a power of two in 4 .. CDS_TEXTURE_MAX_CELL, min_px >= 1.  All arithmetic is fp64 from the fp32 or uint8 entries, bracketed
+ *   as written; every decision is made on integers or on one fp64 comparison.
+ * 1. Visibility.  The mesh is rendered into every view by the rasteriser above, unchanged.  votes[v][f] is the number of pixels
+ *      of view v with valid != 0 and face == f: an integer, whatever the order of the additions.
+ * 2. View of a face.  key[f] = max over v of (votes[v][f] << 32) | (0xffffffff - v), a uint64, 0 before the first view: the most
+ *      votes, the lowest view on a tie.  The face is seen iff key >> 32 >= min_px; then view[f] = 0xffffffff - (key & 0xffffffff),
+ *      else view[f] = -1.
+ * 3. Cell size.  For a seen face whose three vertices are usable by rule 1 of the rasteriser in the face's view, (X_i, Y_i) their
+ *      snapped coordinates: L2 = the largest of the three (Xj - Xi)^2 + (Yj - Yi)^2, exact in int64;  t = (scale scale) (double)L2.
+ *      n is the smallest integer >= 1 with (256 n)^2 >= t; c is the smallest power of two >= n + 2, at least 4 and at most
+ *      max_cell.  Evaluated without a square root: c is the smallest power of two p in 4 .. max_cell / 2 with
+ *      (256 (p - 2)) (256 (p - 2)) >= t, both sides doubles, and max_cell when there is none.  Every other face has c = 4.
+ * 4. Packing.  A cell of side c takes (c / 4)^2 units of 4 x 4 texels.  The faces sorted by c descending, stable in the face index:
+ *      start[k] is the sum of the units of the sorted positions before k, total the sum of all.  The cell takes the units
+ *      start .. start + (c / 4)^2 - 1 of the Z-order curve: its origin is x0 = 4 (the even bits of start, packed), y0 = 4 (the odd
+ *      bits).  Every start is a multiple of the cell's own unit count, so cells are aligned to their size and disjoint.
+ *      W is the smallest power of two >= 4 with (W / 4)^2 >= total;  H = W / 2 when 2 total <= (W / 4)^2 and W >= 8, else W.
+ * 5. UV, in texels of the atlas (the texel (x, y) covers [x, x + 1)^2, row y = 0 the first of the image):  corner a at
+ *      (x0 + 1, y0 + 1), b at (x0 + c - 1, y0 + 1), c at (x0 + 1, y0 + c - 1).
+ * 6. Texel (x0 + i, y0 + j) of a cell, 0 <= i, j < c, inside the triangle or not:
+ *      wb = ((i + 0.5) - 1) / (c - 2),  wc = ((j + 0.5) - 1) / (c - 2),  wa = (1 - wb) - wc.
+ *      For a seen face: P = (wa A + wb B) + wc C per coordinate; u, v, z of P by rule 1 of the rasteriser in view[f].  If z > 0
+ *      and u, v are finite:  uc = min(max(u, 0.5), w - 0.5), x = uc - 0.5, xl = floor(x), xh = min(xl + 1, w - 1), fx = x - xl,
+ *      gx = 1 - fx, and likewise vc, y, yl, yh, fy, gy from v and h;  per channel
+ *        value = (((gx gy) I[yl][xl] + (fx gy) I[yl][xh]) + (gx fy) I[yh][xl]) + (fx fy) I[yh][xh],  texel = floor(value + 0.5).
+ *      Otherwise, and for every texel of a face that is not seen:  value = (wa ca + wb cb) + wc cc from the vertex colours,
+ *      texel = floor(clamp(value, 0, 255) + 0.5) with clamp(NaN) = 0.
+ *      A texel that belongs to no cell is 0.
+ *
+ * cds_texture_votes: rule 1 for a chunk of views.  face int32 and valid uint8 [n_views][h][w] as cds_raster_resolve wrote them;
+ *   votes int32 [n_views][n_faces], zeroed by the caller, receives integer atomic adds.  runs 1: the first lane of a run of equal
+ *   faces inside a wave adds the run's length; runs 0: one add per pixel.  The counts are the same.
+ * cds_texture_best: rule 2 for that chunk, whose first view has the index view0: key uint64 [n_faces], zeroed by the caller
+ *   before the first chunk.
+ * cds_texture_cells: the end of rule 2 and rule 3.  cams [n_views] of ALL views.  Writes view int32 [n_faces] and
+ *   cell int32 [n_faces][3] = (0, 0, c).
+ * cds_texture_place: rules 4 and 5 after the caller's sort.  order int64 [n_faces]: the face of every sorted position;
+ *   starts int64 [n_faces].  Writes the origin into cell and uv int32 [n_faces][3][2].  A position whose face, size or start cannot
+ *   come from rule 4 is skipped.
+ * cds_texture_fill: rule 6.  images: image_bytes bytes that hold every view's [h][w][3] image; views int64 [n_views][3]: the byte
+ *   offset of the view's image in images, its h and its w (the views of a scan may differ in size; a face whose view's entry
+ *   does not lie inside images is coloured as an unseen one).  cams [n_views] of all views.
+ *   atlas uint8 [atlas_h][atlas_w][3], 4-byte aligned; every texel is written.  The unit of a texel
+ *   finds its sorted position by a binary search of its Morton index in starts.  per_unit 0: one thread per texel;
+ *   per_unit 1: one thread per 4 x 4 unit.  The texels are the same.  A unit whose tables do not fit together is written 0.
+ *   CDS_EINVAL: a count < 0 or >= 2^31; n_views < 1 (votes, best: outside 1..CDS_RASTER_MAX_CHUNK); view0 < 0; h or w < 1;
+ *   h w >= 2^31; image_bytes < 0; min_px < 1; scale not finite or <= 0; max_cell not a power of two in 4..CDS_TEXTURE_MAX_CELL; total < 0 or
+ *   > CDS_TEXTURE_MAX_UNITS; atlas_w not a power of two in 4..CDS_TEXTURE_MAX_SIZE; atlas_h neither atlas_w nor atlas_w / 2;
+ *   total beyond the atlas; runs or per_unit not 0 or 1; a null required pointer or a misaligned atlas (an empty mesh returns 0
+ *   first, except in fill, which then writes zeros).
+ */
+#define CDS_TEXTURE_MAX_CELL 4096
+#define CDS_TEXTURE_MAX_SIZE 32768
+#define CDS_TEXTURE_MAX_UNITS (1ll << 26)
+int cds_texture_votes(const int* face, const unsigned char* valid, int n_views, int h, int w, long long n_faces, int* votes,
+                      int runs, void* stream);
+int cds_texture_best(const int* votes, long long n_faces, int n_views, int view0, unsigned long long* key, void* stream);
+int cds_texture_cells(const float* vertices, long long n_vertices, const int* faces, long long n_faces, const double* cams,
+                      int n_views, const unsigned long long* key, long long min_px, double scale, int max_cell, int* view,
+                      int* cell, void* stream);
+int cds_texture_place(const long long* order, const long long* starts, long long n_faces, long long total, int max_cell, int* cell,
+                      int* uv, void* stream);
+int cds_texture_fill(const float* vertices, const unsigned char* colors, long long n_vertices, const int* faces, long long n_faces,
+                     const double* cams, const unsigned char* images, long long image_bytes, const long long* views, int n_views,
+                     const int* view, const int* cell, const long long* order, const long long* starts, long long total,
+                     int max_cell, int atlas_h, int atlas_w, unsigned char* atlas, int per_unit, void* stream);
+
+/*
  * Norm-curvature bookkeeping of one FeatureNet level (module.py:250-251,257-258,264-265) in one launch:
  *   nc_sum[i] = (a[i]^2 + b[i]^2 + c[i]^2) / 3,  nc_abs[i] = |c[i]|   for the three DynamicConv curvature maps of the level
  */

@@ -2,7 +2,7 @@
 // pointcloud.hip / grid_common.hpp:
 //
 //   cds_knn_mean_f64        per query the mean distance to its k nearest grid points (capped terms), one query per lane in cell
-//                           order: the walk of cds_nn_query_f32 (knn_walk) with a k-slot candidate list per lane
+//                           order: grid_walk, the walk of cds_nn_query_f32, with a k-slot candidate list per lane as its sink
 //   cds_radius_count_f32    per query the number of grid points within a radius, up to a cap (cell side >= radius)
 //   cds_outlier_stats_f64   mean and sample standard deviation of n doubles, summed in one fixed order
 //
@@ -21,7 +21,7 @@ namespace {
 constexpr int kStatChunk = 4096;   // elements per chunk of the fixed-order sum: 256 lanes x 16
 constexpr int kStatLanes = 256;
 
-// the k smallest d2 below cap2 seen so far; column `col` = &list[lane], stride = lanes per workgroup
+// grid_walk's sink for the k nearest: the k smallest d2 below cap2 seen so far; column `col` = &list[lane], stride = lanes per workgroup
 struct KnnList {
   float* col;
   int stride, k, count;
@@ -39,7 +39,10 @@ struct KnnList {
     }
   }
 
-  __device__ __forceinline__ void add(float d2) {
+  // a region whose points are all at least bound() away cannot change the list: an equal candidate changes nothing for a multiset
+  __device__ __forceinline__ bool skips(float lb2) const { return lb2 >= bound(); }
+
+  __device__ __forceinline__ void add(float d2, const float4&, int) {
     if (!(d2 < bound())) return;          // at or beyond the cap, or no better than the worst of a full list (NaN too)
     if (count < k) {
       col[count * stride] = d2;
@@ -60,7 +63,7 @@ __global__ __launch_bounds__(256) void knn_mean_kernel(const float* __restrict__
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < m; i += (long long)gridDim.x * blockDim.x) {
     const long long qi = order ? order[i] : i;
     KnnList s{list + threadIdx.x, (int)blockDim.x, k, 0, cap2, cap2, 0};
-    knn_walk(g, query[3 * qi], query[3 * qi + 1], query[3 * qi + 2], s);
+    grid_walk(g, query[3 * qi], query[3 * qi + 1], query[3 * qi + 2], s);
     // selection sort of the lane's column: ascending d2, summed as it goes
     double sum = 0.0;
     float last = 0.0f;
@@ -157,16 +160,6 @@ __global__ void stat_finish_kernel(const double* __restrict__ ws, long long chun
   for (long long c = 0; c < chunks; ++c) s += ws[c];
   if (DEVIATION) out[1] = n > 1 ? sqrt(s / (double)(n - 1)) : 0.0;
   else out[0] = s / (double)n;
-}
-
-bool grid_view(const float* pts, const int* cell_start, const long long* cell_keys, const int* coarse_start,
-               const long long* table_keys, const int* table_vals, int log2_slots, const float* frame_host, GridView& g) {
-  Frame f;
-  if (!read_frame(frame_host, f) || log2_slots < 1 || log2_slots > 40) return false;
-  if (!pts || !cell_start || !cell_keys || !coarse_start || !table_keys || !table_vals) return false;
-  g = GridView{(const float4*)pts, cell_start, (const unsigned long long*)cell_keys, coarse_start,
-               Table{(const unsigned long long*)table_keys, table_vals, (1ull << log2_slots) - 1}, f};
-  return true;
 }
 
 }  // namespace

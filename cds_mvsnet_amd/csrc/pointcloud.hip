@@ -14,7 +14,8 @@
 //
 // Frame (frame_host, 8 floats): origin x y z, cell side h, slop, fine cells per axis nx ny nz.  `slop` bounds how far outside
 // its nominal cell box fp32 binning can put a point; every pruning test is widened by it, so pruning never drops a candidate.
-// The grid helpers and the nearest-neighbour walk live in grid_common.hpp (registration.hip shares them).
+// The grid helpers, the neighbour walk (grid_walk, here with the NearestDist sink) and the check of the grid arguments live in
+// grid_common.hpp; registration.hip and cloud_outlier.hip share them.
 #include "grid_common.hpp"
 
 namespace {
@@ -55,8 +56,9 @@ __global__ __launch_bounds__(256) void nn_query_kernel(const float* __restrict__
   const float cap2 = cap * cap;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < m; i += (long long)gridDim.x * blockDim.x) {
     const long long qi = order ? order[i] : i;
-    const float best2 = nn_walk<false>(g, query[3 * qi], query[3 * qi + 1], query[3 * qi + 2], cap2).d2;
-    dist[qi] = best2 < cap2 ? fminf(sqrtf(best2), cap) : cap;
+    NearestDist s{cap2};
+    grid_walk(g, query[3 * qi], query[3 * qi + 1], query[3 * qi + 2], s);
+    dist[qi] = s.d2 < cap2 ? fminf(sqrtf(s.d2), cap) : cap;
   }
 }
 
@@ -133,10 +135,10 @@ extern "C" int cds_nn_query_f32(const float* query, const long long* order, long
                                 float max_dist, float* dist, void* stream) {
   Frame f;
   if (m < 0 || !read_frame(frame_host, f) || !(max_dist >= 0.0f) || log2_slots < 1 || log2_slots > 40) return CDS_EINVAL;
-  if (m == 0) return 0;
-  if (!query || !pts || !cell_start || !cell_keys || !coarse_start || !table_keys || !table_vals || !dist) return CDS_EINVAL;
-  const GridView g{(const float4*)pts, cell_start, (const unsigned long long*)cell_keys, coarse_start,
-                   Table{(const unsigned long long*)table_keys, table_vals, (1ull << log2_slots) - 1}, f};
+  if (m == 0) return 0;                  // an empty query needs no grid: the pointers are not looked at
+  GridView g;
+  if (!query || !dist || !grid_view(pts, cell_start, cell_keys, coarse_start, table_keys, table_vals, log2_slots, frame_host, g))
+    return CDS_EINVAL;
   hipLaunchKernelGGL(nn_query_kernel, dim3(grid_blocks(m)), dim3(256), 0, (hipStream_t)stream, query, order, m, g, max_dist, dist);
   return cds_launch_status();
 }

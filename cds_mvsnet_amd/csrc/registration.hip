@@ -2,7 +2,7 @@
 // They restate what the public evaluation toolbox does with Open3D on the host, over the sparse grid of pointcloud.hip:
 //
 //   cds_transform_points_f32   p = fp32(T x): a 3x4 float64 transform applied in float64, rounded once
-//   cds_nn_index_f32           capped nearest neighbour with the index of the nearest target point (the walk of cds_nn_query_f32)
+//   cds_nn_index_f32           capped nearest neighbour with the index of the nearest target point (grid_walk with the NearestIndex sink)
 //   cds_icp_sums_f64           one registration step: transform, nearest neighbour and the 18 pair sums of the Umeyama update
 //   cds_voxel_mean_f32         voxel_down_sample: the mean of the points of each occupied voxel
 //   cds_polygon_crop_f32       SelectionPolygonVolume: axis range and even-odd polygon test in float64
@@ -39,7 +39,8 @@ __global__ __launch_bounds__(256) void nn_index_kernel(const float* __restrict__
   const float cap2 = cap * cap;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < m; i += (long long)gridDim.x * blockDim.x) {
     const long long qi = order ? order[i] : i;
-    const Nearest n = nn_walk<true>(g, query[3 * qi], query[3 * qi + 1], query[3 * qi + 2], cap2);
+    NearestIndex n{cap2, cap2, 0x7fffffff, -1};
+    grid_walk(g, query[3 * qi], query[3 * qi + 1], query[3 * qi + 2], n);
     const bool hit = n.d2 < cap2;
     dist[qi] = hit ? fminf(sqrtf(n.d2), cap) : cap;
     index[qi] = hit ? n.index : -1;
@@ -71,7 +72,8 @@ __global__ __launch_bounds__(256) void icp_sums_kernel(const float* __restrict__
     const long long si = order ? order[i] : i;
     const double x = (double)src[3 * si], y = (double)src[3 * si + 1], z = (double)src[3 * si + 2];
     const float px = transform_row(T, 0, x, y, z), py = transform_row(T, 1, x, y, z), pz = transform_row(T, 2, x, y, z);
-    const Nearest n = nn_walk<true>(g, px, py, pz, cap2);
+    NearestIndex n{cap2, cap2, 0x7fffffff, -1};
+    grid_walk(g, px, py, pz, n);
     const bool hit = n.d2 < cap2;
     if (index) index[si] = hit ? n.index : -1;
     if (dist) dist[si] = hit ? fminf(sqrtf(n.d2), cap) : cap;
@@ -159,19 +161,6 @@ __global__ __launch_bounds__(256) void polygon_crop_kernel(const float* __restri
     }
     keep[i] = (unsigned char)(crossings & 1);
   }
-}
-
-bool grid_view(const float* pts, const int* cell_start, const long long* cell_keys, const int* coarse_start,
-               const long long* table_keys, const int* table_vals, int log2_slots, const float* frame_host, GridView& g) {
-  if (!pts || !cell_start || !cell_keys || !coarse_start || !table_keys || !table_vals || log2_slots < 1 || log2_slots > 40 ||
-      !read_frame(frame_host, g.f))
-    return false;
-  g.pts = (const float4*)pts;
-  g.cell_start = cell_start;
-  g.cell_keys = (const unsigned long long*)cell_keys;
-  g.coarse_start = coarse_start;
-  g.t = Table{(const unsigned long long*)table_keys, table_vals, (1ull << log2_slots) - 1};
-  return true;
 }
 
 inline int icp_groups(long long m) {

@@ -50,10 +50,7 @@ class PointGrid:
         if n == 0:
             raise ValueError("PointGrid: no points")
         lib = _lib.load()
-        lo, hi = torch.aminmax(points, dim=0)
-        lo, hi = lo.double().cpu().numpy(), hi.double().cpu().numpy()
-        if not (np.isfinite(lo).all() and np.isfinite(hi).all()):
-            raise ValueError("PointGrid: points must be finite")
+        lo, hi = _bounds(points, "PointGrid")
         ext = float((hi - lo).max())
         self.slop = 2.0 ** -18 * (float(np.abs(np.concatenate([lo, hi])).max()) + ext) + 1e-30
         if thin_dist is not None:       # thinning: above min_dist plus the binning error, so 27 cells cover min_dist
@@ -67,11 +64,7 @@ class PointGrid:
         self.device = points.device
         stream = _stream(points)
 
-        keys = torch.empty(n, dtype=torch.int64, device=self.device)
-        check(lib.cds_grid_keys_f32(points.data_ptr(), n, self.frame.data_ptr(), keys.data_ptr(), stream), "cds_grid_keys_f32")
-        skeys, self.perm = torch.sort(keys, stable=True)
-        self.cell_keys, counts = torch.unique_consecutive(skeys, return_counts=True)
-        self.cell_start = _offsets(counts)
+        self.perm, self.cell_start, self.cell_keys, _ = _cell_layout(points, self.frame)
         ckeys, ccounts = torch.unique_consecutive(self.cell_keys >> _LOCAL_BITS, return_counts=True)
         self.coarse_start = _offsets(ccounts)
         all_keys = torch.cat([self.cell_keys, ckeys | _COARSE_FLAG])
@@ -91,16 +84,41 @@ class PointGrid:
 
     def keys(self, points: Tensor) -> Tensor:
         """Fine cell keys of arbitrary points in this grid's frame (coordinates clamped to the grid)."""
-        keys = torch.empty(points.shape[0], dtype=torch.int64, device=self.device)
-        check(_lib.load().cds_grid_keys_f32(points.data_ptr(), points.shape[0], self.frame.data_ptr(), keys.data_ptr(),
-                                            _stream(points)), "cds_grid_keys_f32")
-        return keys
+        return _cell_keys(points, self.frame)
+
+    def query_order(self, query: Tensor) -> Tensor:
+        """The permutation that puts ``query`` [M,3] into cell order (stable): a wave's lanes then search the same cells."""
+        return torch.sort(self.keys(query), stable=True)[1]
+
+
+def _bounds(points: Tensor, what: str):
+    """(min, max) per axis of ``points`` as float64 numpy [3]; ValueError unless all are finite."""
+    lo, hi = torch.aminmax(points, dim=0)
+    lo, hi = lo.double().cpu().numpy(), hi.double().cpu().numpy()
+    if not (np.isfinite(lo).all() and np.isfinite(hi).all()):
+        raise ValueError(f"{what}: points must be finite")
+    return lo, hi
+
+
+def _cell_keys(points: Tensor, frame: Tensor) -> Tensor:
+    keys = torch.empty(points.shape[0], dtype=torch.int64, device=points.device)
+    check(_lib.load().cds_grid_keys_f32(points.data_ptr(), points.shape[0], frame.data_ptr(), keys.data_ptr(), _stream(points)),
+          "cds_grid_keys_f32")
+    return keys
 
 
 def _offsets(counts: Tensor) -> Tensor:
     out = torch.zeros(counts.numel() + 1, dtype=torch.int32, device=counts.device)
     out[1:] = torch.cumsum(counts, 0).to(torch.int32)
     return out
+
+
+def _cell_layout(points: Tensor, frame: Tensor):
+    """``points`` laid out by the cell keys of ``frame`` (CPU float32 [8]) -> (perm int64 [N]: the input indices sorted by key,
+    stable; start int32 [V+1]: cell v holds perm[start[v]:start[v+1]]; keys int64 [V] ascending; counts int64 [V])."""
+    skeys, perm = torch.sort(_cell_keys(points, frame), stable=True)
+    ukeys, counts = torch.unique_consecutive(skeys, return_counts=True)
+    return perm, _offsets(counts), ukeys, counts
 
 
 def voxel_groups(points: Tensor, voxel: float, what: str = "voxel_groups"):
@@ -111,22 +129,12 @@ def voxel_groups(points: Tensor, voxel: float, what: str = "voxel_groups"):
     take."""
     if not (voxel > 0 and math.isfinite(voxel)):
         raise ValueError(f"{what}: voxel must be positive, got {voxel}")
-    n = points.shape[0]
-    lo, hi = torch.aminmax(points, dim=0)
-    lo, hi = lo.double().cpu().numpy(), hi.double().cpu().numpy()
-    if not (np.isfinite(lo).all() and np.isfinite(hi).all()):
-        raise ValueError(f"{what}: points must be finite")
+    lo, hi = _bounds(points, what)
     origin = (lo - 0.5 * float(voxel)).astype(np.float32)
     dims = np.floor((hi - origin.astype(np.float64)) / float(np.float32(voxel))).astype(np.int64) + 2
     if int(dims.max()) > _MAX_AXIS:
         raise ValueError(f"{what}: {int(dims.max())} voxels along one axis, at most {_MAX_AXIS}")
-    frame = torch.tensor([*origin.tolist(), float(voxel), 0.0, *dims.tolist()], dtype=torch.float32)
-    keys = torch.empty(n, dtype=torch.int64, device=points.device)
-    check(_lib.load().cds_grid_keys_f32(points.data_ptr(), n, frame.data_ptr(), keys.data_ptr(), _stream(points)),
-          "cds_grid_keys_f32")
-    skeys, perm = torch.sort(keys, stable=True)
-    ukeys, counts = torch.unique_consecutive(skeys, return_counts=True)
-    return perm, _offsets(counts), ukeys, counts
+    return _cell_layout(points, torch.tensor([*origin.tolist(), float(voxel), 0.0, *dims.tolist()], dtype=torch.float32))
 
 
 def pack_colors(colors: Tensor) -> Tensor:
@@ -214,12 +222,10 @@ def nearest_distance(query: Tensor, target: Tensor, max_dist: float, grid: Optio
     if grid is None:
         target = _points(target, "target")
         grid = PointGrid(target, cell if cell is not None else default_cell(target))
-    order = torch.sort(grid.keys(query), stable=True)[1]          # cell order: a wave's lanes search the same cells
+    order = grid.query_order(query)
     out = torch.empty(m, dtype=torch.float32, device=query.device)
-    check(_lib.load().cds_nn_query_f32(query.data_ptr(), order.data_ptr(), m, grid.pts.data_ptr(), grid.cell_start.data_ptr(),
-                                       grid.cell_keys.data_ptr(), grid.coarse_start.data_ptr(), grid.table_keys.data_ptr(),
-                                       grid.table_vals.data_ptr(), grid.log2_slots, grid.frame.data_ptr(), float(max_dist),
-                                       out.data_ptr(), _stream(query)), "cds_nn_query_f32")
+    check(_lib.load().cds_nn_query_f32(query.data_ptr(), order.data_ptr(), m, *_grid_args(grid), float(max_dist), out.data_ptr(),
+                                       _stream(query)), "cds_nn_query_f32")
     return out
 
 
@@ -257,7 +263,7 @@ def nearest_index(query: Tensor, target: Tensor, max_dist: float, grid: Optional
         grid = index_grid(target, cell)
     elif not grid.indexed:
         raise ValueError("nearest_index: the grid must come from index_grid (its w lane holds the input indices)")
-    order = torch.sort(grid.keys(query), stable=True)[1]
+    order = grid.query_order(query)
     check(_lib.load().cds_nn_index_f32(query.data_ptr(), order.data_ptr(), m, *_grid_args(grid), float(max_dist),
                                        dist.data_ptr(), index.data_ptr(), _stream(query)), "cds_nn_index_f32")
     return dist, index
@@ -297,7 +303,7 @@ def knn_mean_distance(query: Tensor, target: Tensor, k: int, max_dist: float = m
     mean = torch.empty(m, dtype=torch.float64, device=query.device)
     kth = torch.empty(m, dtype=torch.float32, device=query.device) if want_kth else None
     if m > 0:
-        order = torch.sort(grid.keys(query), stable=True)[1]      # cell order: a wave's lanes search the same cells
+        order = grid.query_order(query)
         check(_lib.load().cds_knn_mean_f64(query.data_ptr(), order.data_ptr(), m, *_grid_args(grid), k, float(max_dist),
                                            mean.data_ptr(), kth.data_ptr() if want_kth else None, _stream(query)),
               "cds_knn_mean_f64")
@@ -325,7 +331,7 @@ def radius_count(query: Tensor, target: Tensor, radius: float, cap: int, grid: O
     if float(grid.frame[3]) < f:
         raise ValueError(f"radius_count: the grid's cell side {float(grid.frame[3])} is below the radius {f}")
     if m > 0:
-        order = torch.sort(grid.keys(query), stable=True)[1]
+        order = grid.query_order(query)
         check(_lib.load().cds_radius_count_f32(query.data_ptr(), order.data_ptr(), m, *_grid_args(grid), f,
                                                min(int(cap), 2 ** 31 - 1), out.data_ptr(), _stream(query)),
               "cds_radius_count_f32")
@@ -439,14 +445,13 @@ def reduce_points(points: Tensor, min_dist: float, order: Optional[Tensor] = Non
     state = torch.zeros(n, dtype=torch.uint8, device=points.device)
     counter = torch.zeros(1, dtype=torch.int32, device=points.device)
     stream = _stream(points)
+    pts, cell_start, _, _, *table = _grid_args(grid)         # a thinning round reads the fine level only
     rounds = 0
     while True:
         counter.zero_()
         for k in range(check_every):
-            check(lib.cds_thin_round_f32(grid.pts.data_ptr(), grid.cell_start.data_ptr(), n, grid.table_keys.data_ptr(),
-                                         grid.table_vals.data_ptr(), grid.log2_slots, grid.frame.data_ptr(), f,
-                                         state.data_ptr(), counter.data_ptr() if k == check_every - 1 else None, stream),
-                  "cds_thin_round_f32")
+            check(lib.cds_thin_round_f32(pts, cell_start, n, *table, f, state.data_ptr(),
+                                         counter.data_ptr() if k == check_every - 1 else None, stream), "cds_thin_round_f32")
         rounds += check_every
         if int(counter.item()) == 0:
             break

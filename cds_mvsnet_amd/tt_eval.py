@@ -244,7 +244,7 @@ def icp(source: Tensor, target: Tensor, cap: float, max_iter: int = 20, rel_fitn
         return T, 0.0, 0.0, 0
     grid = index_grid(target)
     # the lanes follow the cell order of the source at the initial transform: later iterates move it by a fraction of the cap
-    order = torch.sort(grid.keys(transform_points(source, T)), stable=True)[1]
+    order = grid.query_order(transform_points(source, T))
     step = PairSums(source, grid, cap, order)
 
     def quality(s):

@@ -23,6 +23,7 @@ import pytest
 import torch
 
 import cloud_outlier_ref as R
+import tt_eval_ref
 from cds_mvsnet_amd import _lib, fusion, gipuma, mvs_io, pointcloud, synth
 
 pytestmark = pytest.mark.gpu
@@ -126,6 +127,43 @@ def test_knn_mean_default_grid_and_workgroup_sizes():
     with pytest.raises(ValueError):
         pointcloud.knn_mean_distance(_dev(cloud), _dev(cloud), 3, max_dist=-1.0)
     assert pointcloud.knn_mean_distance(_dev(cloud[:0]), _dev(cloud), 3).shape == (0,)
+
+
+def test_every_sink_walks_the_same_grid():
+    """One walk, three sinks (grid_common.hpp): over one index_grid and one query set, nearest_distance, the dist of
+    nearest_index and the k-th distance of knn_mean_distance(k = 1) are the same bits, and nearest_index's index is that of
+    tt_eval_ref (argmin of the fp32 d2, the lowest index among ties, -1 where d2 >= cap^2).  Shapes where a walk can go wrong:
+    one target point, 257 points in one fine cell, 1500 points in ~100 fine cells per axis (the ring walk finds almost
+    everything), the 6^3 lattice with cell 1 and caps that are lattice distances; queries on the cloud, off it and outside
+    the grid's box."""
+    cases = []
+    for n, cells in ((1, 0.1), (257, 0.1), (1500, 100.0)):
+        cloud = _cloud(n, 31 * n)
+        query = _queries(cloud, n)
+        ext = max(float((cloud.max(0) - cloud.min(0)).max()), 1e-3)
+        cases.append((f"n={n}", cloud, query, ext / cells, _caps(query, cloud, 1)))
+    g = np.arange(6, dtype=np.float32)
+    lattice = np.stack(np.meshgrid(g, g, g, indexing="ij"), -1).reshape(-1, 3)
+    face = lattice[:36]                                # x = 0; moved out by 1 and 2: nearest at exactly a cap, not accepted
+    query = np.concatenate([lattice, lattice + np.float32(0.5), face - np.float32([1, 0, 0]), face - np.float32([2, 0, 0])])
+    cases.append(("lattice", lattice, query, 1.0, [1.0, 2.0, np.inf]))
+    for name, cloud, query, cell, caps in cases:
+        grid = pointcloud.index_grid(_dev(cloud), cell)
+        q = _dev(query)
+        for cap in caps:
+            want_d, want_i = tt_eval_ref.nearest_index(query, cloud, cap)
+            alone = pointcloud.nearest_distance(q, _dev(cloud), cap, grid=grid).cpu().numpy()
+            dist, index = pointcloud.nearest_index(q, _dev(cloud), cap, grid=grid)
+            kth = pointcloud.knn_mean_distance(q, None, 1, cap, grid=grid, want_kth=True)[1].cpu().numpy()
+            dist, index = dist.cpu().numpy(), index.cpu().numpy()
+            print(f"{name} cap={cap:.4g}: {len(query)} queries, {int((index < 0).sum())} without a neighbour; differing from "
+                  f"nearest_distance: nearest_index {int((_bits(dist) != _bits(alone)).sum())}, knn k=1 "
+                  f"{int((_bits(kth) != _bits(alone)).sum())}; index differs in {int((index != want_i).sum())}")
+            assert alone.dtype == dist.dtype == kth.dtype == np.float32 and index.dtype == np.int32
+            assert np.array_equal(_bits(dist), _bits(alone)), (name, cap)
+            assert np.array_equal(_bits(kth), _bits(alone)), (name, cap)
+            assert np.array_equal(index, want_i), (name, cap)
+            assert np.array_equal(_bits(dist), _bits(want_d)), (name, cap)
 
 
 def test_radius_count():

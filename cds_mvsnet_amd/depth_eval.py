@@ -392,8 +392,7 @@ def main(argv: Optional[Sequence[str]] = None) -> Dict[str, object]:
     dev = torch.device(args.device)
     if dev.type != "cuda":
         raise SystemExit("depth_eval runs on the GPU only (--device cuda[:N])")
-    with open(args.testlist) as f:
-        scans = [ln.strip() for ln in f if ln.strip()]
+    scans = mvs_io.read_testlist(args.testlist)
     jobs = {folder: _folder_jobs(args.gtpath, args.outdir, scans, folder) for folder in args.folders}   # every file resolved first
     results: Dict[str, Dict[str, float]] = {}
     for folder in args.folders:

@@ -35,6 +35,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
+from .mvs_io import read_testlist
 from .pointcloud import PointGrid, default_cell, nearest_distance, read_ply_points, reduce_points, thinning_order
 
 Tensor = torch.Tensor
@@ -305,8 +306,7 @@ def scan_number(name: str) -> int:
 
 def scan_names(testlist: Optional[str], scans: Optional[str]) -> List[str]:
     if testlist:
-        with open(testlist) as f:
-            names = [ln.strip() for ln in f if ln.strip()]
+        names = read_testlist(testlist)
     else:
         names = [s.strip() for s in scans.split(",") if s.strip()]
     return [f"scan{scan_number(s)}" for s in names]

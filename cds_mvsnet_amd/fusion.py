@@ -26,7 +26,7 @@ running the network again.
 ``--normals`` and ``--merge_voxel`` make the cloud usable outside this project: every point gets the oriented
 normal of its reference view's depth map (``cds_depth_normals_f32``; it faces that camera), and the concatenation of the views,
 in which a surface seen by ten views is written ten times, is merged to one point per occupied voxel (``cds_voxel_merge_f32``).
-With either option the views' points stay on the device until the scan is merged and are downloaded once.
+Whatever the options, the views' points stay on the device until the scan is done and are downloaded once.
 
 ``--outlier_nb K [--outlier_std 2.0]`` and ``--outlier_radius r --outlier_min_nb n`` (``--outlier_max_dist d``) remove the cloud's
 outliers on the device before it is written, after the merge when both are given (:func:`pointcloud.remove_outliers`,
@@ -39,25 +39,14 @@ from __future__ import annotations
 
 import argparse
 import os
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 import torch
 
 from . import ops
-from .mvs_io import read_pair_file, read_pfm
-
-
-def read_fusion_cam(path: str) -> np.ndarray:
-    """``cams/%08d_cam.txt`` as written by save_outputs -> [2,4,4] (extrinsic; intrinsic in [:3,:3], [3,3]=1)
-    (test.py:85-95, 285-288)."""
-    with open(path) as f:
-        lines = [ln.rstrip() for ln in f.readlines()]
-    cam = np.zeros((2, 4, 4), dtype=np.float32)
-    cam[0] = np.array(" ".join(lines[1:5]).split(), dtype=np.float32).reshape(4, 4)
-    cam[1, :3, :3] = np.array(" ".join(lines[7:10]).split(), dtype=np.float32).reshape(3, 3)
-    cam[1, 3, 3] = 1.0
-    return cam
+from .mvs_io import ScanFolder, read_pair_file, read_saved_cam as read_fusion_cam, read_testlist   # noqa: F401
+from .ply import read_ply, read_ply_full, write_ply                                                # noqa: F401
 
 
 def camera_chains(ref_cam: torch.Tensor, src_cams: torch.Tensor) -> torch.Tensor:
@@ -114,79 +103,6 @@ def fuse_view_dynamic(ref_depth: torch.Tensor, ref_conf: torch.Tensor, ref_cam: 
     return out
 
 
-_PLY_XYZ = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
-_PLY_NORMAL = [("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")]
-_PLY_RGB = [("red", "u1"), ("green", "u1"), ("blue", "u1")]
-
-
-def write_ply(path: str, points: np.ndarray, colors: np.ndarray, normals: Optional[np.ndarray] = None) -> None:
-    """Binary little-endian PLY with x,y,z float32 + red,green,blue uint8 vertices (what plyfile writes in
-    test.py:370-382).  With ``normals`` [N,3] the vertex is x y z nx ny nz red green blue, the order Open3D and MeshLab write."""
-    n = int(points.shape[0])
-    if normals is not None and tuple(normals.shape) != (n, 3):
-        raise ValueError(f"write_ply: {tuple(normals.shape)} normals for {n} points")
-    fields = _PLY_XYZ + (_PLY_NORMAL if normals is not None else []) + _PLY_RGB
-    rec = np.empty(n, dtype=fields)
-    rec["x"], rec["y"], rec["z"] = points[:, 0], points[:, 1], points[:, 2]
-    if normals is not None:
-        rec["nx"], rec["ny"], rec["nz"] = normals[:, 0], normals[:, 1], normals[:, 2]
-    rec["red"], rec["green"], rec["blue"] = colors[:, 0], colors[:, 1], colors[:, 2]
-    header = ("ply\nformat binary_little_endian 1.0\n" f"element vertex {n}\n"
-              + "".join(f"property {'float' if t == '<f4' else 'uchar'} {name}\n" for name, t in fields) + "end_header\n")
-    with open(path, "wb") as f:
-        f.write(header.encode("ascii"))
-        rec.tofile(f)
-
-
-def read_ply(path: str) -> Tuple[np.ndarray, np.ndarray]:
-    with open(path, "rb") as f:
-        n = None
-        while True:
-            line = f.readline().decode("ascii").strip()
-            if line.startswith("element vertex"):
-                n = int(line.split()[-1])
-            if line == "end_header":
-                break
-        rec = np.frombuffer(f.read(), dtype=[("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"),
-                                             ("blue", "u1")], count=n)
-    return np.stack([rec["x"], rec["y"], rec["z"]], -1), np.stack([rec["red"], rec["green"], rec["blue"]], -1)
-
-
-def read_ply_full(path: str) -> Tuple[np.ndarray, np.ndarray, Optional[np.ndarray]]:
-    """A PLY written by :func:`write_ply`, with or without normals -> (points float32 [N,3], colors uint8 [N,3],
-    normals float32 [N,3] | None)."""
-    with open(path, "rb") as f:
-        n, props = None, []
-        while True:
-            line = f.readline()
-            if not line:
-                raise ValueError(f"{path}: PLY header without end_header")
-            tok = line.decode("ascii").split()
-            if tok[:2] == ["element", "vertex"]:
-                n = int(tok[2])
-            elif tok[:1] == ["property"]:
-                props.append((tok[1], tok[2]))
-            elif tok[:1] == ["end_header"]:
-                break
-        plain = [("float", c) for c in "xyz"] + [("uchar", c) for c in ("red", "green", "blue")]
-        full = plain[:3] + [("float", c) for c in ("nx", "ny", "nz")] + plain[3:]
-        if n is None or props not in (plain, full):
-            raise ValueError(f"{path}: not a vertex layout that write_ply produces: {props}")
-        has_n = props == full
-        rec = np.frombuffer(f.read(), dtype=_PLY_XYZ + (_PLY_NORMAL if has_n else []) + _PLY_RGB, count=n)
-    return (np.stack([rec["x"], rec["y"], rec["z"]], -1), np.stack([rec["red"], rec["green"], rec["blue"]], -1),
-            np.stack([rec["nx"], rec["ny"], rec["nz"]], -1) if has_n else None)
-
-
-def _load_view(scan_folder: str, vid: int):
-    from PIL import Image
-    depth = read_pfm(os.path.join(scan_folder, "depth_est", f"{vid:08d}.pfm"))[0]
-    conf = read_pfm(os.path.join(scan_folder, "confidence", f"{vid:08d}.pfm"))[0]
-    cam = read_fusion_cam(os.path.join(scan_folder, "cams", f"{vid:08d}_cam.txt"))
-    return np.ascontiguousarray(depth, dtype=np.float32), np.ascontiguousarray(conf.transpose(2, 0, 1)), cam, \
-        lambda: np.asarray(Image.open(os.path.join(scan_folder, "images", f"{vid:08d}.jpg")), dtype=np.float32) / 255.0
-
-
 def filter_depth(pair_folder: str, scan_folder: str, plyfilename: str, conf: Sequence[float] = (0.0, 0.0, 0.0),
                  thres_disp: float = 1.0, thres_view: int = 3, n_src_views: int = 10, device: str = "cuda",
                  verbose: bool = False, method: str = "normal", dist_base: float = DYN_DIST_BASE,
@@ -206,8 +122,12 @@ def filter_depth(pair_folder: str, scan_folder: str, plyfilename: str, conf: Seq
     A kept pixel without a normal is dropped; ``no_normal`` is the dropped share of the otherwise kept pixels of the scan
     (``mean_final_mask`` still describes the fusion mask, before that).  ``merge_voxel``: the scan's points are merged to one per
     occupied voxel of that side (:func:`pointcloud.merge_voxels`), voxels with fewer than ``merge_min_points`` points dropped;
-    ``points`` then counts the merged cloud and ``merged_from`` the points that went in.  With either option the views' points
-    stay on the device until the scan is done; with neither, nothing changes.
+    ``points`` then counts the merged cloud and ``merged_from`` the points that went in.
+
+    Whatever the options, a view leaves its kept points, uint8 colours, normals and three counts (kept, kept with a normal,
+    pixels) on the device, and the scan is finished once (:func:`_finish_cloud`): 15 bytes per kept point stay there until
+    then, a few GB for the largest scenes.  ``mean_final_mask`` is ``mean(kept / pixels)`` over the reference views in
+    float64; ``verbose`` prints one line per reference view at the end of the scan.
 
     ``outlier_nb`` > 0 and / or ``outlier_radius`` > 0 (with ``outlier_std``, ``outlier_min_nb``, ``outlier_max_dist``): the
     cloud goes through :func:`pointcloud.remove_outliers` on the device before it is written, after the voxel
@@ -230,101 +150,73 @@ def filter_depth(pair_folder: str, scan_folder: str, plyfilename: str, conf: Seq
                     max_dist=outlier_max_dist) if outlier_nb > 0 or outlier_radius > 0 else None
     if outliers is not None and plyfilename is None:
         raise ValueError("filter_depth: the outlier removal cleans the cloud that is written; plyfilename is None")
-    cloud = bool(normals) or merge_voxel is not None or outliers is not None
     if merge_voxel is not None and not (float(merge_voxel) > 0 and np.isfinite(float(merge_voxel))):
         raise ValueError(f"filter_depth: merge_voxel must be positive, got {merge_voxel}")
     pairs = read_pair_file(os.path.join(pair_folder, "pair.txt"))
+    scan = ScanFolder(scan_folder)
     cache: Dict[int, tuple] = {}
-    dev_pts: List[torch.Tensor] = []       # the device-resident path of normals / merge_voxel / outliers: per view [k,3] points,
-    dev_col: List[torch.Tensor] = []       # uint8 colours, normals and two counts (kept by the fusion, kept with a normal)
-    dev_nrm: List[torch.Tensor] = []
-    dev_cnt: List[torch.Tensor] = []
 
     def view(vid):
         if vid not in cache:
-            d, c, cam, img = _load_view(scan_folder, vid)
-            cache[vid] = (torch.from_numpy(d).to(device), torch.from_numpy(c).to(device), torch.from_numpy(cam), img)
+            cache[vid] = (torch.from_numpy(scan.depth(vid)).to(device), torch.from_numpy(scan.conf(vid)).to(device),
+                          torch.from_numpy(scan.cam(vid)))
         return cache[vid]
 
-    pts_all: List[np.ndarray] = []
-    col_all: List[np.ndarray] = []
-    rates = []
-    hist: List[np.ndarray] = []
-    n_kept = 0
+    fused: List[tuple] = []     # per reference view: (id, points [k,3], colours uint8 [k,3], normals [k,3] | None, counts [3])
+    hist: List[torch.Tensor] = []
     for ref, srcs in pairs:
         srcs = srcs[:n_src_views]
         if not srcs:
             continue
-        rd, rc, rcam, rimg = view(ref)
-        sv = [view(s) for s in srcs]
+        rd, rc, rcam = view(ref)
+        sd, sc, scam = (torch.stack(a) for a in zip(*(view(s) for s in srcs)))
         if method == "dynamic":
-            out = fuse_view_dynamic(rd, rc, rcam, torch.stack([s[0] for s in sv]), torch.stack([s[1] for s in sv]),
-                                    torch.stack([s[2] for s in sv]), conf, dist_base, rel_base, n_views, want_admit=True)
-            # one read-back per view: how many pixels were admitted at each level
-            hist.append(torch.bincount(out["admit"].reshape(-1).long(), minlength=int(n_views[1]) + 1).cpu().numpy()
-                        / float(out["admit"].numel()))
+            out = fuse_view_dynamic(rd, rc, rcam, sd, sc, scam, conf, dist_base, rel_base, n_views, want_admit=True)
+            hist.append(torch.bincount(out["admit"].reshape(-1).long(), minlength=int(n_views[1]) + 1))
         else:
-            out = fuse_view(rd, rc, rcam, torch.stack([s[0] for s in sv]), torch.stack([s[1] for s in sv]),
-                            torch.stack([s[2] for s in sv]), conf, thres_disp, thres_view)
+            out = fuse_view(rd, rc, rcam, sd, sc, scam, conf, thres_disp, thres_view)
         keep = out["mask"] > 0.5
-        img = torch.from_numpy(np.ascontiguousarray(rimg())).to(device)            # [h,w,3]
+        img = torch.from_numpy(scan.image(ref)).to(device)                          # uint8 [h,w,3]
         if collect is not None:
-            collect.append({"depth": out["depth"], "mask": keep, "image": (img * 255).to(torch.uint8), "cam": rcam,
+            collect.append({"depth": out["depth"], "mask": keep, "image": img, "cam": rcam,
                             "points": out["points"][:, keep].t().contiguous(), "conf": rc[-1]})
-        if cloud:
-            kept = keep.sum()
-            if normals:
-                th = torch.tensor([float(c) for c in conf], dtype=torch.float32, device=rc.device).view(3, 1, 1)
-                nrm, ok = ops.depth_normals(rd, rcam[1, :3, :3], rcam[0], valid=(rc > th).all(0), radius=normal_radius,
-                                            jump=normal_jump, min_pts=normal_min_pts)
-                keep = keep & (ok > 0)
-                dev_nrm.append(nrm[:, keep].t().contiguous())
-            dev_pts.append(out["points"][:, keep].t().contiguous())
-            dev_col.append((img[keep] * 255).to(torch.uint8))
-            dev_cnt.append(torch.stack([kept, keep.sum(), torch.as_tensor(keep.numel(), device=kept.device)]))
-            continue
-        rates.append(float(keep.float().mean()))
-        if verbose:
-            print(f"processing {scan_folder}, ref-view{ref:02d}, final-mask:{rates[-1]:.4f}")
-        if plyfilename is None:                      # nothing to write: count, do not download
-            n_kept += int(keep.sum())
-            continue
-        pts_all.append(out["points"][:, keep].t().contiguous().cpu().numpy())
-        col_all.append((img[keep] * 255).to(torch.uint8).cpu().numpy())
-    if plyfilename is None:
-        cnt = torch.stack(dev_cnt).cpu().numpy().astype(np.float64) if dev_cnt else np.zeros((0, 3))
-        info = {"points": n_kept + sum(int(p.shape[0]) for p in dev_pts),
-                "mean_final_mask": float(np.mean(rates)) if rates else (float(np.mean(cnt[:, 0] / cnt[:, 2])) if len(cnt) else 0.0)}
-    elif cloud:
-        info = _finish_cloud(plyfilename, dev_pts, dev_col, dev_nrm if normals else None, dev_cnt, merge_voxel,
-                             merge_min_points, device, verbose, scan_folder, outliers)
-    else:
-        p_all = np.concatenate(pts_all, 0) if pts_all else np.zeros((0, 3), np.float32)
-        c_all = np.concatenate(col_all, 0) if col_all else np.zeros((0, 3), np.uint8)
-        write_ply(plyfilename, p_all, c_all)
-        info = {"points": int(p_all.shape[0]), "mean_final_mask": float(np.mean(rates)) if rates else 0.0}
+        kept, nrm = keep.sum(), None
+        if normals:
+            th = torch.tensor([float(c) for c in conf], dtype=torch.float32, device=rc.device).view(3, 1, 1)
+            nrm, ok = ops.depth_normals(rd, rcam[1, :3, :3], rcam[0], valid=(rc > th).all(0), radius=normal_radius,
+                                        jump=normal_jump, min_pts=normal_min_pts)
+            keep = keep & (ok > 0)
+            nrm = nrm[:, keep].t().contiguous()
+        counts = torch.stack([kept, keep.sum(), kept.new_full((), keep.numel())])      # kept, kept with a normal, pixels
+        fused.append((ref, out["points"][:, keep].t().contiguous(), img[keep], nrm, counts))
+    info = _finish_cloud(plyfilename, fused, bool(normals), merge_voxel, merge_min_points, device, verbose, scan_folder, outliers)
     if method == "dynamic":
-        share = np.mean(hist, 0) if hist else np.zeros(int(n_views[1]) + 1)
+        pixels = torch.stack([f[4][2] for f in fused]).cpu().numpy().astype(np.float64) if fused else None
+        share = np.mean(torch.stack(hist).cpu().numpy() / pixels[:, None], 0) if hist else np.zeros(int(n_views[1]) + 1)
         info["admitted_at"] = {n: float(share[n]) for n in range(int(n_views[0]), int(n_views[1]) + 1)}
     return info
 
 
-def _finish_cloud(plyfilename, dev_pts, dev_col, dev_nrm, dev_cnt, merge_voxel, merge_min_points, device, verbose,
-                  scan_folder, outliers=None) -> Dict[str, float]:
-    """The end of the device-resident path of :func:`filter_depth`: concatenate the views, merge once, remove outliers
-    (``outliers``: the keyword arguments of :func:`pointcloud.remove_outliers`, or None), download once."""
+def _finish_cloud(plyfilename, fused, normals, merge_voxel, merge_min_points, device, verbose, scan_folder,
+                  outliers=None) -> Dict[str, float]:
+    """The end of a scan in :func:`filter_depth`.  ``fused``: per reference view (id, points, colours, normals | None, counts),
+    on the device.  One read-back of the counts gives ``points`` and ``mean_final_mask``; with a ``plyfilename`` the views are
+    concatenated, merged once, cleaned of outliers (``outliers``: the keyword arguments of :func:`pointcloud.remove_outliers`,
+    or None), downloaded once and written."""
     from .pointcloud import merge_voxels
-    pts = torch.cat(dev_pts) if dev_pts else torch.zeros((0, 3), dtype=torch.float32, device=device)
-    col = torch.cat(dev_col) if dev_col else torch.zeros((0, 3), dtype=torch.uint8, device=device)
-    nrm = None
-    if dev_nrm is not None:
-        nrm = torch.cat(dev_nrm) if dev_nrm else torch.zeros((0, 3), dtype=torch.float32, device=device)
-    cnt = torch.stack(dev_cnt).cpu().numpy().astype(np.float64) if dev_cnt else np.zeros((0, 3))    # kept, with normal, pixels
+    cnt = torch.stack([f[4] for f in fused]).cpu().numpy().astype(np.float64) if fused else np.zeros((0, 3))
     if verbose:
-        for k, with_n, px in cnt:
-            print(f"processing {scan_folder}, final-mask:{k / px:.4f}, with a normal:{with_n / px:.4f}")
-    info = {"points": int(pts.shape[0]), "mean_final_mask": float(np.mean(cnt[:, 0] / cnt[:, 2])) if len(cnt) else 0.0}
-    if dev_nrm is not None:
+        for (ref, *_), (k, with_n, px) in zip(fused, cnt):
+            print(f"processing {scan_folder}, ref-view{ref:02d}, final-mask:{k / px:.4f}"
+                  + (f", with a normal:{with_n / px:.4f}" if normals else ""))
+    info = {"points": int(cnt[:, 1].sum()), "mean_final_mask": float(np.mean(cnt[:, 0] / cnt[:, 2])) if len(cnt) else 0.0}
+    if plyfilename is None:
+        return info
+    def cat(i, dtype):
+        return torch.cat([f[i] for f in fused]) if fused else torch.zeros((0, 3), dtype=dtype, device=device)
+
+    pts, col, nrm = cat(1, torch.float32), cat(2, torch.uint8), cat(3, torch.float32) if normals else None
+    if normals:
         kept = float(cnt[:, 0].sum())
         info["no_normal"] = float((kept - cnt[:, 1].sum()) / kept) if kept > 0 else 0.0
     if merge_voxel is not None:
@@ -477,10 +369,8 @@ def parse_args(argv=None) -> argparse.Namespace:
 
 def main(argv=None) -> Dict[str, Dict[str, float]]:
     args = parse_args(argv)
-    with open(args.testlist) as f:
-        scans = [ln.strip() for ln in f if ln.strip()]
     out = {}
-    for scan in scans:
+    for scan in read_testlist(args.testlist):
         if args.from_ply is not None:
             o = args.outliers
             os.makedirs(args.outdir, exist_ok=True)

@@ -40,14 +40,14 @@ import argparse
 import os
 import shutil
 import struct
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
 from . import ops
-from .fusion import read_fusion_cam, write_ply
-from .mvs_io import read_pfm, write_pfm
+from .mvs_io import ScanFolder, read_testlist, write_pfm
+from .ply import write_ply
 
 DEPTH_MIN = 0.001
 DEPTH_MAX = 100000.0
@@ -125,38 +125,11 @@ def fuse_views(depths: torch.Tensor, confs: torch.Tensor, cams, images: torch.Te
 
 
 # ------------------------------------------------------------------------------------------------------------- files
-def view_ids(scan_folder: str) -> List[int]:
-    """The ids of ``images/%08d.jpg`` in ascending order (the views fusibile is given)."""
-    ids = []
-    for name in os.listdir(os.path.join(scan_folder, "images")):
-        stem, ext = os.path.splitext(name)
-        if ext.lower() == ".jpg" and stem.isdigit():
-            ids.append(int(stem))
-    return sorted(ids)
-
-
 def load_scan(scan_folder: str) -> Dict[str, np.ndarray]:
     """depths [V,h,w], confs [V,3,h,w] float32, cams [V,2,4,4], images [V,h,w,3] uint8 and ids [V] of one ``infer`` scan
-    folder; ValueError if the views differ in size."""
-    from PIL import Image
-    ids = view_ids(scan_folder)
-    depths, confs, cams, images = [], [], [], []
-    for vid in ids:
-        d = read_pfm(os.path.join(scan_folder, "depth_est", f"{vid:08d}.pfm"))[0]
-        c = read_pfm(os.path.join(scan_folder, "confidence", f"{vid:08d}.pfm"))[0]
-        img = np.asarray(Image.open(os.path.join(scan_folder, "images", f"{vid:08d}.jpg")).convert("RGB"), dtype=np.uint8)
-        shape = depths[0].shape if depths else d.shape
-        if d.shape != shape or c.shape != shape + (3,) or img.shape != shape + (3,):
-            raise ValueError(f"{scan_folder}: view {vid} has depth {d.shape}, confidence {c.shape} and image {img.shape}; "
-                             f"every view must be {shape[0]}x{shape[1]}")
-        depths.append(d)
-        confs.append(np.ascontiguousarray(c.transpose(2, 0, 1)))
-        cams.append(read_fusion_cam(os.path.join(scan_folder, "cams", f"{vid:08d}_cam.txt")))
-        images.append(img)
-    if not ids:
-        raise ValueError(f"{scan_folder}: no views in images/")
-    return {"ids": np.array(ids), "depths": np.stack(depths), "confs": np.stack(confs), "cams": np.stack(cams),
-            "images": np.stack(images)}
+    folder, the views in ascending id (the views fusibile is given); ValueError if the views differ in size."""
+    scan = ScanFolder(scan_folder)
+    return scan.load_views(scan.view_ids())
 
 
 def filter_scan(scan_folder: str, plyfilename: str, prob_threshold: Sequence[float] = (0.0, 0.0, 0.0),
@@ -222,21 +195,16 @@ def export_fusibile_inputs(scan_folder: str, prob_threshold: Sequence[float] = (
     ``depth_est/<id>_prob_filtered.pfm`` and ``points_mvsnet/`` with ``cams/<image>.P``, ``images/``,
     ``2333__<id>/disp.dmb`` and ``normals.dmb`` (1/sqrt(3) where the depth is positive).  -> the points_mvsnet folder."""
     th = _thresholds(prob_threshold)
-    names = sorted(os.listdir(os.path.join(scan_folder, "images")))
+    scan = ScanFolder(scan_folder)
     point_folder = os.path.join(scan_folder, "points_mvsnet")
     for sub in ("cams", "images"):
         os.makedirs(os.path.join(point_folder, sub), exist_ok=True)
-    for name in names:
-        stem = os.path.splitext(name)[0]
-        depth = read_pfm(os.path.join(scan_folder, "depth_est", stem + ".pfm"))[0]
-        prob = read_pfm(os.path.join(scan_folder, "confidence", stem + ".pfm"))[0]
-        keep = np.ones(depth.shape, bool)
-        for i, p in enumerate(th):
-            keep &= prob[:, :, i] > np.float32(p)
-        depth[~keep] = 0
-        write_pfm(os.path.join(scan_folder, "depth_est", stem + "_prob_filtered.pfm"), depth)
-        cam = read_fusion_cam(os.path.join(scan_folder, "cams", stem + "_cam.txt"))
-        write_projection(os.path.join(point_folder, "cams", name + ".P"), projection_matrix(cam))
+    for vid in scan.view_ids():
+        stem, name = f"{vid:08d}", f"{vid:08d}.jpg"
+        depth = scan.depth(vid)
+        depth[~(scan.conf(vid) > np.array(th, np.float32).reshape(3, 1, 1)).all(0)] = 0
+        write_pfm(scan.path("depth_est", vid, "_prob_filtered.pfm"), depth)
+        write_projection(os.path.join(point_folder, "cams", name + ".P"), projection_matrix(scan.cam(vid)))
         shutil.copyfile(os.path.join(scan_folder, "images", name), os.path.join(point_folder, "images", name))
         view_dir = os.path.join(point_folder, GIPUMA_PREFIX + stem)
         os.makedirs(view_dir, exist_ok=True)
@@ -267,8 +235,7 @@ def parse_args(argv=None) -> argparse.Namespace:
 
 def main(argv=None) -> Dict[str, Dict[str, int]]:
     args = parse_args(argv)
-    with open(args.testlist) as f:
-        scans = [ln.strip() for ln in f if ln.strip()]
+    scans = read_testlist(args.testlist)
     out = {}
     for scan in scans:
         folder = os.path.join(args.outdir, scan)

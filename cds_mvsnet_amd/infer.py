@@ -44,7 +44,7 @@ import numpy as np
 import torch
 
 from . import CDSMVSNet, seeded_init_
-from .mvs_io import EvalScenes, save_outputs, write_pfm
+from .mvs_io import EvalScenes, read_testlist, save_outputs, write_pfm
 
 
 class _Opaque:
@@ -216,8 +216,7 @@ def run(args) -> float:
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     dev = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
     torch.cuda.set_device(dev)
-    with open(args.testlist) as f:
-        scans = [ln.strip() for ln in f if ln.strip()]
+    scans = read_testlist(args.testlist)
     scene_args = dict(nviews=args.num_view, ndepths=args.numdepth, interval_scale=args.interval_scale, max_h=args.max_h,
                       max_w=args.max_w, refine=args.refine, dataset=args.dataset)
     model = build_model(args).to(dev).eval()

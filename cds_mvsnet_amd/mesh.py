@@ -58,6 +58,8 @@ import torch
 
 from . import _lib
 from ._lib import check
+from .mvs_io import read_testlist
+from .ply import read_mesh_ply, write_mesh_ply, write_ply
 
 Tensor = torch.Tensor
 
@@ -781,90 +783,36 @@ def sample_mesh(mesh_dict: Dict[str, Tensor], spacing: float, max_points: int = 
     return out, info
 
 
+def load_mesh(mesh, device="cuda") -> Dict[str, Tensor]:
+    """A mesh file of :func:`write_mesh_ply`, or a mesh dict of this module already on the device -> {"vertices", "colors",
+    "faces"} on the device."""
+    keys = ("vertices", "colors", "faces")
+    if isinstance(mesh, dict):
+        return {k: mesh[k] for k in keys}
+    dev = torch.device(device)
+    return {k: torch.from_numpy(np.ascontiguousarray(a)).to(dev) for k, a in zip(keys, read_mesh_ply(str(mesh)))}
+
+
 def sample_file(path: str, spacing: float, device="cuda", max_points: int = MAX_SAMPLES):
     """The faces of a mesh file of :func:`write_mesh_ply` through :func:`sample_mesh` -> (its result, its info).  ValueError
     that names the file when it holds no face (a cloud: there is no surface to sample)."""
     spacing = check_spacing(spacing, "sample_file")
     try:
-        v, c, f = read_mesh_ply(path)
+        mesh = load_mesh(path, device)
     except ValueError as e:
         raise ValueError(f"{path}: the faces of a mesh are needed to sample its surface, and this is not a mesh file of "
                          f"write_mesh_ply ({e})") from None
-    if len(f) == 0:
+    if len(mesh["faces"]) == 0:
         raise ValueError(f"{path}: no faces: there is no surface to sample")
-    dev = torch.device(device)
-    return sample_mesh({"vertices": torch.from_numpy(np.ascontiguousarray(v)).to(dev), "colors": torch.from_numpy(
-        np.ascontiguousarray(c)).to(dev), "faces": torch.from_numpy(np.ascontiguousarray(f)).to(dev)}, spacing, max_points)
+    return sample_mesh(mesh, spacing, max_points)
 
 
 def write_surface_ply(path: str, mesh_dict: Dict[str, Tensor], spacing: float) -> Dict[str, object]:
     """The sampled surface of a mesh on the device as an ``x y z red green blue`` cloud (:func:`fusion.write_ply`)
     -> sample_mesh's info."""
-    from .fusion import write_ply
     out, info = sample_mesh(mesh_dict, spacing)
     write_ply(path, out["points"].cpu().numpy(), out["colors"].cpu().numpy())
     return info
-
-
-# --------------------------------------------------------------------------------------------------------------------- PLY
-_VERTEX =[("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1")]
-_FACE = [("k", "u1"), ("v", "<i4", (3,))]
-_HEADER = ("ply\nformat binary_little_endian 1.0\nelement vertex {}\nproperty float x\nproperty float y\nproperty float z\n"
-           "property uchar red\nproperty uchar green\nproperty uchar blue\nelement face {}\n"
-           "property list uchar int vertex_indices\nend_header\n")
-
-
-def write_mesh_ply(path: str, vertices: np.ndarray, colors: np.ndarray, faces: np.ndarray) -> None:
-    """Binary little-endian PLY: vertex x y z red green blue, face ``property list uchar int vertex_indices`` (triangles).
-    No normals: viewers derive them from the winding."""
-    vertices, colors, faces = np.asarray(vertices), np.asarray(colors), np.asarray(faces)
-    nv, nf = int(vertices.shape[0]), int(faces.shape[0])
-    if tuple(vertices.shape) != (nv, 3) or tuple(colors.shape) != (nv, 3) or tuple(faces.shape) != (nf, 3):
-        raise ValueError(f"write_mesh_ply: vertices [V,3], colors [V,3], faces [F,3] expected, got {vertices.shape}, {colors.shape}, "
-                         f"{faces.shape}")
-    if nf and (int(faces.min()) < 0 or int(faces.max()) >= nv):
-        raise ValueError(f"write_mesh_ply: faces index outside the {nv} vertices")
-    vrec = np.empty(nv, dtype=_VERTEX)
-    for i, c in enumerate("xyz"):
-        vrec[c] = vertices[:, i]
-    for i, c in enumerate(("red", "green", "blue")):
-        vrec[c] = colors[:, i]
-    frec = np.empty(nf, dtype=_FACE)
-    frec["k"] = 3
-    frec["v"] = faces
-    with open(path, "wb") as f:
-        f.write(_HEADER.format(nv, nf).encode("ascii"))
-        vrec.tofile(f)
-        frec.tofile(f)
-
-
-def read_mesh_ply(path: str):
-    """A file of :func:`write_mesh_ply` -> (vertices float32 [V,3], colors uint8 [V,3], faces int32 [F,3])."""
-    with open(path, "rb") as f:
-        counts, lines = {}, []
-        while True:
-            line = f.readline()
-            if not line:
-                raise ValueError(f"{path}: PLY header without end_header")
-            line = line.decode("ascii", "replace").strip()
-            lines.append(line)
-            tok = line.split()
-            if tok[:1] == ["element"]:
-                counts[tok[1]] = int(tok[2])
-            if line == "end_header":
-                break
-        if "\n".join(lines) + "\n" != _HEADER.format(counts.get("vertex"), counts.get("face")):
-            raise ValueError(f"{path}: not the layout that write_mesh_ply produces")
-        nv, nf = counts["vertex"], counts["face"]
-        vraw = f.read(np.dtype(_VERTEX).itemsize * nv)
-        fraw = f.read(np.dtype(_FACE).itemsize * nf)
-        if len(vraw) != np.dtype(_VERTEX).itemsize * nv or len(fraw) != np.dtype(_FACE).itemsize * nf:
-            raise ValueError(f"{path}: truncated")
-        vrec, frec = np.frombuffer(vraw, dtype=_VERTEX, count=nv), np.frombuffer(fraw, dtype=_FACE, count=nf)
-    if nf and not (frec["k"] == 3).all():
-        raise ValueError(f"{path}: faces that are not triangles")
-    return (np.stack([vrec["x"], vrec["y"], vrec["z"]], -1).reshape(nv, 3), np.stack([vrec["red"], vrec["green"], vrec["blue"]], -1)
-            .reshape(nv, 3), np.ascontiguousarray(frec["v"]).reshape(nf, 3))
 
 
 # -------------------------------------------------------------------------------------------------------------------- scans
@@ -992,11 +940,9 @@ def clean_file(src_ply: str, dst_ply: str, min_component: int = 0, keep_largest:
     simplify = _check_simplify(simplify, placement, "clean_file")
     sample = _check_sample(sample, surface_ply, "clean_file")
     smooth = _check_smooth(smooth, smooth_lambda, smooth_mu, smooth_max_move, "clean_file")
-    dev = torch.device(device)
-    v, c, f = (torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in read_mesh_ply(src_ply))
     alone = simplify == 0 and smooth is None
     clean = (min_component, keep_largest) if alone or int(min_component) > 0 or int(keep_largest) > 0 else None
-    return _finish({"vertices": v, "colors": c, "faces": f}, dst_ply, clean, smooth, simplify, placement, sample, surface_ply)
+    return _finish(load_mesh(src_ply, device), dst_ply, clean, smooth, simplify, placement, sample, surface_ply)
 
 
 def format_mesh(info: Dict[str, object]) -> str:
@@ -1153,8 +1099,7 @@ def main(argv=None) -> Dict[str, Dict[str, object]]:
     if args.filter_method == "gipuma":
         ap.error("--mesh_voxel is not implemented for --filter_method gipuma (its fused point has no single depth map); "
                  "use normal or dynamic")
-    with open(args.testlist) as f:
-        scans = [ln.strip() for ln in f if ln.strip()]
+    scans = read_testlist(args.testlist)
     out = {}
     if args.from_mesh is not None:
         for scan in scans:

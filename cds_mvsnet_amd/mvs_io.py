@@ -92,6 +92,18 @@ def write_cam_file(path: str, cam: np.ndarray) -> None:
         f.write("\n" + " ".join(str(cam[1][3][j]) for j in range(4)) + "\n")
 
 
+def read_saved_cam(path: str) -> np.ndarray:
+    """``cams/%08d_cam.txt`` as written by :func:`write_cam_file` -> [2,4,4] float32 (extrinsic; intrinsic in [:3,:3],
+    [3,3]=1) (test.py:85-95, 285-288).  The depth-range line is not read."""
+    with open(path) as f:
+        lines = [ln.rstrip() for ln in f.readlines()]
+    cam = np.zeros((2, 4, 4), dtype=np.float32)
+    cam[0] = np.array(" ".join(lines[1:5]).split(), dtype=np.float32).reshape(4, 4)
+    cam[1, :3, :3] = np.array(" ".join(lines[7:10]).split(), dtype=np.float32).reshape(3, 3)
+    cam[1, 3, 3] = 1.0
+    return cam
+
+
 def read_pair_file(path: str) -> List[Tuple[int, List[int]]]:
     with open(path) as f:
         n = int(f.readline())
@@ -101,6 +113,12 @@ def read_pair_file(path: str) -> List[Tuple[int, List[int]]]:
             src = [int(x) for x in f.readline().rstrip().split()[1::2]]
             out.append((ref, src))
     return out
+
+
+def read_testlist(path: str) -> List[str]:
+    """One name per line; blank lines skipped."""
+    with open(path) as f:
+        return [ln.strip() for ln in f if ln.strip()]
 
 
 # ------------------------------------------------------------------------------------------------
@@ -200,3 +218,72 @@ def save_outputs(outdir: str, filename: str, depth: np.ndarray, confs: Sequence[
     write_cam_file(paths["cams"], cam)
     img = nearest_resize(np.transpose(img_chw, (1, 2, 0)), h, w)
     Image.fromarray(np.clip(img * 255, 0, 255).astype(np.uint8)).save(paths["images"], quality=95)
+
+
+class ScanFolder:
+    """What :func:`save_outputs` wrote for one scan, ``<outdir>/<scan>/{depth_est,confidence,cams,images}``, read back by
+    view id: the one reader of the stages after the network (fusion, gipuma, mesh, render, texture)."""
+
+    def __init__(self, folder: str):
+        self.folder = folder
+
+    def path(self, sub: str, vid: int, ext: str) -> str:
+        return os.path.join(self.folder, sub, f"{vid:08d}{ext}")
+
+    def view_ids(self) -> List[int]:
+        """The ids of ``images/%08d.jpg`` in ascending order."""
+        stems = (os.path.splitext(name) for name in os.listdir(os.path.join(self.folder, "images")))
+        return sorted(int(stem) for stem, ext in stems if ext.lower() == ".jpg" and stem.isdigit())
+
+    def depth(self, vid: int) -> np.ndarray:
+        """float32 [h,w], contiguous."""
+        return np.ascontiguousarray(read_pfm(self.path("depth_est", vid, ".pfm"))[0], dtype=np.float32)
+
+    def conf(self, vid: int) -> np.ndarray:
+        """The three stage confidences, float32 [3,h,w], contiguous."""
+        return np.ascontiguousarray(read_pfm(self.path("confidence", vid, ".pfm"))[0].transpose(2, 0, 1))
+
+    def cam(self, vid: int) -> np.ndarray:
+        return read_saved_cam(self.path("cams", vid, "_cam.txt"))
+
+    def image(self, vid: int) -> np.ndarray:
+        """uint8 RGB [h,w,3], whatever the mode of the file."""
+        from PIL import Image
+        return np.array(Image.open(self.path("images", vid, ".jpg")).convert("RGB"), dtype=np.uint8)
+
+    def map_size(self, vid: int) -> Tuple[int, int]:
+        """(h, w) of the depth map, from the PFM header alone."""
+        with open(self.path("depth_est", vid, ".pfm"), "rb") as f:
+            f.readline()
+            w, h = (int(x) for x in f.readline().split())
+        return h, w
+
+    def image_size(self, vid: int) -> Tuple[int, int]:
+        """(h, w) of the image, from its header alone."""
+        from PIL import Image
+        with Image.open(self.path("images", vid, ".jpg")) as im:
+            w, h = im.size
+        return h, w
+
+    @staticmethod
+    def groups(vids: Sequence[int], size_of) -> Dict[Tuple[int, int], List[int]]:
+        """``vids`` by ``size_of(vid)`` (:meth:`map_size` or :meth:`image_size`): each group in the given order, the groups in
+        the order of their first view."""
+        out: Dict[Tuple[int, int], List[int]] = {}
+        for vid in vids:
+            out.setdefault(size_of(vid), []).append(vid)
+        return out
+
+    def load_views(self, vids: Sequence[int]) -> Dict[str, np.ndarray]:
+        """ids [V], depths [V,h,w], confs [V,3,h,w] float32, cams [V,2,4,4] and images [V,h,w,3] uint8 of the views ``vids``;
+        ValueError if they differ in size or there are none."""
+        if not len(vids):
+            raise ValueError(f"{self.folder}: no views in images/")
+        views = [(self.depth(v), self.conf(v), self.cam(v), self.image(v)) for v in vids]
+        h, w = views[0][0].shape
+        for vid, (d, c, _, img) in zip(vids, views):
+            if d.shape != (h, w) or c.shape != (3, h, w) or img.shape != (h, w, 3):
+                raise ValueError(f"{self.folder}: view {vid} has depth {d.shape}, confidence {c.shape[1:] + c.shape[:1]} and image "
+                                 f"{img.shape}; every view must be {h}x{w}")
+        depths, confs, cams, images = (np.stack(a) for a in zip(*views))
+        return {"ids": np.array(vids), "depths": depths, "confs": confs, "cams": cams, "images": images}

@@ -18,6 +18,7 @@ import torch
 from . import _lib
 from ._lib import check
 from .ops import _dev, _stream
+from .ply import read_ply_points          # noqa: F401 (the evaluations import it from here)
 
 Tensor = torch.Tensor
 
@@ -462,92 +463,3 @@ def reduce_points(points: Tensor, min_dist: float, order: Optional[Tensor] = Non
     if info is not None:
         info["rounds"] = rounds
     return keep
-
-
-# ---------------------------------------------------------------------------------------------------------------------
-_PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2", "ushort": "u2",
-              "uint16": "u2", "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4",
-              "double": "f8", "float64": "f8"}
-
-
-def read_ply_points(path: str) -> np.ndarray:
-    """x, y, z of the ``vertex`` element of a PLY file as float32 [N,3]: ascii, binary_little_endian or binary_big_endian,
-    any scalar vertex properties (x, y, z picked by name), other elements before or after it skipped (what plyread.m
-    reads at BaseEvalMain_web.m:47-48 and PointCompareMain.m:12-13)."""
-    with open(path, "rb") as f:
-        if f.readline().strip() != b"ply":
-            raise ValueError(f"{path}: not a PLY file")
-        fmt, elements = None, []                      # elements: [name, count, [(prop, type) | (prop, (count_t, item_t))]]
-        while True:
-            line = f.readline()
-            if not line:
-                raise ValueError(f"{path}: PLY header without end_header")
-            tok = line.decode("ascii", "replace").split()
-            if not tok or tok[0] in ("comment", "obj_info"):
-                continue
-            if tok[0] == "end_header":
-                break
-            if tok[0] == "format":
-                fmt = tok[1]
-            elif tok[0] == "element":
-                elements.append([tok[1], int(tok[2]), []])
-            elif tok[0] == "property":
-                if not elements:
-                    raise ValueError(f"{path}: property before any element")
-                if tok[1] == "list":
-                    elements[-1][2].append((tok[4], (_ply_type(tok[2], path), _ply_type(tok[3], path))))
-                else:
-                    elements[-1][2].append((tok[2], _ply_type(tok[1], path)))
-        if fmt not in ("ascii", "binary_little_endian", "binary_big_endian"):
-            raise ValueError(f"{path}: unsupported PLY format {fmt}")
-        names = [e[0] for e in elements]
-        if "vertex" not in names:
-            raise ValueError(f"{path}: no vertex element")
-        end = ">" if fmt == "binary_big_endian" else "<"
-        for name, count, props in elements:
-            if name == "vertex":
-                pnames = [p[0] for p in props]
-                for c in "xyz":
-                    if c not in pnames:
-                        raise ValueError(f"{path}: vertex element has no property {c}")
-                if any(isinstance(p[1], tuple) for p in props):
-                    raise ValueError(f"{path}: list properties in the vertex element are not supported")
-                if fmt == "ascii":
-                    rows = [f.readline() for _ in range(count)]
-                    vals = np.array(b" ".join(rows).split(), dtype=np.float64)
-                    if vals.size != count * len(props):
-                        raise ValueError(f"{path}: truncated ascii vertex data")
-                    vals = vals.reshape(count, len(props))
-                    return np.stack([vals[:, pnames.index(c)] for c in "xyz"], 1).astype(np.float32)
-                dt = np.dtype([(p, end + t) for p, t in props])
-                raw = f.read(dt.itemsize * count)
-                if len(raw) != dt.itemsize * count:
-                    raise ValueError(f"{path}: truncated binary vertex data")
-                rec = np.frombuffer(raw, dtype=dt, count=count)
-                return np.stack([rec[c].astype(np.float32) for c in "xyz"], 1)
-            _skip_element(f, fmt, end, count, props, path)
-    raise AssertionError("unreachable")
-
-
-def _ply_type(t: str, path: str) -> str:
-    if t not in _PLY_TYPES:
-        raise ValueError(f"{path}: unknown PLY type {t}")
-    return _PLY_TYPES[t]
-
-
-def _skip_element(f, fmt, end, count, props, path):
-    if fmt == "ascii":
-        for _ in range(count):
-            f.readline()
-        return
-    if not any(isinstance(p[1], tuple) for p in props):
-        f.seek(np.dtype([(p, end + t) for p, t in props]).itemsize * count, 1)
-        return
-    for _ in range(count):
-        for _, t in props:
-            if isinstance(t, tuple):
-                cdt = np.dtype(end + t[0])
-                k = int(np.frombuffer(f.read(cdt.itemsize), cdt)[0])
-                f.seek(k * np.dtype(t[1]).itemsize, 1)
-            else:
-                f.seek(np.dtype(t).itemsize, 1)

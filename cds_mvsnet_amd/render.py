@@ -27,7 +27,8 @@ import torch
 
 from . import _lib
 from ._lib import check
-from .mesh import check_mesh_device, check_mesh_layout
+from .mesh import check_mesh_device, check_mesh_layout, load_mesh
+from .mvs_io import ScanFolder, read_pair_file, read_testlist, write_pfm
 
 Tensor = torch.Tensor
 
@@ -124,14 +125,6 @@ def render_mesh(vertices: Tensor, faces: Tensor, cams: Tensor, h: int, w: int, c
 
 
 # -------------------------------------------------------------------------------------------------------------------- scans
-def _pfm_size(path: str):
-    """(h, w) from a PFM header."""
-    with open(path, "rb") as f:
-        f.readline()
-        w, h = (int(x) for x in f.readline().split())
-    return h, w
-
-
 def render_scan(scan_out_folder: str, mesh_ply, pair_folder: str, subdir: str = "depth_mesh", back: str = "mask",
                 max_rel_diff: Optional[float] = None, save_image: bool = False, device: str = "cuda", chunk: int = 8,
                 large_px: int = 64) -> Dict[str, object]:
@@ -144,37 +137,24 @@ def render_scan(scan_out_folder: str, mesh_ply, pair_folder: str, subdir: str = 
     differs from the rendered depth by more than R times the rendered depth (a label is kept only where the
     network's own estimate already agrees with the fused surface).  ``save_image`` writes the colour render as ``%08d.jpg``.
     -> {"views", "valid": share of pixels written, "back": share of pixels whose nearest face looks away}."""
-    from .mesh import read_mesh_ply
-    from .mvs_io import read_cam_file, read_pair_file, read_pfm, write_pfm
     if back not in ("mask", "keep"):
         raise ValueError(f"render_scan: back must be 'mask' or 'keep', got {back!r}")
     if max_rel_diff is not None and not float(max_rel_diff) >= 0:
         raise ValueError(f"render_scan: max_rel_diff must be >= 0, got {max_rel_diff}")
     dev = torch.device(device)
-    if isinstance(mesh_ply, dict):
-        vert, col, fac = mesh_ply["vertices"], mesh_ply["colors"], mesh_ply["faces"]
-    else:
-        vert, col, fac = (torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in read_mesh_ply(str(mesh_ply)))
+    mesh = load_mesh(mesh_ply, dev)
+    scan = ScanFolder(scan_out_folder)
     vids = [ref for ref, _ in read_pair_file(os.path.join(pair_folder, "pair.txt"))]
-    groups: Dict[tuple, list] = {}                                  # views by map size, each in pair.txt order
-    cams = {}
-    for vid in vids:
-        intr, extr, _, _ = read_cam_file(os.path.join(scan_out_folder, "cams", f"{vid:08d}_cam.txt"))
-        cam = np.zeros((2, 4, 4), np.float32)
-        cam[0], cam[1, :3, :3] = extr, intr
-        cams[vid] = cam
-        groups.setdefault(_pfm_size(os.path.join(scan_out_folder, "depth_est", f"{vid:08d}.pfm")), []).append(vid)
     os.makedirs(os.path.join(scan_out_folder, subdir), exist_ok=True)
     n_px = n_valid = n_back = 0
-    for (h, w), ids in groups.items():
-        out = render_mesh(vert, fac, torch.from_numpy(np.stack([cams[i] for i in ids])), h, w, colors=col if save_image else None,
-                          chunk=chunk, large_px=large_px)
+    for (h, w), ids in scan.groups(vids, scan.map_size).items():          # views by map size, each in pair.txt order
+        out = render_mesh(mesh["vertices"], mesh["faces"], torch.from_numpy(np.stack([scan.cam(i) for i in ids])), h, w,
+                          colors=mesh["colors"] if save_image else None, chunk=chunk, large_px=large_px)
         hit = out["face"] >= 0
         keep = hit if back == "keep" else out["valid"] != 0
         depth = out["depth"]
         if max_rel_diff is not None:
-            est = torch.from_numpy(np.stack([read_pfm(os.path.join(scan_out_folder, "depth_est", f"{i:08d}.pfm"))[0]
-                                             for i in ids])).to(dev)
+            est = torch.from_numpy(np.stack([scan.depth(i) for i in ids])).to(dev)
             keep = keep & ~((est > 0) & ((depth - est).abs() > float(max_rel_diff) * depth))
         depth = torch.where(keep, depth, torch.zeros_like(depth)).cpu().numpy()
         n_px += hit.numel()
@@ -200,7 +180,6 @@ def export_blended(scan: str, testpath: str, outdir: str, dst: str, subdir: str 
     ``<outdir>/<scan>/images``), ``cams/%08d_cam.txt`` (extrinsic and K of ``<outdir>/<scan>/cams``, which hold K at the saved
     image's resolution, and the depth-range line of the scene's own ``<testpath>/<scan>/cams`` file), ``cams/pair.txt`` (the
     scene's) and ``rendered_depth_maps/%08d.pfm`` (``<outdir>/<scan>/<subdir>``).  -> the number of views."""
-    from .mvs_io import read_pair_file
     src, out = os.path.join(testpath, scan), os.path.join(outdir, scan)
     for sub in ("blended_images", "cams", "rendered_depth_maps"):
         os.makedirs(os.path.join(dst, scan, sub), exist_ok=True)
@@ -245,8 +224,7 @@ def main(argv=None) -> Dict[str, Dict[str, object]]:
     args = ap.parse_args(argv)
     if args.max_rel_diff is not None and not args.max_rel_diff >= 0:
         ap.error(f"--max_rel_diff must be >= 0, got {args.max_rel_diff}")
-    with open(args.testlist) as f:
-        scans = [ln.strip() for ln in f if ln.strip()]
+    scans = read_testlist(args.testlist)
     out = {}
     for scan in scans:
         ply = (args.mesh or os.path.join(args.outdir, "{scan}_mesh.ply")).format(scan=scan)

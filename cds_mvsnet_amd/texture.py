@@ -26,7 +26,8 @@ import torch
 
 from . import _lib
 from ._lib import check
-from .mesh import check_mesh_device, check_mesh_layout
+from .mesh import check_mesh_device, check_mesh_layout, load_mesh
+from .mvs_io import ScanFolder, read_pair_file, read_testlist
 from .render import CAM_DOUBLES, MAX_CHUNK, camera_table, render_mesh
 
 Tensor = torch.Tensor
@@ -253,28 +254,14 @@ def texture_scan(scan_out_folder: str, mesh_ply, pair_folder: str, prefix: str, 
     ``mesh.write_mesh_ply``, or the mesh dict of the mesh stage on the device.  The views are grouped by image size as
     ``render.render_scan`` groups them, each group in pair.txt order, and numbered through the groups.  -> the info of
     :func:`texture_mesh`."""
-    from PIL import Image
-    from .mesh import read_mesh_ply
-    from .mvs_io import read_cam_file, read_pair_file
     check_texture_args(scale, max_cell, max_size, min_px, "texture_scan")
     dev = torch.device(device)
-    if isinstance(mesh_ply, dict):
-        mesh = {k: mesh_ply[k] for k in ("vertices", "colors", "faces")}
-    else:
-        mesh = dict(zip(("vertices", "colors", "faces"),
-                        (torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in read_mesh_ply(str(mesh_ply)))))
+    mesh = load_mesh(mesh_ply, dev)
+    scan = ScanFolder(scan_out_folder)
     vids = [ref for ref, _ in read_pair_file(os.path.join(pair_folder, "pair.txt"))]
-    groups: Dict[tuple, list] = {}                                  # views by image size, each in pair.txt order
-    cams, imgs = {}, {}
-    for vid in vids:
-        intr, extr, _, _ = read_cam_file(os.path.join(scan_out_folder, "cams", f"{vid:08d}_cam.txt"))
-        cam = np.zeros((2, 4, 4), np.float32)
-        cam[0], cam[1, :3, :3] = extr, intr
-        cams[vid] = cam
-        imgs[vid] = np.asarray(Image.open(os.path.join(scan_out_folder, "images", f"{vid:08d}.jpg")).convert("RGB"))
-        groups.setdefault(imgs[vid].shape[:2], []).append(vid)
-    images = [torch.from_numpy(np.stack([imgs[i] for i in ids])).to(dev) for ids in groups.values()]
-    cam_t = [torch.from_numpy(np.stack([cams[i] for i in ids])) for ids in groups.values()]
+    groups = scan.groups(vids, scan.image_size).values()              # views by image size, each in pair.txt order
+    images = [torch.from_numpy(np.stack([scan.image(i) for i in ids])).to(dev) for ids in groups]
+    cam_t = [torch.from_numpy(np.stack([scan.cam(i) for i in ids])) for ids in groups]
     out, info = texture_mesh(mesh, images, cam_t, scale=scale, max_cell=max_cell, max_size=max_size, min_px=min_px, chunk=chunk)
     if info["H"] == 0:
         raise ValueError(f"texture_scan: {scan_out_folder}: a mesh of {info['faces']} faces and {info['views']} views: nothing to texture")
@@ -323,8 +310,7 @@ def main(argv=None) -> Dict[str, Dict[str, object]]:
     add_texture_args(ap)
     args = ap.parse_args(argv)
     kw = texture_kwargs(ap, args)
-    with open(args.testlist) as f:
-        scans = [ln.strip() for ln in f if ln.strip()]
+    scans = read_testlist(args.testlist)
     out = {}
     for scan in scans:
         ply = (args.mesh or os.path.join(args.outdir, "{scan}_mesh.ply")).format(scan=scan)

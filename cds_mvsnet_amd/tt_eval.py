@@ -406,13 +406,13 @@ def write_log_trajectory(path: str, poses) -> None:
 
 def camera_poses_from_cams(folder: str) -> np.ndarray:
     """Camera-to-world poses float64 [M,4,4] of an MVSNet ``cams`` folder: ``%08d_cam.txt`` in ascending id, the
-    world-to-camera extrinsic of :func:`mvs_io.read_cam_file` inverted in float64."""
+    world-to-camera extrinsic of :func:`mvs_io.read_saved_cam` inverted in float64."""
     if not os.path.isdir(folder):
         raise FileNotFoundError(f"{folder} not found")
     names = sorted(n for n in os.listdir(folder) if re.fullmatch(r"\d{8}_cam\.txt", n))
     if not names:
         raise FileNotFoundError(f"{folder}: no %08d_cam.txt files")
-    return np.stack([np.linalg.inv(mvs_io.read_cam_file(os.path.join(folder, n))[1].astype(np.float64)) for n in names])
+    return np.stack([np.linalg.inv(mvs_io.read_saved_cam(os.path.join(folder, n))[0].astype(np.float64)) for n in names])
 
 
 def _correspondences(t: Tensor, name: str) -> Tensor:
@@ -489,8 +489,7 @@ def trajectory_alignment(est_poses, ref_poses, trans, threshold: float = 0.2, k:
 # ---------------------------------------------------------------------------------------------------------------------
 def scene_names(testlist: Optional[str], scenes: Optional[str]) -> List[str]:
     if testlist:
-        with open(testlist) as f:
-            return [ln.strip() for ln in f if ln.strip()]
+        return mvs_io.read_testlist(testlist)
     return [s.strip() for s in scenes.split(",") if s.strip()]
 
 

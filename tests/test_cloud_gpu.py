@@ -419,6 +419,43 @@ def test_filter_depth_harness(tmp_path, method):
     assert open(out / "scan1.ply", "rb").read() == open(tmp_path / "m2.ply", "rb").read()
 
 
+@pytest.mark.parametrize("method", ["normal", "dynamic"])
+def test_filter_depth_is_the_views_in_pair_order(tmp_path, method):
+    """The plain cloud, byte for byte: per reference view in pair.txt order the kept points of fuse_view / fuse_view_dynamic,
+    row-major, with the colours of the uint8 image; and the call that only collects counts what the call that writes counts."""
+    from PIL import Image
+    sc, scan, pairs = _write_outputs(tmp_path)
+    n = SCENES["s4x48x64"][0]
+    pts, col, rates = [], [], []
+    for i in range(n):
+        others = [j for j in range(n) if j != i]
+        cams = torch.stack([torch.from_numpy(fusion.read_fusion_cam(str(scan / "cams" / f"{j:08d}_cam.txt"))) for j in [i] + others])
+        args = (sc["depths"][i].cuda(), sc["confs"][i].cuda(), cams[0], sc["depths"][others].cuda(), sc["confs"][others].cuda(),
+                cams[1:])
+        out = fusion.fuse_view_dynamic(*args, conf=CONF) if method == "dynamic" else fusion.fuse_view(*args, conf=CONF, thres_view=2)
+        keep = (out["mask"] > 0.5).cpu().numpy()
+        img = np.asarray(Image.open(str(scan / "images" / f"{i:08d}.jpg")).convert("RGB"))
+        assert img.dtype == np.uint8 and img.shape == keep.shape + (3,)
+        pts.append(out["points"].cpu().numpy()[:, keep].T)
+        col.append(img[keep])
+        rates.append(keep.sum() / keep.size)
+    want = str(tmp_path / "assembled.ply")
+    fusion.write_ply(want, np.concatenate(pts), np.concatenate(col))
+    kw = dict(conf=CONF, method=method, thres_view=2)
+    plain = str(tmp_path / "plain.ply")
+    info = fusion.filter_depth(str(pairs), str(scan), plain, **kw)
+    print(f"{method}: {info['points']} points, mean_final_mask {info['mean_final_mask']!r}, per view {[len(p) for p in pts]}")
+    assert info["points"] == sum(len(p) for p in pts) > 0 and all(len(p) > 0 for p in pts)
+    assert open(plain, "rb").read() == open(want, "rb").read()
+    assert info["mean_final_mask"] == float(np.mean(np.array(rates, np.float64)))
+    views = []
+    counted = fusion.filter_depth(str(pairs), str(scan), None, collect=views, **kw)
+    assert counted == info
+    assert len(views) == n and all(v["image"].dtype == torch.uint8 for v in views)
+    assert np.array_equal(torch.cat([v["points"] for v in views]).cpu().numpy(), np.concatenate(pts))
+    assert np.array_equal(torch.cat([v["image"][v["mask"]] for v in views]).cpu().numpy(), np.concatenate(col))
+
+
 def test_infer_fuse_normals_merge(tmp_path, capsys):
     """infer --fuse --normals --merge_voxel end to end on the tiny synthetic scan of test_infer_fuse_dynamic (an untrained
     network: loose consistency settings, a wide jump)."""

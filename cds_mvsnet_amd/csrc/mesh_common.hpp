@@ -1,6 +1,6 @@
-// What the mesh kernels share (mesh_clean.hip, mesh_simplify.hip, mesh_smooth.hip, mesh_sample.hip, raster.hip, mesh_texture.hip;
-// DESIGN §1.10-1.15, §1.17): the launch shape, the size and finiteness tests, the face loader, the rasteriser's rule 1, and the one
-// compaction behind cds_mesh_cc_gather and cds_mesh_simplify_gather.
+// What the mesh kernels share (mesh_clean.hip, mesh_simplify.hip, mesh_smooth.hip, mesh_sample.hip, raster.hip, mesh_texture.hip,
+// photo.hip): the launch shape, the size and finiteness tests, the face loader, the rasteriser's
+// rules 1, 4 and 6 for one point, and the one compaction behind cds_mesh_cc_gather and cds_mesh_simplify_gather.
 #pragma once
 #include "cds_common.hpp"
 
@@ -57,6 +57,53 @@ __device__ __forceinline__ bool snap_point(const ViewPoint& p, int& X, int& Y) {
   X = usable ? (int)sx : kUnusable;
   Y = usable ? (int)sy : kUnusable;
   return usable;
+}
+
+// Rules 4 and 6 of the rasteriser, stated once for raster.hip and photo.hip: the plane of a face in camera space, the depth of a
+// pixel's ray on it and the weights of the three corners at that point.
+struct FacePlane {
+  double n[3], d;
+};
+
+__device__ __forceinline__ void load_point(const double* __restrict__ xc, int v, double p[3]) {
+  p[0] = xc[3 * (long long)v]; p[1] = xc[3 * (long long)v + 1]; p[2] = xc[3 * (long long)v + 2];
+}
+
+__device__ __forceinline__ FacePlane face_plane(const double a[3], const double b[3], const double c[3]) {
+  const double e1[3] = {b[0] - a[0], b[1] - a[1], b[2] - a[2]}, e2[3] = {c[0] - a[0], c[1] - a[1], c[2] - a[2]};
+  FacePlane f;
+  f.n[0] = e1[1] * e2[2] - e1[2] * e2[1];
+  f.n[1] = e1[2] * e2[0] - e1[0] * e2[2];
+  f.n[2] = e1[0] * e2[1] - e1[1] * e2[0];
+  f.d = (f.n[0] * a[0] + f.n[1] * a[1]) + f.n[2] * a[2];
+  return f;
+}
+
+// Rule 4 for one pixel: the ray (rx, ry, 1) and the depth along it.  The fragment exists iff the result is finite and > 0.
+__device__ __forceinline__ double fragment_depth(const FacePlane& f, const double* __restrict__ cam, int px, int py, double& rx,
+                                                 double& ry) {
+  ry = (((double)py + 0.5) - cam[16]) / cam[15];
+  rx = ((((double)px + 0.5) - cam[14]) - cam[13] * ry) / cam[12];
+  const double den = (f.n[0] * rx + f.n[1] * ry) + f.n[2];
+  return f.d / den;
+}
+
+__device__ __forceinline__ bool fragment_exists(double zf) { return zf > 0.0 && zf <= kHuge; }
+
+// Rule 6: the weights of the corners a, b, c (camera space) at the surface point zf (rx, ry, 1).
+__device__ __forceinline__ void surface_weights(const FacePlane& f, const double a[3], const double b[3], const double c[3],
+                                                double zf, double rx, double ry, double wt[3]) {
+  const double P[3] = {zf * rx, zf * ry, zf};
+  const double pa[3] = {a[0] - P[0], a[1] - P[1], a[2] - P[2]}, pb[3] = {b[0] - P[0], b[1] - P[1], b[2] - P[2]},
+               pc[3] = {c[0] - P[0], c[1] - P[1], c[2] - P[2]};
+  const double nn = (f.n[0] * f.n[0] + f.n[1] * f.n[1]) + f.n[2] * f.n[2];
+  const double* q[4] = {pb, pc, pa, pb};                               // w_a from (b, c), w_b from (c, a), w_c from (a, b)
+  for (int k = 0; k < 3; ++k) {
+    const double* s = q[k];
+    const double* t = q[k + 1];
+    const double c0 = s[1] * t[2] - s[2] * t[1], c1 = s[2] * t[0] - s[0] * t[2], c2 = s[0] * t[1] - s[1] * t[0];
+    wt[k] = ((f.n[0] * c0 + f.n[1] * c1) + f.n[2] * c2) / nn;
+  }
 }
 
 }  // namespace cds_mesh

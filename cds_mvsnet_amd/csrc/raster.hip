@@ -18,8 +18,14 @@
 namespace {
 
 using cds_mesh::blocks_for;
+using cds_mesh::face_plane;
+using cds_mesh::FacePlane;
+using cds_mesh::fragment_depth;
+using cds_mesh::fragment_exists;
 using cds_mesh::kThreads;
 using cds_mesh::kUnusable;
+using cds_mesh::load_point;
+using cds_mesh::surface_weights;
 
 constexpr int kCam = CDS_RASTER_CAM;           // doubles per camera: R 0..8, t 9..11, fx 12, s 13, cx 14, fy 15, cy 16
 
@@ -29,11 +35,6 @@ struct FaceSetup {
   int g;                                       // sign of A
   int px0, py0, bw, bh;                        // candidate pixels: px0 .. px0 + bw - 1, py0 .. py0 + bh - 1
   long long count;                             // bw bh, 0 when the face is not drawn or no pixel centre lies in its box
-};
-
-// Rule 4: the face's plane in camera space.
-struct FacePlane {
-  double n[3], d;
 };
 
 __device__ __forceinline__ long long floor_div256(long long a) { return a >> 8; }   // arithmetic shift: floor for negatives too
@@ -77,31 +78,6 @@ __device__ __forceinline__ bool covered(const FaceSetup& s, int px, int py) {
   }
   return in;
 }
-
-__device__ __forceinline__ void load_point(const double* __restrict__ xc, int v, double p[3]) {
-  p[0] = xc[3 * (long long)v]; p[1] = xc[3 * (long long)v + 1]; p[2] = xc[3 * (long long)v + 2];
-}
-
-__device__ __forceinline__ FacePlane face_plane(const double a[3], const double b[3], const double c[3]) {
-  const double e1[3] = {b[0] - a[0], b[1] - a[1], b[2] - a[2]}, e2[3] = {c[0] - a[0], c[1] - a[1], c[2] - a[2]};
-  FacePlane f;
-  f.n[0] = e1[1] * e2[2] - e1[2] * e2[1];
-  f.n[1] = e1[2] * e2[0] - e1[0] * e2[2];
-  f.n[2] = e1[0] * e2[1] - e1[1] * e2[0];
-  f.d = (f.n[0] * a[0] + f.n[1] * a[1]) + f.n[2] * a[2];
-  return f;
-}
-
-// Rule 4 for one pixel: the ray (rx, ry, 1) and the depth along it.  The fragment exists iff the result is finite and > 0.
-__device__ __forceinline__ double fragment_depth(const FacePlane& f, const double* __restrict__ cam, int px, int py, double& rx,
-                                                 double& ry) {
-  ry = (((double)py + 0.5) - cam[16]) / cam[15];
-  rx = ((((double)px + 0.5) - cam[14]) - cam[13] * ry) / cam[12];
-  const double den = (f.n[0] * rx + f.n[1] * ry) + f.n[2];
-  return f.d / den;
-}
-
-__device__ __forceinline__ bool fragment_exists(double zf) { return zf > 0.0 && zf <= 1.7976931348623157e308; }
 
 // Rules 3-5 for candidate i of the face.
 __device__ __forceinline__ void draw_candidate(const FaceSetup& s, const FacePlane& f, const double* __restrict__ cam, long long i,
@@ -215,18 +191,8 @@ __global__ __launch_bounds__(kThreads) void raster_resolve_kernel(const unsigned
     if (colors && image) {
       double rx, ry;
       const double zf = fragment_depth(f, cams + (long long)view * kCam, (int)(p % w), (int)(p / w), rx, ry);
-      const double P[3] = {zf * rx, zf * ry, zf};
-      const double pa[3] = {a[0] - P[0], a[1] - P[1], a[2] - P[2]}, pb[3] = {b[0] - P[0], b[1] - P[1], b[2] - P[2]},
-                   pc[3] = {c[0] - P[0], c[1] - P[1], c[2] - P[2]};
-      const double nn = (f.n[0] * f.n[0] + f.n[1] * f.n[1]) + f.n[2] * f.n[2];
-      const double* q[4] = {pb, pc, pa, pb};                           // w_a from (b, c), w_b from (c, a), w_c from (a, b)
       double wt[3];
-      for (int k = 0; k < 3; ++k) {
-        const double* s = q[k];
-        const double* t = q[k + 1];
-        const double c0 = s[1] * t[2] - s[2] * t[1], c1 = s[2] * t[0] - s[0] * t[2], c2 = s[0] * t[1] - s[1] * t[0];
-        wt[k] = ((f.n[0] * c0 + f.n[1] * c1) + f.n[2] * c2) / nn;
-      }
+      surface_weights(f, a, b, c, zf, rx, ry, wt);
       for (int ch = 0; ch < 3; ++ch) {
         const double ca = colors[3 * (long long)idx[0] + ch], cb = colors[3 * (long long)idx[1] + ch],
                      cc = colors[3 * (long long)idx[2] + ch];

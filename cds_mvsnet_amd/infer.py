@@ -23,7 +23,9 @@ of that mesh as a cloud; `--mesh_weight angle|conf|angle_conf
 the pixels and interpolate the depth in the integration.  With `--mesh_voxel`, `--render_mesh` (`--back`, `--max_rel_diff R`, `--save_image`) renders
 that mesh into every view, `<out>/<scan>/depth_mesh/%08d.pfm`, and `--export_blended DIR` writes the tree `fit --dataset blended`
 trains from (render.py); `--texture` (`--texture_scale S`, `--texture_max_cell C`, `--texture_max_size N`,
-`--texture_min_px P`) textures it from the saved images, `<out>/<scan>_textured.{obj,mtl,png}` (texture.py).
+`--texture_min_px P`) textures it from the saved images, `<out>/<scan>_textured.{obj,mtl,png}` (texture.py, DESIGN.md §1.17);
+`--photo_eval` (`--photo_holdout N`) scores it against the saved images, PSNR and SSIM of its textured render in the views kept
+out of the texture (photo_eval.py).
 `--save_stages` also writes the three stages' own depth maps, `<out>/<scan>/depth_stage{1,2,3}/%08d.pfm`, at their resolutions
 (what evaluations/precision.py scores stage by stage; `python -m cds_mvsnet_amd.depth_eval --folders ...`).
 
@@ -259,6 +261,11 @@ def run(args) -> float:
                 from .texture import texture_scan
                 texture_scan(os.path.join(args.outdir, scan), info["mesh"], os.path.join(args.testpath, scan),
                              os.path.join(args.outdir, f"{scan}_textured"), device=kw.get("device", "cuda"), **args.texture_kw)
+            if args.photo_eval:
+                # the mesh just written, from the device tensors, scored against the saved images of the scan
+                from .photo_eval import score_scan
+                score_scan(os.path.join(args.outdir, scan), info["mesh"], os.path.join(args.testpath, scan),
+                           holdout=args.photo_holdout or 0, device=kw.get("device", "cuda"), **args.texture_kw)
             return info["cloud"]
 
         if world > 1:  # every rank's depth maps must be on disk before any scan is fused
@@ -351,6 +358,12 @@ def parse_args(argv=None) -> argparse.Namespace:
                     help="--mesh_voxel: texture the mesh from the saved images and write <outdir>/<scan>_textured.{obj,mtl,png} "
                          "(texture.py, DESIGN §1.17)")
     add_texture_args(ap)
+    ap.add_argument("--photo_eval", action="store_true",
+                    help="--mesh_voxel: score the mesh against the saved images, PSNR and SSIM of its textured render "
+                         "(photo_eval.py, DESIGN §1.18); the --texture_* options apply")
+    ap.add_argument("--photo_holdout", type=int, default=None, metavar="N",
+                    help="--photo_eval: keep the views at the positions 0, N, 2N, ... of pair.txt out of the texture and score only "
+                         "them (N >= 2); without it every view textures and is scored, a consistency score")
     args = ap.parse_args(argv)
     args.outliers = outlier_kwargs(args, ap)
     if (args.outlier_nb > 0 or args.outlier_radius > 0) and not args.fuse:
@@ -363,7 +376,13 @@ def parse_args(argv=None) -> argparse.Namespace:
         ap.error(f"--max_rel_diff must be >= 0, got {args.max_rel_diff}")
     if args.texture and args.mesh_voxel is None:
         ap.error("--texture textures the mesh of --mesh_voxel: give --fuse --mesh_voxel SIZE as well")
-    args.texture_kw = texture_kwargs(ap, args, args.texture)
+    if args.photo_eval and args.mesh_voxel is None:
+        ap.error("--photo_eval scores the mesh of --mesh_voxel: give --fuse --mesh_voxel SIZE as well")
+    if args.photo_holdout is not None and not args.photo_eval:
+        ap.error("--photo_holdout belongs to --photo_eval")
+    if args.photo_holdout is not None and args.photo_holdout != 0 and args.photo_holdout < 2:
+        ap.error(f"--photo_holdout must be 0 or >= 2, got {args.photo_holdout}")
+    args.texture_kw = texture_kwargs(ap, args, args.texture or args.photo_eval)
     check_clean_args(ap, args, args.mesh_voxel is not None)
     args.mesh_interp_jump = check_weight_args(ap, args, args.mesh_voxel is not None)
     if args.mesh_voxel is not None:

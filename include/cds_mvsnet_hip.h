@@ -1056,6 +1056,57 @@ int cds_texture_fill(const float* vertices, const unsigned char* colors, long lo
                      int max_cell, int atlas_h, int atlas_w, unsigned char* atlas, int per_unit, void* stream);
 
 /*
+ * A mesh scored against the photographs of its scan: the textured render, and PSNR / SSIM sums of two images under a mask
+ * (csrc/photo.hip).  All arithmetic is fp64 from the uint8, fp32 or int32 entries, bracketed as written; every
+ * decision is made on integers.
+ *
+ * S. Shade.  vertices, faces and cams [n_views][CDS_RASTER_CAM] as the rasteriser takes them; uv int32 [n_faces][3][2] and atlas
+ *      uint8 [H][W][3] as rule 5 and rule 6 of the texture stage give them; face int32 [n_views][h][w] as cds_raster_resolve wrote
+ *      it.  For a pixel (px, py) with face = f in [0, n_faces) whose three indices are inside the vertices:
+ *      Surface point: Xc of the three corners by rule 1 of the rasteriser; n, d, rx, ry, zf by its rule 4; P and w_a, w_b, w_c
+ *        by its rule 6, with the same brackets: the bits the rasteriser computed.
+ *      Texel coordinate: T = (w_a U_a + w_b U_b) + w_c U_c per coordinate, U the face's three uv corners as doubles.
+ *      Cell, from the corners (so a model read back from an OBJ is shaded too): x0 = U_a.x - 1, y0 = U_a.y - 1,
+ *        c = U_b.x - U_a.x + 2, in int64.  The fall-back: when c < 4 or the cell does not lie inside the atlas
+ *        (x0 < 0, y0 < 0, x0 + c > W or y0 + c > H) the pixel is black (0, 0, 0) and nothing is read.
+ *      Clamp into the cell: tx = T.x if T.x > x0 + 0.5 else x0 + 0.5 (a NaN takes the lower bound); tx = min(tx, x0 + c - 0.5);
+ *        x = tx - 0.5, xl = floor(x), xh = min(xl + 1, x0 + c - 1), fx = x - xl, gx = 1 - fx; likewise ty, y, yl, yh, fy, gy.
+ *      Value, per channel:  value = (((gx gy) A[yl][xl] + (fx gy) A[yl][xh]) + (gx fy) A[yh][xl]) + (fx fy) A[yh][xh],
+ *        pixel = floor(value + 0.5).
+ *      Every other pixel is 0.
+ * C. Compare.  a, b uint8 [n_views][h][w][3], mask uint8 [n_views][h][w]; g: 11 doubles of the HOST, the window's weights (the
+ *      kernels evaluate no exp).  Per view:
+ *      Masked pixels: n_px = the number of pixels with mask != 0; sse[ch] = the sum of (a - b)^2 over them, exact in int64.
+ *      Windows: one for every top-left (x', y') with 0 <= x' <= w - 11 and 0 <= y' <= h - 11; it counts iff all 121 mask bytes are
+ *        non-zero (an integer sum).
+ *      Moments of a counting window, per channel: for m in {a, b, a a, b b, a b} (the products as doubles)
+ *        r[y][x'] = ((g0 m[y][x'] + g1 m[y][x' + 1]) + ...) + g10 m[y][x' + 10], ascending, left to right;
+ *        E[m] = ((g0 r[y'][x'] + g1 r[y' + 1][x']) + ...) + g10 r[y' + 10][x'].
+ *      SSIM: mua = E[a], mub = E[b], va = E[aa] - mua mua, vb = E[bb] - mub mub, vab = E[ab] - mua mub;
+ *        ssim = ((2 mua mub + C1) (2 vab + C2)) / (((mua mua + mub mub) + C1) ((va + vb) + C2)),  C1 = 6.5025, C2 = 58.5225.
+ *      Outputs: counts int64 [n_views][5] = n_px, sse[3], n_win (the counting windows); ssim_sum fp64 [n_views][3], the sum of
+ *        ssim over the counting windows: per tile of CDS_PHOTO_TILE x CDS_PHOTO_TILE windows a fixed tree over the tile's
+ *        windows, then per view a fixed walk and tree over the tiles: the same bits run to run, no atomics.
+ *        ssim_map, when not null: fp64 [n_views][3][h - 10][w - 10], NaN for a window that does not count; with h < 11 or w < 11
+ *        there is no window, n_win = 0 and the map is not touched.
+ *
+ * cds_photo_shade: rule S.  image uint8 [n_views][h][w][3]; every pixel is written.  An empty mesh or an atlas of 0 x 0 writes
+ *   zeros.  CDS_EINVAL: a count < 0 or >= 2^31; n_views outside 1..CDS_RASTER_MAX_CHUNK; h or w < 1; h w >= 2^31; an atlas that
+ *   is neither 0 x 0 nor of a size cds_texture_fill accepts; a null required pointer.
+ * cds_photo_scores: rule C.  ws: CDS_PHOTO_SCORES_WS_WORDS(n_views, h, w) int64 words of workspace, ws_words the words it has.
+ *   CDS_EINVAL: n_views, h, w as above; ws_words too small; a null pointer other than ssim_map.
+ */
+#define CDS_PHOTO_TILE 16
+#define CDS_PHOTO_RECORD 8
+#define CDS_PHOTO_SCORES_WS_WORDS(n_views, h, w) \
+  ((long long)(n_views) * (((h) + CDS_PHOTO_TILE - 1) / CDS_PHOTO_TILE) * (((w) + CDS_PHOTO_TILE - 1) / CDS_PHOTO_TILE) * CDS_PHOTO_RECORD)
+int cds_photo_shade(const float* vertices, long long n_vertices, const int* faces, long long n_faces, const int* uv,
+                    const unsigned char* atlas, int atlas_h, int atlas_w, const double* cams, int n_views, const int* face, int h,
+                    int w, unsigned char* image, void* stream);
+int cds_photo_scores(const unsigned char* a, const unsigned char* b, const unsigned char* mask, const double* g, int n_views, int h,
+                     int w, long long* ws, long long ws_words, long long* counts, double* ssim_sum, double* ssim_map, void* stream);
+
+/*
  * Norm-curvature bookkeeping of one FeatureNet level (module.py:250-251,257-258,264-265) in one launch:
  *   nc_sum[i] = (a[i]^2 + b[i]^2 + c[i]^2) / 3,  nc_abs[i] = |c[i]|   for the three DynamicConv curvature maps of the level
  */

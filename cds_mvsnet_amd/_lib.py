@@ -181,6 +181,10 @@ SIGNATURES = {
     "cds_texture_cells": [P, L, P, L, P, I, P, L, DB, I, P, P, P],
     "cds_texture_place": [P, P, L, L, I, P, P, P],
     "cds_texture_fill": [P, P, L, P, L, P, P, L, P, I, P, P, P, P, L, I, I, I, P, I, P],
+    "cds_texture_level_samples": [P, L, P, P, L, P, I, P, L, P, P, P],
+    "cds_texture_level_pairs": [P, P, P, P, L, I, P, P],
+    "cds_texture_level_step": [P, P, P, P, P, L, P, L, L, I, DB, P, P, P],
+    "cds_texture_fill_level": [P, P, L, P, L, P, P, L, P, I, P, P, P, P, L, I, I, I, P, I, P, P, L, P],
     "cds_photo_shade": [P, L, P, L, P, P, I, I, P, I, P, I, I, P, P],
     "cds_photo_scores": [P, P, P, P, I, I, I, P, L, P, P, P, P],
     "cds_grid_hash_log2_slots": [L],

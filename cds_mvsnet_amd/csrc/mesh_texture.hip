@@ -6,11 +6,17 @@
 //   cds_texture_cells   one thread per face: the view of rule 2 from the key, the cell size of rule 3
 //   cds_texture_place   one thread per face of the sorted order: rules 4 and 5, the cell's origin from its Morton start, the UV
 //   cds_texture_fill    one thread per atlas texel, or per 4 x 4 unit: rule 6
+// and the seam levelling of DESIGN §1.19 (rules L1-L6 of the header):
+//   cds_texture_level_samples  one thread per node, a (vertex, view) pair: rule L2, the image branch of rule 6 at the vertex
+//   cds_texture_level_pairs    one thread per node: the integer pair table of rule L3
+//   cds_texture_level_step     one thread per node: one iteration of rule L5, gathers only
+//   cds_texture_fill_level     cds_texture_fill with rule L6: the same load_cell / texel, instantiated with the corrections
 //
 // Decisions are made in integers or fp64 with the bracketing of the rule (the library is built with -ffp-contract=off).  The only
-// atomic is the integer add of the votes: a count does not depend on the order of its additions.  Every loop has its bound fixed
-// before it starts, and every index that comes from data (face, view, sorted position, cell origin, pixel) is tested against its
-// range before it is used: wrong tables leave texels black, they are never followed outside a buffer.
+// atomics are the integer adds of the votes and of the pair table: such a sum does not depend on the order of its additions.
+// Every loop has its bound fixed before it starts, and every index that comes from data (face, view, sorted position, cell
+// origin, pixel, node, span, corner, table slot) is tested against its range before it is used: wrong tables leave texels black
+// or unlevelled, they are never followed outside a buffer.
 #include "mesh_common.hpp"
 
 namespace {
@@ -173,6 +179,9 @@ struct FillArgs {
   long long total;
   int max_cell, log2_w, height;
   unsigned char* atlas;
+  const int* corner_node;                                                // rule L6 (the levelled fill only): [n_faces][3]
+  const double* g;                                                       // [n_nodes][3]
+  long long n_nodes;
 };
 
 // What the texels of one cell share.
@@ -182,6 +191,8 @@ struct CellFace {
   const unsigned char* img;
   double P[3][3];                                                        // the corners A, B, C
   int idx[3];
+  bool level;                                                            // rule L6: the three corner nodes are inside [0, N)
+  double G[3][3];                                                        // their corrections
 };
 
 // The last sorted position whose start is <= m (mesh_sample.hip's search); starts[0] == 0 <= m is the caller's.
@@ -193,7 +204,46 @@ __device__ __forceinline__ long long owner(const long long* __restrict__ starts,
   return lo;
 }
 
-// The cell that holds unit (ux, uy); false where the unit belongs to none.
+// The image of view v; false for an entry that does not lie inside the bytes, which is not read.
+__device__ __forceinline__ bool view_image(const long long* __restrict__ views, const unsigned char* __restrict__ images,
+                                           long long image_bytes, long long v, int& h_out, int& w_out,
+                                           const unsigned char*& img) {
+  const long long off = views[3 * v], h = views[3 * v + 1], w = views[3 * v + 2];
+  if (!(h >= 1 && w >= 1 && h * w <= 0x7fffffffLL && off >= 0 && off <= image_bytes - 3 * h * w)) return false;
+  h_out = (int)h; w_out = (int)w; img = images + off;
+  return true;
+}
+
+// The image branch of rule 6 for the world point P in one view: the unrounded values; false unless z > 0 and u, v are finite.
+__device__ __forceinline__ bool image_value(const double* __restrict__ cam, int h, int w, const unsigned char* __restrict__ img,
+                                            double P0, double P1, double P2, double val[3]) {
+  const cds_mesh::ViewPoint p = cds_mesh::view_point(cam, P0, P1, P2);
+  if (!(p.z > 0.0 && cds_mesh::is_finite(p.u) && cds_mesh::is_finite(p.v))) return false;
+  const double wmax = (double)w - 0.5, hmax = (double)h - 0.5;
+  const double uc = p.u < 0.5 ? 0.5 : (p.u > wmax ? wmax : p.u), vc = p.v < 0.5 ? 0.5 : (p.v > hmax ? hmax : p.v);
+  const double x = uc - 0.5, y = vc - 0.5;
+  int x0 = (int)floor(x), y0 = (int)floor(y);
+  x0 = x0 < 0 ? 0 : (x0 > w - 1 ? w - 1 : x0);                           // already there; the image is never read outside
+  y0 = y0 < 0 ? 0 : (y0 > h - 1 ? h - 1 : y0);
+  const int x1 = x0 + 1 < w ? x0 + 1 : x0, y1 = y0 + 1 < h ? y0 + 1 : y0;
+  const double fx = x - (double)x0, fy = y - (double)y0, gx = 1.0 - fx, gy = 1.0 - fy;
+  const double w00 = gx * gy, w10 = fx * gy, w01 = gx * fy, w11 = fx * fy;
+  const unsigned char *p00 = img + 3 * ((size_t)y0 * w + x0), *p10 = img + 3 * ((size_t)y0 * w + x1),
+                      *p01 = img + 3 * ((size_t)y1 * w + x0), *p11 = img + 3 * ((size_t)y1 * w + x1);
+#pragma unroll
+  for (int ch = 0; ch < 3; ++ch)
+    val[ch] = ((w00 * (double)p00[ch] + w10 * (double)p10[ch]) + w01 * (double)p01[ch]) + w11 * (double)p11[ch];
+  return true;
+}
+
+// clamp(value, 0, 255) with clamp(NaN) = 0, then the nearest level.
+__device__ __forceinline__ unsigned char clamped_level(double val) {
+  const double cl = val > 0.0 ? (val < 255.0 ? val : 255.0) : 0.0;
+  return (unsigned char)(int)floor(cl + 0.5);
+}
+
+// The cell that holds unit (ux, uy); false where the unit belongs to none.  kLevel: the corrections of the face's corner nodes too.
+template <bool kLevel>
 __device__ __forceinline__ bool load_cell(const FillArgs& a, int ux, int uy, CellFace& cf) {
   const long long m = (long long)(spread_bits((unsigned)ux) | (spread_bits((unsigned)uy) << 1));
   if (m >= a.total || a.starts[0] > m) return false;
@@ -207,11 +257,23 @@ __device__ __forceinline__ bool load_cell(const FillArgs& a, int ux, int uy, Cel
   if (!cds_mesh::load_face(a.faces, f, a.n_vertices, cf.idx)) return false;
   const int v = a.view[f];
   cf.view = -1; cf.h = 1; cf.w = 1; cf.img = a.images;
-  if (v >= 0 && v < a.n_views) {
-    const long long off = a.views[3 * (long long)v], h = a.views[3 * (long long)v + 1], w = a.views[3 * (long long)v + 2];
-    // an image that does not lie inside the buffer is not read: the face keeps its vertex colours
-    if (h >= 1 && w >= 1 && h * w <= 0x7fffffffLL && off >= 0 && off <= a.image_bytes - 3 * h * w) {
-      cf.view = v; cf.h = (int)h; cf.w = (int)w; cf.img = a.images + off;
+  // an image that does not lie inside the buffer is not read: the face keeps its vertex colours
+  if (v >= 0 && v < a.n_views && view_image(a.views, a.images, a.image_bytes, v, cf.h, cf.w, cf.img)) cf.view = v;
+  cf.level = false;
+  if (kLevel && cf.view >= 0) {
+    long long node[3];
+    bool inside = true;
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+      node[q] = a.corner_node[3 * f + q];
+      inside = inside && node[q] >= 0 && node[q] < a.n_nodes;
+    }
+    if (inside) {                                                        // a node outside [0, N) is never followed
+      cf.level = true;
+#pragma unroll
+      for (int q = 0; q < 3; ++q)
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) cf.G[q][ch] = a.g[3 * node[q] + ch];
     }
   }
 #pragma unroll
@@ -221,33 +283,24 @@ __device__ __forceinline__ bool load_cell(const FillArgs& a, int ux, int uy, Cel
   return true;
 }
 
-// Rule 6 for texel (i, j) of the cell.
+// Rule 6 for texel (i, j) of the cell; with kLevel, rule L6 on its image branch.
+template <bool kLevel>
 __device__ __forceinline__ void texel(const FillArgs& a, const CellFace& cf, int i, int j, unsigned char rgb[3]) {
   const double den = (double)(cf.c - 2);
   const double wb = (((double)i + 0.5) - 1.0) / den, wc = (((double)j + 0.5) - 1.0) / den, wa = (1.0 - wb) - wc;
   if (cf.view >= 0) {
-    double P[3];
+    double P[3], val[3];
 #pragma unroll
     for (int d = 0; d < 3; ++d) P[d] = (wa * cf.P[0][d] + wb * cf.P[1][d]) + wc * cf.P[2][d];
-    const cds_mesh::ViewPoint p = cds_mesh::view_point(a.cams + (long long)cf.view * kCam, P[0], P[1], P[2]);
-    if (p.z > 0.0 && cds_mesh::is_finite(p.u) && cds_mesh::is_finite(p.v)) {
-      const int w = cf.w, h = cf.h;
-      const double wmax = (double)w - 0.5, hmax = (double)h - 0.5;
-      const double uc = p.u < 0.5 ? 0.5 : (p.u > wmax ? wmax : p.u), vc = p.v < 0.5 ? 0.5 : (p.v > hmax ? hmax : p.v);
-      const double x = uc - 0.5, y = vc - 0.5;
-      int x0 = (int)floor(x), y0 = (int)floor(y);
-      x0 = x0 < 0 ? 0 : (x0 > w - 1 ? w - 1 : x0);                       // already there; the image is never read outside
-      y0 = y0 < 0 ? 0 : (y0 > h - 1 ? h - 1 : y0);
-      const int x1 = x0 + 1 < w ? x0 + 1 : x0, y1 = y0 + 1 < h ? y0 + 1 : y0;
-      const double fx = x - (double)x0, fy = y - (double)y0, gx = 1.0 - fx, gy = 1.0 - fy;
-      const double w00 = gx * gy, w10 = fx * gy, w01 = gx * fy, w11 = fx * fy;
-      const unsigned char* img = cf.img;
-      const unsigned char *p00 = img + 3 * ((size_t)y0 * w + x0), *p10 = img + 3 * ((size_t)y0 * w + x1),
-                          *p01 = img + 3 * ((size_t)y1 * w + x0), *p11 = img + 3 * ((size_t)y1 * w + x1);
+    if (image_value(a.cams + (long long)cf.view * kCam, cf.h, cf.w, cf.img, P[0], P[1], P[2], val)) {
 #pragma unroll
       for (int ch = 0; ch < 3; ++ch) {
-        const double val = ((w00 * (double)p00[ch] + w10 * (double)p10[ch]) + w01 * (double)p01[ch]) + w11 * (double)p11[ch];
-        rgb[ch] = (unsigned char)(int)floor(val + 0.5);
+        if (kLevel && cf.level) {
+          const double corr = (wa * cf.G[0][ch] + wb * cf.G[1][ch]) + wc * cf.G[2][ch];
+          rgb[ch] = clamped_level(val[ch] + corr);
+        } else {
+          rgb[ch] = (unsigned char)(int)floor(val[ch] + 0.5);
+        }
       }
       return;
     }
@@ -256,38 +309,38 @@ __device__ __forceinline__ void texel(const FillArgs& a, const CellFace& cf, int
   for (int ch = 0; ch < 3; ++ch) {
     const double ca = a.colors[3 * (long long)cf.idx[0] + ch], cb = a.colors[3 * (long long)cf.idx[1] + ch],
                  cc = a.colors[3 * (long long)cf.idx[2] + ch];
-    const double val = (wa * ca + wb * cb) + wc * cc;
-    const double cl = val > 0.0 ? (val < 255.0 ? val : 255.0) : 0.0;     // NaN -> 0
-    rgb[ch] = (unsigned char)(int)floor(cl + 0.5);
+    rgb[ch] = clamped_level((wa * ca + wb * cb) + wc * cc);              // NaN -> 0
   }
 }
 
 // One thread per texel: a wave writes 192 consecutive bytes of a row.
+template <bool kLevel>
 __global__ __launch_bounds__(kThreads) void texture_fill_texel_kernel(const FillArgs a) {
   const long long t = (long long)blockIdx.x * kThreads + threadIdx.x;
   if (t >= ((long long)a.height << a.log2_w)) return;
   const int x = (int)(t & ((1ll << a.log2_w) - 1)), y = (int)(t >> a.log2_w);
   unsigned char rgb[3] = {0, 0, 0};
   CellFace cf;
-  if (load_cell(a, x >> 2, y >> 2, cf)) texel(a, cf, x - cf.x0, y - cf.y0, rgb);
+  if (load_cell<kLevel>(a, x >> 2, y >> 2, cf)) texel<kLevel>(a, cf, x - cf.x0, y - cf.y0, rgb);
   unsigned char* o = a.atlas + 3 * t;
   o[0] = rgb[0]; o[1] = rgb[1]; o[2] = rgb[2];
 }
 
 // One thread per 4 x 4 unit: one search for 16 texels; every row of the unit is 12 bytes, written as three words.
+template <bool kLevel>
 __global__ __launch_bounds__(kThreads) void texture_fill_unit_kernel(const FillArgs a) {
   const long long t = (long long)blockIdx.x * kThreads + threadIdx.x;
   const int log2_uw = a.log2_w - 2;
   if (t >= ((long long)(a.height >> 2) << log2_uw)) return;
   const int ux = (int)(t & ((1ll << log2_uw) - 1)), uy = (int)(t >> log2_uw);
   CellFace cf;
-  const bool owned = load_cell(a, ux, uy, cf);
+  const bool owned = load_cell<kLevel>(a, ux, uy, cf);
   for (int r = 0; r < 4; ++r) {
     unsigned word[3] = {0u, 0u, 0u};
     if (owned) {
       unsigned char row[12];
 #pragma unroll
-      for (int q = 0; q < 4; ++q) texel(a, cf, 4 * ux + q - cf.x0, 4 * uy + r - cf.y0, row + 3 * q);
+      for (int q = 0; q < 4; ++q) texel<kLevel>(a, cf, 4 * ux + q - cf.x0, 4 * uy + r - cf.y0, row + 3 * q);
 #pragma unroll
       for (int q = 0; q < 3; ++q)
         word[q] = (unsigned)row[4 * q] | ((unsigned)row[4 * q + 1] << 8) | ((unsigned)row[4 * q + 2] << 16) |
@@ -296,6 +349,146 @@ __global__ __launch_bounds__(kThreads) void texture_fill_unit_kernel(const FillA
     unsigned* o = reinterpret_cast<unsigned*>(a.atlas + 3 * ((((long long)(4 * uy + r)) << a.log2_w) + 4 * ux));
     o[0] = word[0]; o[1] = word[1]; o[2] = word[2];
   }
+}
+
+// --------------------------------------------------------------------------------------------------------------------- level
+// Seam levelling (rules L1-L6).  A node is a (vertex, view) pair; node_key = vertex * V + view, ascending, so the
+// nodes of one vertex are consecutive: span[n] = (the first node of n's vertex, their number).
+
+// Rule L2: one thread per node.  A node whose key, view entry or projection does not fit is not ok and samples 0.
+__global__ __launch_bounds__(kThreads) void level_samples_kernel(const float* __restrict__ vertices, long long n_vertices,
+                                                                 const double* __restrict__ cams,
+                                                                 const unsigned char* __restrict__ images, long long image_bytes,
+                                                                 const long long* __restrict__ views, int n_views,
+                                                                 const long long* __restrict__ node_key, long long n_nodes,
+                                                                 double* __restrict__ sample, unsigned char* __restrict__ ok) {
+  const long long n = (long long)blockIdx.x * kThreads + threadIdx.x;
+  if (n >= n_nodes) return;
+  const long long key = node_key[n];
+  double val[3] = {0.0, 0.0, 0.0};
+  bool good = false;
+  if (key >= 0) {
+    const long long vertex = key / n_views, label = key % n_views;
+    int h, w;
+    const unsigned char* img;
+    if (vertex < n_vertices && view_image(views, images, image_bytes, label, h, w, img)) {
+      const float* q = vertices + 3 * vertex;
+      good = image_value(cams + label * kCam, h, w, img, (double)q[0], (double)q[1], (double)q[2], val);
+      if (!good) val[0] = val[1] = val[2] = 0.0;
+    }
+  }
+  sample[3 * n] = val[0]; sample[3 * n + 1] = val[1]; sample[3 * n + 2] = val[2];
+  ok[n] = good ? 1 : 0;
+}
+
+// The nodes of n's vertex as [first, first + count); false for a span that does not hold n or leaves the nodes.
+__device__ __forceinline__ bool load_span(const int* __restrict__ span, long long n, long long n_nodes, int n_views,
+                                          long long& first, long long& count) {
+  first = span[2 * n]; count = span[2 * n + 1];
+  return first >= 0 && count >= 1 && count <= n_views && first <= n && n < first + count && first + count <= n_nodes;
+}
+
+// Rule L3: one thread per node i, the pairs (i, j) with j after i in the vertex.  table [V][V][4]: cnt, dsum[3]; integer adds.
+// The nodes of a workgroup are neighbours in the vertex order and share a few label pairs, and the whole scan has only V V table
+// entries: the workgroup sums its pairs in a small hash table in LDS and adds every used slot to the table once.  A pair that
+// finds no slot within kPairProbes adds to the table itself.  Integer sums: the result is the same in any order.
+constexpr int kPairSlots = 512, kPairProbes = 8;
+
+__global__ __launch_bounds__(kThreads) void level_pairs_kernel(const double* __restrict__ sample, const unsigned char* __restrict__ ok,
+                                                               const long long* __restrict__ node_key, const int* __restrict__ span,
+                                                               long long n_nodes, int n_views,
+                                                               unsigned long long* __restrict__ table) {
+  __shared__ int slot_key[kPairSlots];
+  __shared__ unsigned long long slot_sum[kPairSlots][4];
+  for (int s = threadIdx.x; s < kPairSlots; s += kThreads) {
+    slot_key[s] = -1;
+    slot_sum[s][0] = 0; slot_sum[s][1] = 0; slot_sum[s][2] = 0; slot_sum[s][3] = 0;
+  }
+  __syncthreads();
+  const long long i = (long long)blockIdx.x * kThreads + threadIdx.x;
+  long long first = 0, count = 0;
+  const long long key = i < n_nodes ? node_key[i] : -1;
+  if (key >= 0 && ok[i] != 0 && load_span(span, i, n_nodes, n_views, first, count)) {
+    const long long vertex = key / n_views, a = key % n_views;
+    long long qi[3];
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) qi[ch] = (long long)floor(sample[3 * i + ch] * 256.0 + 0.5);
+    const long long end = first + count;
+    for (long long j = i + 1; j < end; ++j) {
+      const long long kj = node_key[j];
+      if (ok[j] == 0 || kj < 0 || kj / n_views != vertex) continue;
+      const long long b = kj % n_views;
+      if (b <= a) continue;                                              // keys ascend: never with the tables of rule L1
+      const int entry = (int)(a * n_views + b);                          // < V V <= 2^18
+      unsigned long long add[4] = {1ull, 0ull, 0ull, 0ull};
+#pragma unroll
+      for (int ch = 0; ch < 3; ++ch)                                     // two's complement: the int64 sum
+        add[1 + ch] = (unsigned long long)(qi[ch] - (long long)floor(sample[3 * j + ch] * 256.0 + 0.5));
+      unsigned h = ((unsigned)entry * 2654435761u) >> 23;                // 9 bits: kPairSlots
+      unsigned long long* dst = table + 4 * (long long)entry;
+      bool found = false;
+      for (int probe = 0; probe < kPairProbes; ++probe) {
+        if (!found) {
+          const int prev = atomicCAS(&slot_key[h], -1, entry);
+          if (prev == -1 || prev == entry) { dst = slot_sum[h]; found = true; }
+          else h = (h + 1) & (kPairSlots - 1);
+        }
+      }
+#pragma unroll
+      for (int q = 0; q < 4; ++q) atomicAdd(dst + q, add[q]);
+    }
+  }
+  __syncthreads();
+  for (int s = threadIdx.x; s < kPairSlots; s += kThreads) {
+    const int entry = slot_key[s];
+    if (entry < 0 || entry >= n_views * n_views) continue;               // n_views <= 512: no overflow
+#pragma unroll
+    for (int q = 0; q < 4; ++q) atomicAdd(table + 4 * (long long)entry + q, slot_sum[s][q]);
+  }
+}
+
+// Rule L5: one thread per node, gathers only; g_in is the previous iteration, g_out the next.
+__global__ __launch_bounds__(kThreads) void level_step_kernel(const double* __restrict__ sample, const unsigned char* __restrict__ ok,
+                                                              const int* __restrict__ span, const long long* __restrict__ corner_start,
+                                                              const long long* __restrict__ corner_list, long long n_list,
+                                                              const int* __restrict__ corner_node, long long n_nodes,
+                                                              long long n_faces, int n_views, double lambda,
+                                                              const double* __restrict__ g_in, double* __restrict__ g_out) {
+  const long long n = (long long)blockIdx.x * kThreads + threadIdx.x;
+  if (n >= n_nodes) return;
+  const double g[3] = {g_in[3 * n], g_in[3 * n + 1], g_in[3 * n + 2]};
+  double S[3] = {0.0, 0.0, 0.0}, T[3] = {0.0, 0.0, 0.0};
+  long long c = 0, d = 0, first, count;
+  if (ok[n] != 0 && load_span(span, n, n_nodes, n_views, first, count)) {
+    const double s[3] = {sample[3 * n], sample[3 * n + 1], sample[3 * n + 2]};
+    const long long end = first + count;
+    for (long long m = first; m < end; ++m) {
+      if (m == n || ok[m] == 0) continue;
+#pragma unroll
+      for (int ch = 0; ch < 3; ++ch) S[ch] = S[ch] + ((sample[3 * m + ch] + g_in[3 * m + ch]) - s[ch]);
+      ++c;
+    }
+  }
+  const long long n_corners = 3 * n_faces, lo = corner_start[n], hi = corner_start[n + 1];
+  if (lo >= 0 && lo <= hi && hi <= n_list) {
+    for (long long k = lo; k < hi; ++k) {
+      const long long corner = corner_list[k];
+      if (corner < 0 || corner >= n_corners) continue;
+      const long long f = corner / 3, q = corner - 3 * f;
+#pragma unroll
+      for (int step = 1; step <= 2; ++step) {
+        const long long m = corner_node[3 * f + (q + step) % 3];
+        if (m < 0 || m >= n_nodes) continue;
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) T[ch] = T[ch] + g_in[3 * m + ch];
+        ++d;
+      }
+    }
+  }
+  const double den = (double)c + lambda * (double)d;
+#pragma unroll
+  for (int ch = 0; ch < 3; ++ch)
+    g_out[3 * n + ch] = den > 0.0 ? g[ch] + CDS_TEXTURE_LEVEL_OMEGA * ((S[ch] + lambda * T[ch]) / den - g[ch]) : g[ch];
 }
 
 bool map_ok(int n_views, int h, int w) {
@@ -359,10 +552,12 @@ extern "C" int cds_texture_place(const long long* order, const long long* starts
   return cds_launch_status();
 }
 
-extern "C" int cds_texture_fill(const float* vertices, const unsigned char* colors, long long n_vertices, const int* faces,
-                                long long n_faces, const double* cams, const unsigned char* images, long long image_bytes,
-                                const long long* views, int n_views, const int* view, const int* cell, const long long* order, const long long* starts, long long total,
-                                int max_cell, int atlas_h, int atlas_w, unsigned char* atlas, int per_unit, void* stream) {
+// The argument checks and the launch of both fills.  level: rule L6 from corner_node, g and n_nodes.
+static int fill_dispatch(const float* vertices, const unsigned char* colors, long long n_vertices, const int* faces, long long n_faces,
+                         const double* cams, const unsigned char* images, long long image_bytes, const long long* views, int n_views,
+                         const int* view, const int* cell, const long long* order, const long long* starts, long long total,
+                         int max_cell, int atlas_h, int atlas_w, unsigned char* atlas, int per_unit, bool level,
+                         const int* corner_node, const double* g, long long n_nodes, void* stream) {
   int log2_w = -1;
   for (int s = 2; (1 << s) <= CDS_TEXTURE_MAX_SIZE; ++s)
     if ((1 << s) == atlas_w) log2_w = s;
@@ -372,14 +567,70 @@ extern "C" int cds_texture_fill(const float* vertices, const unsigned char* colo
     return CDS_EINVAL;
   if (!atlas || ((size_t)atlas & 3) != 0) return CDS_EINVAL;
   if (n_faces > 0 && (!vertices || !colors || !faces || !cams || !images || !views || !view || !cell || !order || !starts)) return CDS_EINVAL;
+  if (level && (!cds_mesh::sizes_ok(n_nodes, 0) || (n_faces > 0 && !corner_node) || (n_nodes > 0 && !g))) return CDS_EINVAL;
   FillArgs a;
   a.vertices = vertices; a.colors = colors; a.n_vertices = n_vertices; a.faces = faces; a.n_faces = n_faces; a.cams = cams;
   a.images = images; a.image_bytes = image_bytes; a.views = views; a.n_views = n_views; a.view = view; a.cell = cell; a.order = order; a.starts = starts;
   a.total = n_faces > 0 ? total : 0; a.max_cell = max_cell; a.log2_w = log2_w; a.height = atlas_h; a.atlas = atlas;
+  a.corner_node = corner_node; a.g = g; a.n_nodes = level ? n_nodes : 0;
   const long long texels = (long long)atlas_h * atlas_w;
-  if (per_unit)
-    hipLaunchKernelGGL(texture_fill_unit_kernel, dim3(blocks_for(texels / 16)), dim3(kThreads), 0, (hipStream_t)stream, a);
-  else
-    hipLaunchKernelGGL(texture_fill_texel_kernel, dim3(blocks_for(texels)), dim3(kThreads), 0, (hipStream_t)stream, a);
+  const dim3 units(blocks_for(texels / 16)), all(blocks_for(texels)), block(kThreads);
+  hipStream_t st = (hipStream_t)stream;
+  if (per_unit && level) hipLaunchKernelGGL(texture_fill_unit_kernel<true>, units, block, 0, st, a);
+  else if (per_unit)     hipLaunchKernelGGL(texture_fill_unit_kernel<false>, units, block, 0, st, a);
+  else if (level)        hipLaunchKernelGGL(texture_fill_texel_kernel<true>, all, block, 0, st, a);
+  else                   hipLaunchKernelGGL(texture_fill_texel_kernel<false>, all, block, 0, st, a);
+  return cds_launch_status();
+}
+
+extern "C" int cds_texture_fill(const float* vertices, const unsigned char* colors, long long n_vertices, const int* faces,
+                                long long n_faces, const double* cams, const unsigned char* images, long long image_bytes,
+                                const long long* views, int n_views, const int* view, const int* cell, const long long* order, const long long* starts, long long total,
+                                int max_cell, int atlas_h, int atlas_w, unsigned char* atlas, int per_unit, void* stream) {
+  return fill_dispatch(vertices, colors, n_vertices, faces, n_faces, cams, images, image_bytes, views, n_views, view, cell, order,
+                       starts, total, max_cell, atlas_h, atlas_w, atlas, per_unit, false, nullptr, nullptr, 0, stream);
+}
+
+extern "C" int cds_texture_fill_level(const float* vertices, const unsigned char* colors, long long n_vertices, const int* faces,
+                                      long long n_faces, const double* cams, const unsigned char* images, long long image_bytes,
+                                      const long long* views, int n_views, const int* view, const int* cell, const long long* order,
+                                      const long long* starts, long long total, int max_cell, int atlas_h, int atlas_w,
+                                      unsigned char* atlas, int per_unit, const int* corner_node, const double* g, long long n_nodes,
+                                      void* stream) {
+  return fill_dispatch(vertices, colors, n_vertices, faces, n_faces, cams, images, image_bytes, views, n_views, view, cell, order,
+                       starts, total, max_cell, atlas_h, atlas_w, atlas, per_unit, true, corner_node, g, n_nodes, stream);
+}
+
+extern "C" int cds_texture_level_samples(const float* vertices, long long n_vertices, const double* cams, const unsigned char* images,
+                                         long long image_bytes, const long long* views, int n_views, const long long* node_key,
+                                         long long n_nodes, double* sample, unsigned char* ok, void* stream) {
+  if (!cds_mesh::sizes_ok(n_vertices, n_nodes) || n_views < 1 || n_views > CDS_TEXTURE_LEVEL_MAX_VIEWS || image_bytes < 0)
+    return CDS_EINVAL;
+  if (n_nodes == 0) return 0;
+  if (!vertices || !cams || !images || !views || !node_key || !sample || !ok) return CDS_EINVAL;
+  hipLaunchKernelGGL(level_samples_kernel, dim3(blocks_for(n_nodes)), dim3(kThreads), 0, (hipStream_t)stream, vertices, n_vertices,
+                     cams, images, image_bytes, views, n_views, node_key, n_nodes, sample, ok);
+  return cds_launch_status();
+}
+
+extern "C" int cds_texture_level_pairs(const double* sample, const unsigned char* ok, const long long* node_key, const int* span,
+                                       long long n_nodes, int n_views, long long* table, void* stream) {
+  if (!cds_mesh::sizes_ok(n_nodes, 0) || n_views < 1 || n_views > CDS_TEXTURE_LEVEL_MAX_VIEWS) return CDS_EINVAL;
+  if (n_nodes == 0) return 0;
+  if (!sample || !ok || !node_key || !span || !table) return CDS_EINVAL;
+  hipLaunchKernelGGL(level_pairs_kernel, dim3(blocks_for(n_nodes)), dim3(kThreads), 0, (hipStream_t)stream, sample, ok, node_key,
+                     span, n_nodes, n_views, reinterpret_cast<unsigned long long*>(table));
+  return cds_launch_status();
+}
+
+extern "C" int cds_texture_level_step(const double* sample, const unsigned char* ok, const int* span, const long long* corner_start,
+                                      const long long* corner_list, long long n_list, const int* corner_node, long long n_nodes,
+                                      long long n_faces, int n_views, double lambda, const double* g_in, double* g_out, void* stream) {
+  if (!cds_mesh::sizes_ok(n_nodes, n_faces) || n_list < 0 || n_list > 3 * n_faces || n_views < 1 || n_views > CDS_TEXTURE_LEVEL_MAX_VIEWS || !cds_mesh::finite_pos(lambda))
+    return CDS_EINVAL;
+  if (n_nodes == 0) return 0;
+  if (!sample || !ok || !span || !corner_start || !corner_list || !corner_node || !g_in || !g_out || g_in == g_out) return CDS_EINVAL;
+  hipLaunchKernelGGL(level_step_kernel, dim3(blocks_for(n_nodes)), dim3(kThreads), 0, (hipStream_t)stream, sample, ok, span,
+                     corner_start, corner_list, n_list, corner_node, n_nodes, n_faces, n_views, lambda, g_in, g_out);
   return cds_launch_status();
 }

@@ -23,7 +23,8 @@ of that mesh as a cloud; `--mesh_weight angle|conf|angle_conf
 the pixels and interpolate the depth in the integration.  With `--mesh_voxel`, `--render_mesh` (`--back`, `--max_rel_diff R`, `--save_image`) renders
 that mesh into every view, `<out>/<scan>/depth_mesh/%08d.pfm`, and `--export_blended DIR` writes the tree `fit --dataset blended`
 trains from (render.py); `--texture` (`--texture_scale S`, `--texture_max_cell C`, `--texture_max_size N`,
-`--texture_min_px P`) textures it from the saved images, `<out>/<scan>_textured.{obj,mtl,png}` (texture.py, DESIGN.md §1.17);
+`--texture_min_px P`) textures it from the saved images, `<out>/<scan>_textured.{obj,mtl,png}` (texture.py), with
+`--texture_level ITER` (`--texture_level_lambda L`) after levelling the seams between faces coloured from different views (§1.19);
 `--photo_eval` (`--photo_holdout N`) scores it against the saved images, PSNR and SSIM of its textured render in the views kept
 out of the texture (photo_eval.py).
 `--save_stages` also writes the three stages' own depth maps, `<out>/<scan>/depth_stage{1,2,3}/%08d.pfm`, at their resolutions

@@ -9,7 +9,8 @@ are the kernels of ``csrc/photo.hip``.  There is no CPU path.
 
     python -m cds_mvsnet_amd.photo_eval --testpath <scenes> --outdir <out> --testlist <list> [--mesh "<out>/{scan}_mesh.ply"]
         [--holdout N] [--colors texture|vertex] [--back mask|keep] [--texture_scale S] [--texture_max_cell C]
-        [--texture_max_size N] [--texture_min_px P] [--save_renders] [--json scores.json]
+        [--texture_max_size N] [--texture_min_px P] [--texture_level ITER [--texture_level_lambda L]] [--save_renders]
+        [--json scores.json]
 
 scores ``<out>/<scan>_mesh.ply`` against ``<out>/<scan>/images/%08d.jpg`` with the cameras of ``<out>/<scan>/cams`` for the views
 of ``<testpath>/<scan>/pair.txt``, prints one line per scan and the means over the list.  ``--holdout N`` (N >= 2) keeps the views
@@ -169,7 +170,7 @@ def score_scan(scan_out_folder: str, mesh_ply, pair_folder: str, holdout: int = 
     ``mesh_ply``: a file of ``mesh.write_mesh_ply``, or the mesh dict of the mesh stage on the device.
 
     ``holdout = N >= 2``: the views at the positions k of pair.txt with k % N == 0 are the test views; the others texture the mesh
-    (``texture.texture_mesh`` with ``texture_kw``: scale, max_cell, max_size, min_px); the test views are rendered and scored.
+    (``texture.texture_mesh`` with ``texture_kw``: scale, max_cell, max_size, min_px, level, level_lambda); the test views are rendered and scored.
     ``holdout = 0``: every view textures and every view is scored, a consistency score and not a held-out one.
     ``colors="vertex"`` scores the vertex-colour render of the rasteriser instead; the mesh's vertex colours were fused from
     EVERY view, so no view is truly held out in that mode.

@@ -8,8 +8,14 @@ vertex colours.  The output is a function of the input alone.  The hot paths are
 (``cds_texture_votes``, ``cds_texture_best``, ``cds_texture_cells``, ``cds_texture_place``, ``cds_texture_fill``) behind
 ``render.render_mesh``; torch sorts the cell sizes and sums the units between two launches.  There is no CPU path.
 
+``level=ITER`` (``--texture_level ITER``) levels the seams between faces that take their colour from different views (DESIGN
+§1.19, rules L1-L6 of the header): an additive correction per (vertex, view), a per-view offset found by least squares from the
+integer pair table of ``cds_texture_level_pairs`` and ITER damped Jacobi steps of ``cds_texture_level_step``, interpolated over
+each face by ``cds_texture_fill_level``.  Without it nothing new runs.
+
     python -m cds_mvsnet_amd.texture --testpath <scenes> --outdir <out> --testlist <list> [--mesh "<out>/{scan}_mesh.ply"]
         [--texture_scale S] [--texture_max_cell C] [--texture_max_size N] [--texture_min_px P]
+        [--texture_level ITER [--texture_level_lambda L]]
 
 textures ``<out>/<scan>_mesh.ply`` from ``<out>/<scan>/images/%08d.jpg`` with the cameras of ``<out>/<scan>/cams`` for the views of
 ``<testpath>/<scan>/pair.txt`` and writes ``<out>/<scan>_textured.{obj,mtl,png}``.
@@ -34,7 +40,9 @@ Tensor = torch.Tensor
 
 MAX_CELL = 4096                # CDS_TEXTURE_MAX_CELL
 MAX_SIZE = 32768               # CDS_TEXTURE_MAX_SIZE
-DEFAULTS = dict(scale=1.0, max_cell=256, max_size=16384, min_px=1)
+DEFAULTS = dict(scale=1.0, max_cell=256, max_size=16384, min_px=1, level=0, level_lambda=0.1)
+LEVEL_MAX_VIEWS = 512          # CDS_TEXTURE_LEVEL_MAX_VIEWS: rule L3 keeps a dense V x V table
+LEVEL_RIDGE = 2.0 ** -10       # rule L3
 VOTE_RUNS = 1                  # cds_texture_votes: one add per run of equal faces (profiles/mesh_texture.md)
 FILL_PER_UNIT = 1              # cds_texture_fill: one thread per 4 x 4 unit, one search for its 16 texels (profiles/mesh_texture.md)
 
@@ -43,9 +51,21 @@ def _is_pow2(n: int) -> bool:
     return n >= 1 and n & (n - 1) == 0
 
 
-def check_texture_args(scale, max_cell, max_size, min_px, what: str = "texture_mesh") -> Tuple[float, int, int, int]:
+def check_level_args(level, level_lambda, what: str = "texture_mesh") -> Tuple[int, float]:
+    """-> (level, level_lambda); ValueError unless level is an integer >= 0 and level_lambda finite and > 0."""
+    if isinstance(level, bool) or int(level) != level or int(level) < 0 or int(level) >= 2 ** 31:
+        raise ValueError(f"{what}: level must be a number of iterations >= 0, got {level}")
+    level_lambda = float(level_lambda)
+    if not (level_lambda > 0 and level_lambda < float("inf")):
+        raise ValueError(f"{what}: level_lambda must be finite and > 0, got {level_lambda}")
+    return int(level), level_lambda
+
+
+def check_texture_args(scale, max_cell, max_size, min_px, what: str = "texture_mesh", level=0,
+                       level_lambda=0.1) -> Tuple[float, int, int, int]:
     """-> (scale, max_cell, max_size, min_px); ValueError unless scale is finite and > 0, max_cell a power of two in 4..4096,
-    max_size in 4..32768 and min_px >= 1."""
+    max_size in 4..32768 and min_px >= 1, and unless level and level_lambda pass :func:`check_level_args`."""
+    check_level_args(level, level_lambda, what)
     scale = float(scale)
     if not (scale > 0 and scale < float("inf")):
         raise ValueError(f"{what}: scale must be finite and > 0, got {scale}")
@@ -93,8 +113,98 @@ def _view_groups(images, cams, what: str):
     return groups
 
 
+# ----------------------------------------------------------------------------------------------------------------- levelling
+def level_offsets(cnt, dsum, n_label) -> np.ndarray:
+    """Rule L3 on the host: cnt int64 [V,V] and dsum int64 [V,V,3] as cds_texture_level_pairs left them (entries with a < b),
+    n_label int64 [V]: the nodes of every label -> o fp64 [V,3], the solution of the normal equations, per channel."""
+    cnt, dsum = np.asarray(cnt, np.int64), np.asarray(dsum, np.int64)
+    v = cnt.shape[0]
+    up = np.triu(cnt, 1).astype(np.float64)
+    sym = up + up.T
+    a = np.diag(sym.sum(1) + LEVEL_RIDGE * np.maximum(np.asarray(n_label, np.int64), 1).astype(np.float64)) - sym
+    o = np.zeros((v, 3), np.float64)
+    for ch in range(3):
+        d = np.triu(dsum[:, :, ch], 1).astype(np.float64) / 256.0       # cnt[a][b] D[a][b]
+        o[:, ch] = np.linalg.solve(a, d.sum(0) - d.sum(1))
+    return o
+
+
+def _seam_jump(sample: Tensor, ok: Tensor, vertex: Tensor, g: Tensor, longest: int) -> Tensor:
+    """The sum over the ok pairs of one vertex and the channels of |(s_i + g_i) - (s_j + g_j)|, on the device (reporting only)."""
+    t = sample + g
+    total = torch.zeros((), dtype=torch.float64, device=sample.device)
+    for d in range(1, longest):
+        pair = (vertex[d:] == vertex[:-d]) & ok[d:] & ok[:-d]
+        total = total + ((t[d:] - t[:-d]).abs().sum(1) * pair).sum()
+    return total
+
+
+def level_pair_table(node_key: Tensor, sample: Tensor, ok: Tensor, n_views: int):
+    """The table of rule L3 from the nodes of :func:`texture_mesh`'s "level" -> (table int64 [V,V,4] = cnt, dsum[3] on the device,
+    span int32 [N,2]: the first node of every node's vertex and the number of its nodes, the longest span as a tensor [1])."""
+    dev, n = node_key.device, int(node_key.numel())
+    table = torch.zeros((n_views, n_views, 4), dtype=torch.int64, device=dev)
+    if n == 0:
+        return table, torch.zeros((0, 2), dtype=torch.int32, device=dev), torch.zeros(1, dtype=torch.int64, device=dev)
+    _, which, count = torch.unique_consecutive(node_key // n_views, return_inverse=True, return_counts=True)
+    span = torch.stack([(torch.cumsum(count, 0) - count)[which], count[which]], 1).to(torch.int32).contiguous()
+    with torch.cuda.device(dev):
+        check(_lib.load().cds_texture_level_pairs(sample.data_ptr(), ok.data_ptr(), node_key.data_ptr(), span.data_ptr(), n, n_views,
+                                                  table.data_ptr(), torch.cuda.current_stream(dev).cuda_stream), "cds_texture_level_pairs")
+    return table, span, count.max().reshape(1)
+
+
+def level_nodes(faces: Tensor, view: Tensor, n_views: int, what: str = "texture_mesh") -> Dict[str, Tensor]:
+    """Rule L1, by torch's sort: faces int32 [NF,3] and view int32 [NF] on the device -> {"node_key" int64 [N], "corner_node" int32
+    [NF,3], "corner_list" int64: the corners 3 f + k of node 0, ascending, then those of node 1, ..., "corner_start" int64 [N+1]}."""
+    dev, nf = faces.device, int(faces.shape[0])
+    seen = (view >= 0)[:, None].expand(nf, 3).reshape(-1)
+    corners = torch.nonzero(seen).reshape(-1)                         # ascending
+    keys = (faces.to(torch.int64) * n_views + view.to(torch.int64)[:, None]).reshape(-1)[corners]
+    node_key, inverse = torch.unique(keys, sorted=True, return_inverse=True)
+    n = int(node_key.numel())
+    if n >= 2 ** 31:
+        raise ValueError(f"{what}: {n} (vertex, view) nodes, at most 2^31 - 1")
+    corner_node = torch.full((3 * nf,), -1, dtype=torch.int32, device=dev)
+    corner_node[corners] = inverse.to(torch.int32)
+    corner_start = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    corner_start[1:] = torch.cumsum(torch.bincount(inverse, minlength=n), 0)
+    return {"node_key": node_key, "corner_node": corner_node.reshape(nf, 3),
+            "corner_list": corners[torch.sort(inverse, stable=True).indices].contiguous(), "corner_start": corner_start}
+
+
+def _level(lib, stream, vert, nv, faces, nf, tab, pixels, views, v, view, level, level_lambda, what):
+    """Rules L1-L5 -> (the "level" dict of texture_mesh, pairs, the two jump sums as a device tensor [2])."""
+    dev = vert.device
+    nodes = level_nodes(faces, view, v, what)
+    node_key, corner_node, corner_list, corner_start = (nodes[k] for k in ("node_key", "corner_node", "corner_list", "corner_start"))
+    n = int(node_key.numel())
+    vertex, label = node_key // v, node_key % v
+    sample = torch.empty((n, 3), dtype=torch.float64, device=dev)
+    ok = torch.empty(n, dtype=torch.uint8, device=dev)
+    check(lib.cds_texture_level_samples(vert.data_ptr(), nv, tab.data_ptr(), pixels.data_ptr(), int(pixels.numel()), views.data_ptr(),
+                                        v, node_key.data_ptr(), n, sample.data_ptr(), ok.data_ptr(), stream), "cds_texture_level_samples")
+    table, span, longest = level_pair_table(node_key, sample, ok, v)
+    # rule L3: the one read of levelling
+    host = torch.cat([table.reshape(-1), torch.bincount(label, minlength=v), longest]).cpu().numpy()
+    pair = host[:4 * v * v].reshape(v, v, 4)
+    offsets = torch.from_numpy(level_offsets(pair[:, :, 0], pair[:, :, 1:], host[4 * v * v:4 * v * v + v])).to(dev)
+    g = offsets[label].contiguous() if n else torch.zeros((0, 3), dtype=torch.float64, device=dev)     # rule L4
+    other = torch.empty_like(g)
+    for _ in range(level):                                            # rule L5: nothing is read on the host
+        check(lib.cds_texture_level_step(sample.data_ptr(), ok.data_ptr(), span.data_ptr(), corner_start.data_ptr(),
+                                         corner_list.data_ptr(), int(corner_list.numel()), corner_node.data_ptr(), n, nf, v,
+                                         level_lambda, g.data_ptr(), other.data_ptr(), stream), "cds_texture_level_step")
+        g, other = other, g
+    okb = ok != 0
+    jumps = torch.stack([_seam_jump(sample, okb, vertex, torch.zeros_like(g), int(host[-1])),
+                         _seam_jump(sample, okb, vertex, g, int(host[-1]))])
+    out = {"node_key": node_key, "corner_node": corner_node, "sample": sample, "ok": ok, "offsets": offsets, "g": g}
+    return out, int(pair[:, :, 0].sum()), jumps
+
+
 def texture_mesh(mesh_dict: Dict[str, Tensor], images, cams, scale: float = 1.0, max_cell: int = 256, max_size: int = 16384,
-                 min_px: int = 1, chunk: int = 8):
+                 min_px: int = 1, chunk: int = 8, level: int = 0, level_lambda: float = 0.1):
     """``mesh_dict`` as the mesh stage returns it (vertices float32 [NV,3], colors uint8 [NV,3], faces int32 [NF,3], on one ROCm
     device); ``images`` uint8 [V,h,w,3] on that device; ``cams`` [V,2,4,4] on any device, as ``render.render_mesh`` takes them.
     For views of several image sizes, ``images`` and ``cams`` are two lists with one such pair per size; the views are numbered
@@ -105,7 +215,11 @@ def texture_mesh(mesh_dict: Dict[str, Tensor], images, cams, scale: float = 1.0,
     -> ({"atlas" uint8 [H,W,3], "uv" int32 [NF,3,2]: the texel coordinates of the three corners (x, y), "view" int32 [NF] (-1: no
     view sees the face), "cell" int32 [NF,3]: (x0, y0, c)} on that device; info: {"H", "W", "faces", "unseen", "units": (used, of
     the atlas), "views"}).  An empty mesh gives an empty atlas [0,0,3]; so do zero views, with view -1 and cell 0 for every face:
-    neither launches anything."""
+    neither launches anything.
+    ``level`` > 0: the seams are levelled with that many iterations of rule L5 at the smoothness weight
+    ``level_lambda``; uv, view and cell are what they are without it.  The result gains "level": {"node_key" int64 [N],
+    "corner_node" int32 [NF,3], "sample" float64 [N,3], "ok" uint8 [N], "offsets" float64 [V,3], "g" float64 [N,3]} on the device,
+    and info "seam": (the seam pairs, their mean colour jump before, and after levelling).  ValueError beyond 512 views."""
     what = "texture_mesh"
     vert, col, faces = mesh_dict["vertices"], mesh_dict["colors"], mesh_dict["faces"]
     nv, nf = check_mesh_layout(vert, col, faces, what), int(faces.shape[0])
@@ -116,16 +230,26 @@ def texture_mesh(mesh_dict: Dict[str, Tensor], images, cams, scale: float = 1.0,
     if not (1 <= chunk <= MAX_CHUNK):
         raise ValueError(f"{what}: chunk must lie in 1..{MAX_CHUNK}, got {chunk}")
     scale, max_cell, max_size, min_px = check_texture_args(scale, max_cell, max_size, min_px, what)
+    level, level_lambda = check_level_args(level, level_lambda, what)
     tab = torch.cat([camera_table(cam) for _, cam in groups]) if groups else torch.zeros((0, CAM_DOUBLES), dtype=torch.float64)
     dev = check_mesh_device(vert, col, faces, what)
     for img, _ in groups:
         if not img.is_cuda or img.device != dev:
             raise RuntimeError(f"{what}: images must be on {dev}; there is no CPU fallback")
     v = int(tab.shape[0])
+    if level and v > LEVEL_MAX_VIEWS:
+        raise ValueError(f"{what}: levelling keeps a table of views x views: at most {LEVEL_MAX_VIEWS} views, got {v}")
     out = {"atlas": torch.zeros((0, 0, 3), dtype=torch.uint8, device=dev), "uv": torch.zeros((nf, 3, 2), dtype=torch.int32, device=dev),
            "view": torch.full((nf,), -1, dtype=torch.int32, device=dev), "cell": torch.zeros((nf, 3), dtype=torch.int32, device=dev)}
     info = {"H": 0, "W": 0, "faces": nf, "unseen": nf, "units": (0, 0), "views": v}
     if nf == 0 or v == 0:
+        if level:
+            out["level"] = {"node_key": torch.zeros(0, dtype=torch.int64, device=dev),
+                            "corner_node": torch.full((nf, 3), -1, dtype=torch.int32, device=dev),
+                            "sample": torch.zeros((0, 3), dtype=torch.float64, device=dev), "ok": torch.zeros(0, dtype=torch.uint8, device=dev),
+                            "offsets": torch.zeros((v, 3), dtype=torch.float64, device=dev),
+                            "g": torch.zeros((0, 3), dtype=torch.float64, device=dev)}
+            info["seam"] = (0, 0.0, 0.0)
         return out, info
     vert, col, faces = vert.contiguous(), col.contiguous(), faces.contiguous()
     groups = [(img.contiguous(), cam) for img, cam in groups if img.shape[0] > 0]
@@ -161,24 +285,43 @@ def texture_mesh(mesh_dict: Dict[str, Tensor], images, cams, scale: float = 1.0,
         order = torch.sort(-c, stable=True).indices
         units = (c[order] >> 2) ** 2
         ends = torch.cumsum(units, 0)
-        total, unseen = (int(x) for x in torch.stack([ends[-1], (out["view"] < 0).sum()]).cpu())   # the one read
+        counts = torch.stack([ends[-1], (out["view"] < 0).sum()])
+        if level:
+            # before the read below, so that the report of the seams travels with it: levelling itself reads only its pair table
+            out["level"], pairs, jumps = _level(lib, stream, vert, nv, faces, nf, tab, pixels, views, v, out["view"], level,
+                                                level_lambda, what)
+            counts = torch.cat([counts, jumps.view(torch.int64)])
+        counts = counts.cpu()                                         # the one read
+        total, unseen = int(counts[0]), int(counts[1])
+        if level:
+            before, after = (float(x) / (3 * pairs) if pairs else 0.0 for x in counts[2:].view(torch.float64))
+            info["seam"] = (pairs, before, after)
         ah, aw = atlas_size(total, max_size, what)
         starts = ends - units
         check(lib.cds_texture_place(order.data_ptr(), starts.data_ptr(), nf, total, max_cell, out["cell"].data_ptr(),
                                     out["uv"].data_ptr(), stream), "cds_texture_place")
         out["atlas"] = torch.empty((ah, aw, 3), dtype=torch.uint8, device=dev)
-        check(lib.cds_texture_fill(vert.data_ptr(), col.data_ptr(), nv, faces.data_ptr(), nf, tab.data_ptr(), pixels.data_ptr(),
-                                   int(pixels.numel()), views.data_ptr(), v, out["view"].data_ptr(), out["cell"].data_ptr(),
-                                   order.data_ptr(), starts.data_ptr(), total, max_cell, ah, aw, out["atlas"].data_ptr(), FILL_PER_UNIT,
-                                   stream), "cds_texture_fill")
+        fill = (vert.data_ptr(), col.data_ptr(), nv, faces.data_ptr(), nf, tab.data_ptr(), pixels.data_ptr(), int(pixels.numel()),
+                views.data_ptr(), v, out["view"].data_ptr(), out["cell"].data_ptr(), order.data_ptr(), starts.data_ptr(), total,
+                max_cell, ah, aw, out["atlas"].data_ptr(), FILL_PER_UNIT)
+        if level:
+            lv = out["level"]
+            check(lib.cds_texture_fill_level(*fill, lv["corner_node"].data_ptr(), lv["g"].data_ptr(), int(lv["g"].shape[0]), stream),
+                  "cds_texture_fill_level")
+        else:
+            check(lib.cds_texture_fill(*fill, stream), "cds_texture_fill")
     info.update(H=ah, W=aw, unseen=unseen, units=(total, (ah // 4) * (aw // 4)))
     return out, info
 
 
 def format_texture(info: Dict[str, object]) -> str:
     used, room = info["units"]
-    return (f"atlas {info['W']} x {info['H']}, {100.0 * used / room if room else 0.0:.1f} % of its units used, {info['faces']} faces from "
+    line = (f"atlas {info['W']} x {info['H']}, {100.0 * used / room if room else 0.0:.1f} % of its units used, {info['faces']} faces from "
             f"{info['views']} views, {100.0 * info['unseen'] / info['faces'] if info['faces'] else 0.0:.2f} % unseen")
+    if "seam" in info:
+        pairs, before, after = info["seam"]
+        line += f", {pairs} seam pairs levelled: mean jump {before:.2f} -> {after:.2f} levels"
+    return line
 
 
 # -------------------------------------------------------------------------------------------------------------------- files
@@ -248,13 +391,14 @@ def read_textured_obj(path: str):
 
 # -------------------------------------------------------------------------------------------------------------------- scans
 def texture_scan(scan_out_folder: str, mesh_ply, pair_folder: str, prefix: str, scale: float = 1.0, max_cell: int = 256,
-                 max_size: int = 16384, min_px: int = 1, device: str = "cuda", chunk: int = 8) -> Dict[str, object]:
+                 max_size: int = 16384, min_px: int = 1, device: str = "cuda", chunk: int = 8, level: int = 0,
+                 level_lambda: float = 0.1) -> Dict[str, object]:
     """Texture a mesh from the views of ``<pair_folder>/pair.txt``, in that order: the images ``<scan_out_folder>/images/%08d.jpg``
     with the cameras of ``<scan_out_folder>/cams/%08d_cam.txt``, and write ``<prefix>.{obj,mtl,png}``.  ``mesh_ply``: a file of
     ``mesh.write_mesh_ply``, or the mesh dict of the mesh stage on the device.  The views are grouped by image size as
-    ``render.render_scan`` groups them, each group in pair.txt order, and numbered through the groups.  -> the info of
-    :func:`texture_mesh`."""
-    check_texture_args(scale, max_cell, max_size, min_px, "texture_scan")
+    ``render.render_scan`` groups them, each group in pair.txt order, and numbered through the groups.  ``level``,
+    ``level_lambda``: the seam levelling of :func:`texture_mesh`.  -> the info of :func:`texture_mesh`."""
+    check_texture_args(scale, max_cell, max_size, min_px, "texture_scan", level, level_lambda)
     dev = torch.device(device)
     mesh = load_mesh(mesh_ply, dev)
     scan = ScanFolder(scan_out_folder)
@@ -262,7 +406,8 @@ def texture_scan(scan_out_folder: str, mesh_ply, pair_folder: str, prefix: str, 
     groups = scan.groups(vids, scan.image_size).values()              # views by image size, each in pair.txt order
     images = [torch.from_numpy(np.stack([scan.image(i) for i in ids])).to(dev) for ids in groups]
     cam_t = [torch.from_numpy(np.stack([scan.cam(i) for i in ids])) for ids in groups]
-    out, info = texture_mesh(mesh, images, cam_t, scale=scale, max_cell=max_cell, max_size=max_size, min_px=min_px, chunk=chunk)
+    out, info = texture_mesh(mesh, images, cam_t, scale=scale, max_cell=max_cell, max_size=max_size, min_px=min_px, chunk=chunk,
+                             level=level, level_lambda=level_lambda)
     if info["H"] == 0:
         raise ValueError(f"texture_scan: {scan_out_folder}: a mesh of {info['faces']} faces and {info['views']} views: nothing to texture")
     write_textured_obj(prefix, mesh, out)
@@ -281,22 +426,31 @@ def add_texture_args(ap: argparse.ArgumentParser) -> None:
                     help=f"texture: the widest atlas, in texels, at most {MAX_SIZE} (default {DEFAULTS['max_size']})")
     ap.add_argument("--texture_min_px", type=int, default=None, metavar="P",
                     help=f"texture: pixels a face needs in its best view to take its colour from it (default {DEFAULTS['min_px']})")
+    ap.add_argument("--texture_level", type=int, default=None, metavar="ITER",
+                    help="texture: level the seams between faces coloured from different views: per-view offsets and ITER "
+                         f"iterations of per-vertex corrections (DESIGN §1.19; default {DEFAULTS['level']}: no levelling)")
+    ap.add_argument("--texture_level_lambda", type=float, default=None, metavar="L",
+                    help=f"--texture_level: the weight of the corrections' smoothness over a face (default {DEFAULTS['level_lambda']})")
 
 
 def texture_kwargs(ap: argparse.ArgumentParser, args, enabled: bool = True) -> Dict[str, object]:
     """The --texture_* options -> the keywords of :func:`texture_scan`.  ap.error for one given without --texture (``enabled``
-    false) and for a value outside its range."""
+    false), for a value outside its range and for --texture_level_lambda without --texture_level."""
     given = {k: getattr(args, "texture_" + k) for k in DEFAULTS}
     if not enabled:
         names = [f"--texture_{k}" for k, val in given.items() if val is not None]
         if names:
             ap.error(f"{', '.join(names)} belong to --texture")
         return {}
+    if given["level_lambda"] is not None and not given["level"]:
+        ap.error("--texture_level_lambda belongs to --texture_level ITER with ITER >= 1")
     kw = {k: DEFAULTS[k] if val is None else val for k, val in given.items()}
     try:
-        check_texture_args(kw["scale"], kw["max_cell"], kw["max_size"], kw["min_px"], "--texture")
+        check_texture_args(kw["scale"], kw["max_cell"], kw["max_size"], kw["min_px"], "--texture", kw["level"], kw["level_lambda"])
     except ValueError as e:
         ap.error(str(e))
+    if given["level"] is None:                                        # without the option the keywords are what they were
+        del kw["level"], kw["level_lambda"]
     return kw
 
 

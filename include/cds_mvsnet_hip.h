@@ -1056,6 +1056,69 @@ int cds_texture_fill(const float* vertices, const unsigned char* colors, long lo
                      int max_cell, int atlas_h, int atlas_w, unsigned char* atlas, int per_unit, void* stream);
 
 /*
+ * Seam levelling of that atlas: an additive correction per (vertex, view), found by least squares and interpolated over each
+ * face, so that faces which take their colour from different exposures meet without a step (csrc/mesh_texture.hip).
+ * Rules 1-5 above are unchanged; only the texel colours of seen faces change.  All arithmetic is fp64 from the fp32 or uint8
+ * entries, bracketed as written; every decision is made on integers.  V is the number of views, at most
+ * CDS_TEXTURE_LEVEL_MAX_VIEWS: rule L3 keeps a dense V x V table.
+ *
+ * L1. Nodes.  Every corner k of every face f with view[f] = l >= 0 and valid vertex indices has the key vertex V + l (int64).
+ *      The nodes are the distinct keys, ascending; a node's id is its rank.  corner_node int32 [n_faces][3] holds the node of
+ *      every corner, -1 for the corners of unseen faces.  A node's corners are the corner indices 3 f + k that map to it,
+ *      ascending.  The nodes of one vertex are consecutive and ordered by label.  (The caller sorts: these are tables, not a
+ *      kernel.)
+ * L2. Sample.  s_n[ch] is the unrounded value of rule 6 (the same clamps, the same brackets) at the projection of the node's
+ *      vertex, as a double, into the node's view.  ok_n iff z > 0, u and v are finite and the view's image entry lies inside
+ *      the bytes; a node that is not ok samples 0.
+ * L3. Per-view offsets.  q_n[ch] = (int64)floor(s_n[ch] 256 + 0.5).  For every pair of ok nodes i < j of one vertex, with the
+ *      labels a < b:  cnt[a][b] += 1, dsum[a][b][ch] += q_i - q_j, int64 sums, whatever the order of the additions.
+ *      The host reads the table once and solves per channel, in fp64, the normal equations of
+ *        sum cnt[a][b] ((o_a - o_b) + dsum[a][b] / (256 cnt[a][b]))^2 + RIDGE sum max(n_a, 1) o_a^2,   RIDGE = 2^-10,
+ *      n_a the number of nodes with label a:  o fp64 [V][3].
+ * L4. Start.  g_n = o[label_n].
+ * L5. One iteration, a damped Jacobi step of
+ *        sum over seam pairs ((s + g) - (s' + g'))^2 + lambda sum over faces, over the face's three edges (g - g')^2.
+ *      For node n, per channel, every read from the previous iteration's g:
+ *        S = the sum of ((s_m + g_m) - s_n) over the other ok nodes m of n's vertex, ascending in m, from 0, c their number,
+ *            when n is ok; else S = 0, c = 0;
+ *        T = the sum of g over the two other corner nodes of each corner of n, the corners ascending and the partners in the
+ *            order (k + 1) % 3, (k + 2) % 3, from 0, d their number;
+ *        den = c + lambda d;   g'_n = g_n + OMEGA (((S + lambda T) / den) - g_n),   OMEGA = CDS_TEXTURE_LEVEL_OMEGA.
+ * L6. Texel.  Where rule 6 takes its image branch for face f, with the face's three corner nodes A, B, C:
+ *        corr = (wa g_A + wb g_B) + wc g_C,   texel = floor(clamp(value + corr, 0, 255) + 0.5) with clamp(NaN) = 0.
+ *      The vertex-colour branch and unseen faces are unchanged.  A face with a corner node outside [0, N) is unlevelled: the
+ *      node is never followed.
+ *
+ * cds_texture_level_samples: rule L2.  node_key int64 [n_nodes]; images, image_bytes, views, cams as cds_texture_fill takes them.
+ *   Writes sample fp64 [n_nodes][3] and ok uint8 [n_nodes].  A key < 0 or with a vertex outside the vertices is not ok.
+ * cds_texture_level_pairs: the table of rule L3.  span int32 [n_nodes][2]: the first node of the node's vertex and the number
+ *   of its nodes.  table int64 [n_views][n_views][4] = cnt, dsum[3], zeroed by the caller, receives integer atomic adds (a
+ *   workgroup sums its pairs in LDS first and adds every entry it used once; the sums are the same).  A span
+ *   that does not hold its node, leaves the nodes or is longer than n_views is skipped, as is a partner of another vertex.
+ * cds_texture_level_step: rule L5, one thread per node, gathers only.  corner_start int64 [n_nodes + 1] and corner_list int64
+ *   [n_list]: the corners of node n are corner_list[corner_start[n] .. corner_start[n + 1]).  g_in and g_out fp64 [n_nodes][3],
+ *   two buffers.  A range outside the list, a corner outside 0 .. 3 n_faces and a partner outside [0, n_nodes) are skipped.
+ * cds_texture_fill_level: cds_texture_fill with rule L6 from corner_node int32 [n_faces][3] and g fp64 [n_nodes][3].
+ *   CDS_EINVAL: what cds_texture_fill refuses; a count < 0 or >= 2^31; n_views outside 1..CDS_TEXTURE_LEVEL_MAX_VIEWS; lambda not
+ *   finite or <= 0; n_list < 0 or > 3 n_faces; g_in == g_out; a null required pointer (zero nodes return 0 first, except in the fill).
+ */
+#define CDS_TEXTURE_LEVEL_MAX_VIEWS 512
+#define CDS_TEXTURE_LEVEL_OMEGA 0.75
+int cds_texture_level_samples(const float* vertices, long long n_vertices, const double* cams, const unsigned char* images,
+                              long long image_bytes, const long long* views, int n_views, const long long* node_key,
+                              long long n_nodes, double* sample, unsigned char* ok, void* stream);
+int cds_texture_level_pairs(const double* sample, const unsigned char* ok, const long long* node_key, const int* span,
+                            long long n_nodes, int n_views, long long* table, void* stream);
+int cds_texture_level_step(const double* sample, const unsigned char* ok, const int* span, const long long* corner_start,
+                           const long long* corner_list, long long n_list, const int* corner_node, long long n_nodes,
+                           long long n_faces, int n_views, double lambda, const double* g_in, double* g_out, void* stream);
+int cds_texture_fill_level(const float* vertices, const unsigned char* colors, long long n_vertices, const int* faces,
+                           long long n_faces, const double* cams, const unsigned char* images, long long image_bytes,
+                           const long long* views, int n_views, const int* view, const int* cell, const long long* order,
+                           const long long* starts, long long total, int max_cell, int atlas_h, int atlas_w, unsigned char* atlas,
+                           int per_unit, const int* corner_node, const double* g, long long n_nodes, void* stream);
+
+/*
  * A mesh scored against the photographs of its scan: the textured render, and PSNR / SSIM sums of two images under a mask
  * (csrc/photo.hip).  All arithmetic is fp64 from the uint8, fp32 or int32 entries, bracketed as written; every
  * decision is made on integers.

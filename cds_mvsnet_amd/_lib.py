@@ -173,6 +173,13 @@ SIGNATURES = {
     "cds_mesh_adj_finish": [L, P, P, L, P, P, P],
     "cds_mesh_smooth_step_f32": [P, P, L, P, P, P, DB, P],
     "cds_mesh_smooth_limit_f32": [P, P, L, DB, P, P, P],
+    "cds_mesh_fill_max_edges": [],
+    "cds_mesh_fill_keys": [P, L, L, P, P],
+    "cds_mesh_fill_borders": [P, L, L, P, P, P, P, P],
+    "cds_mesh_fill_init": [L, P, P, P, P, P, P, P, P, P, P],
+    "cds_mesh_fill_double": [P, L, L, P, P, P, P, P],
+    "cds_mesh_fill_walk": [P, P, L, P, P, P, P, L, I, P, P, P, P],
+    "cds_mesh_fill_emit": [P, P, L, L, P, L, I, P, P, P, P, P, L, L, P, P, P, P],
     "cds_mesh_sample_max_n": [],
     "cds_mesh_sample_count": [P, L, P, L, DB, P, P, P],
     "cds_mesh_sample_emit": [P, P, L, P, L, P, P, L, P, P, P, P],

@@ -17,7 +17,8 @@ outliers, for every fusion method.
 `--mesh_voxel SIZE` (`--mesh_trunc T`, `--mesh_min_weight N`; not for gipuma) also writes `<out>/<scan>_mesh.ply`, a triangle mesh
 from the same fusion pass (mesh.py); `--mesh_min_component N` / `--mesh_keep_largest K` drop its small connected
 components first and `--mesh_simplify CELL` (`--mesh_simplify_placement quadric|mean`) then merges the vertices
-of every cell of that side into one, after `--mesh_smooth ITER` (`--mesh_smooth_lambda L`, `--mesh_smooth_mu M`,
+of every cell of that side into one, after `--mesh_fill_holes N` has closed the holes of at most N border edges
+ and `--mesh_smooth ITER` (`--mesh_smooth_lambda L`, `--mesh_smooth_mu M`,
 `--mesh_smooth_max_move D`) has smoothed it; `--mesh_sample SPACING` also writes `<out>/<scan>_surface.ply`, the surface
 of that mesh as a cloud; `--mesh_weight angle|conf|angle_conf` and `--mesh_interp` (`--mesh_interp_jump J`) weigh
 the pixels and interpolate the depth in the integration.  With `--mesh_voxel`, `--render_mesh` (`--back`, `--max_rel_diff R`, `--save_image`) renders
@@ -248,7 +249,7 @@ def run(args) -> float:
                              simplify=args.mesh_simplify or 0.0, placement=args.mesh_simplify_placement,
                              sample=args.mesh_sample or 0.0, surface_ply=os.path.join(args.outdir, f"{scan}_surface.ply"),
                              weight=args.mesh_weight, interp=args.mesh_interp, interp_jump=args.mesh_interp_jump,
-                             **dict(zip(SMOOTH_KEYS, smooth_args(args))), **kw)
+                             **dict(zip(SMOOTH_KEYS, smooth_args(args))), fill_holes=args.mesh_fill_holes or 0, **kw)
             print(f"[{rank}] {scan}_mesh.ply: {format_mesh(info)}", flush=True)
             if args.render_mesh:
                 # the mesh just written, from the device tensors, into every view of the scan

@@ -9,7 +9,7 @@ the blocks out.  There is no CPU path.
 
     python -m cds_mvsnet_amd.mesh --testpath <scenes> --outdir <out> --testlist <list> --mesh_voxel SIZE [--mesh_trunc T]
         [--mesh_min_weight 2] [--mesh_min_component N] [--mesh_keep_largest K] [--mesh_simplify CELL]
-        [--mesh_simplify_placement quadric|mean] [--mesh_smooth ITER] [--mesh_smooth_lambda 0.5] [--mesh_smooth_mu -0.53]
+        [--mesh_simplify_placement quadric|mean] [--mesh_fill_holes N] [--mesh_smooth ITER] [--mesh_smooth_lambda 0.5] [--mesh_smooth_mu -0.53]
         [--mesh_smooth_max_move D] [--mesh_sample SPACING] [--mesh_weight one|angle|conf|angle_conf] [--mesh_interp]
         [--mesh_interp_jump 0.05] [--filter_method normal|dynamic] [--conf 0,0,0] [--thres_disp 1.0] [--thres_view 3]
         [--dyn_dist_base 0.25] [--dyn_rel_base 0.000769] [--dyn_views 2,10]
@@ -35,6 +35,11 @@ collapse or repeat are dropped.  ``--from_mesh FILE --mesh_simplify CELL`` does 
 which takes the noise of the depth maps and the staircase of the tetrahedra out of the surface without shrinking it; faces,
 colours and counts stay as they are.  ``--mesh_smooth_max_move D`` keeps every vertex within D of where it was.
 ``--from_mesh FILE --mesh_smooth ITER`` does it to a saved mesh.
+
+``--mesh_fill_holes N`` closes the holes of the mesh whose rim has at most N border edges, after the clean-up and before the
+smoothing (the kernels of ``csrc/mesh_fill.hip``): a hole of three edges gets one face, a larger one a new vertex
+at the mean of its rim and a fan of faces around it, oriented as the surface around the hole.  The rows of the input stay bit for
+bit; the fan is flat, so ``--mesh_smooth`` after it fairs the cap.  ``--from_mesh FILE --mesh_fill_holes N`` does it to a saved mesh.
 
 ``--mesh_sample SPACING`` also writes ``<out>/<scan>_surface.ply``, the surface of the mesh written as a cloud (the
 kernels of ``csrc/mesh_sample.hip``): every face is cut into n^2 congruent sub-triangles with edges of at most SPACING and the
@@ -75,6 +80,7 @@ MAX_SAMPLES = 1 << 28          # points sample_mesh makes unless told otherwise:
 MAX_SMOOTH = 1000              # iterations smooth_mesh takes
 ADJ_SMALL = 64                 # entries of a vertex's segment that cds_mesh_adj_finish sorts itself (CDS_MESH_ADJ_SMALL)
 ADJ_BOUNDARY, ADJ_ISOLATED = 1, 2   # the flag bits of cds_mesh_adj_finish
+MAX_FILL_EDGES = 4096          # border edges of the largest hole fill_holes takes (CDS_MESH_FILL_MAX_EDGES): one thread walks a loop
 PACK_BITS = 21                 # three cluster numbers of at most this many bits make one sort key of a face's identity
 
 
@@ -731,6 +737,120 @@ def smooth_mesh(mesh_dict: Dict[str, Tensor], iterations: int, lam: float = 0.5,
     return {"vertices": src, "colors": col, "faces": faces}, info
 
 
+# ------------------------------------------------------------------------------------------------------------ hole filling
+def check_fill(max_edges, what: str = "fill_holes") -> int:
+    """-> max_edges as an int; ValueError unless it is an int in 3..MAX_FILL_EDGES.  The upper end is there because one thread
+    walks a loop from end to end (rule 4 of DESIGN §1.20)."""
+    if isinstance(max_edges, bool) or not isinstance(max_edges, (int, np.integer)) or not (3 <= int(max_edges) <= MAX_FILL_EDGES):
+        raise ValueError(f"{what}: max_edges must be an int in 3..{MAX_FILL_EDGES} (one thread walks a hole's rim), got {max_edges!r}")
+    return int(max_edges)
+
+
+def _borders(faces: Tensor, nv: int, what: str):
+    """Rules 1-3 of DESIGN §1.20 for a contiguous int32 [F,3] face list on the current device, nv > 0 and F > 0 -> (next int32
+    [nv], -1 where the vertex is not regular, regular uint8 [nv], the border half-edges that leave each vertex int32 [nv], and the
+    two pairs (label, jump) int32 [2,nv] at the start of the pointer doubling, along next and along prev).  One key per half-edge,
+    one torch sort of the keys, the border kernel over the sorted keys and the kernel of rule 3."""
+    dev, nf = faces.device, int(faces.shape[0])
+    if 3 * nf >= 2 ** 31:
+        raise ValueError(f"{what}: {nf} faces, at most {(2 ** 31 - 1) // 3}")
+    lib, stream = _lib.load(), _stream(dev)
+    keys = torch.empty(3 * nf, dtype=torch.int64, device=dev)
+    check(lib.cds_mesh_fill_keys(faces.data_ptr(), nf, nv, keys.data_ptr(), stream), "cds_mesh_fill_keys")
+    keys = torch.sort(keys).values
+    leave = torch.zeros(nv, dtype=torch.int32, device=dev)
+    enter = torch.zeros(nv, dtype=torch.int32, device=dev)
+    nxt = torch.full((nv,), -1, dtype=torch.int32, device=dev)
+    prv = torch.full((nv,), -1, dtype=torch.int32, device=dev)
+    check(lib.cds_mesh_fill_borders(keys.data_ptr(), 3 * nf, nv, leave.data_ptr(), enter.data_ptr(), nxt.data_ptr(), prv.data_ptr(),
+                                    stream), "cds_mesh_fill_borders")
+    regular = torch.empty(nv, dtype=torch.uint8, device=dev)
+    pairs = [torch.empty((2, nv), dtype=torch.int32, device=dev) for _ in range(4)]
+    check(lib.cds_mesh_fill_init(nv, leave.data_ptr(), enter.data_ptr(), nxt.data_ptr(), prv.data_ptr(), regular.data_ptr(),
+                                 *(t.data_ptr() for t in pairs), stream), "cds_mesh_fill_init")
+    return nxt, regular, leave, pairs
+
+
+def mesh_borders(faces: Tensor, n_vertices: int) -> Dict[str, object]:
+    """The border loops that :func:`fill_holes` walks (DESIGN §1.20 rules 1-3): faces int32 [F,3] on a ROCm device, every index in
+    [0, n_vertices) -> {"next" int32 [V]: the end of the one border half-edge that leaves a regular vertex, -1 where the vertex is
+    not regular, "regular" bool [V]: exactly one border half-edge leaves the vertex and exactly one enters it, "border_edges":
+    the half-edges whose edge one face slot holds, an int}, on that device."""
+    nv = _check_faces(faces, n_vertices, "mesh_borders")
+    dev = faces.device
+    if nv == 0 or faces.shape[0] == 0:
+        return {"next": torch.full((nv,), -1, dtype=torch.int32, device=dev), "regular": torch.zeros(nv, dtype=torch.bool, device=dev),
+                "border_edges": 0}
+    with torch.cuda.device(dev):
+        nxt, regular, leave, _ = _borders(faces.contiguous(), nv, "mesh_borders")
+        return {"next": nxt, "regular": regular != 0, "border_edges": int(leave.sum())}
+
+
+def fill_holes(mesh_dict: Dict[str, Tensor], max_edges: int):
+    """Close the small holes of a mesh with centroid fans: ``mesh_dict`` as :meth:`TsdfVolume.extract` returns it
+    (vertices float32 [V,3], colors uint8 [V,3], faces int32 [F,3], on one ROCm device).  A border edge is one that a single face
+    slot holds; a hole is a cycle of border edges through vertices that each have one border edge coming and one going.  A hole of
+    3 .. ``max_edges`` edges is filled: one of 3 with one face, a larger one with a new vertex at the mean of its rim (position
+    summed in fp64 in loop order, colour rounded in integers) and one face per border edge, each running its edge backwards and
+    so oriented as the surface around it.  Larger loops (the outer rim of an open scan), holes that touch in a vertex and
+    non-manifold edges stay as they are.  The fan is flat: :func:`smooth_mesh` after it fairs the cap.  -> (mesh dict: the input's
+    rows bit for bit, then the new vertices and the new faces in ascending order of each loop's smallest vertex; info:
+    {"max_edges", "loops": filled, "largest": edges of the largest filled loop, "border_edges", "vertices", "faces": (before,
+    after)}).  A mesh in which nothing is filled comes back as the input's own tensors.  There is no CPU fallback."""
+    what = "fill_holes"
+    max_edges = check_fill(max_edges, what)
+    vert, col, faces, nv, dev = _check_mesh(mesh_dict, what)
+    nf = int(faces.shape[0])
+    same = {"vertices": vert, "colors": col, "faces": faces}
+    info = {"max_edges": max_edges, "loops": 0, "largest": 0, "border_edges": (0, 0), "vertices": (nv, nv), "faces": (nf, nf)}
+    if nv == 0 or nf == 0:
+        return same, info
+    vert, col, faces = vert.contiguous(), col.contiguous(), faces.contiguous()
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        stream = _stream(dev)
+        nxt, regular, leave, (label, jump, label_b, jump_b) = _borders(faces, nv, what)
+        n_border = int(leave.sum())                                          # the read that ends the detection
+        info["border_edges"] = (n_border, n_border)
+        if n_border == 0:
+            return same, info
+        ring = torch.nonzero(regular).reshape(-1).to(torch.int32)             # the regular vertices, ascending
+        m = int(ring.numel())
+        if m == 0:
+            return same, info
+        for _ in range((max_edges - 1).bit_length()):                        # windows of 2^rounds >= max_edges vertices
+            check(lib.cds_mesh_fill_double(ring.data_ptr(), m, nv, label.data_ptr(), jump.data_ptr(), label_b.data_ptr(),
+                                           jump_b.data_ptr(), stream), "cds_mesh_fill_double")
+            label, jump, label_b, jump_b = label_b, jump_b, label, jump
+        edges = torch.empty(m, dtype=torch.int32, device=dev)
+        centre = torch.empty((m, 3), dtype=torch.float32, device=dev)
+        centre_color = torch.empty((m, 3), dtype=torch.uint8, device=dev)
+        check(lib.cds_mesh_fill_walk(vert.data_ptr(), col.data_ptr(), nv, nxt.data_ptr(), regular.data_ptr(), label.data_ptr(),
+                                     ring.data_ptr(), m, max_edges, edges.data_ptr(), centre.data_ptr(), centre_color.data_ptr(),
+                                     stream), "cds_mesh_fill_walk")
+        fan = (edges >= 4).to(torch.int64)
+        made = torch.where(edges == 3, 1, edges).to(torch.int64)
+        vend, fend = torch.cumsum(fan, 0), torch.cumsum(made, 0)
+        loops, new_v, new_f, largest, closed = (int(x) for x in torch.stack(
+            [(edges > 0).sum(), vend[-1], fend[-1], edges.max().long(), edges.sum()]).cpu())          # the ONE read of the fill
+        info.update(loops=loops, largest=largest, border_edges=(n_border, n_border - closed), vertices=(nv, nv + new_v),
+                    faces=(nf, nf + new_f))
+        if loops == 0:
+            return same, info
+        if nv + new_v >= 2 ** 31 or nf + new_f >= 2 ** 31:
+            raise ValueError(f"{what}: {nv + new_v} vertices and {nf + new_f} faces after the fill, at most 2^31 - 1 each")
+        out = _empty_mesh(dev, nv + new_v, nf + new_f)
+        out["vertices"][:nv].copy_(vert)
+        out["colors"][:nv].copy_(col)
+        out["faces"][:nf].copy_(faces)
+        vertex_at, face_at = vend - fan, fend - made                         # the exclusive prefix sums
+        check(lib.cds_mesh_fill_emit(nxt.data_ptr(), regular.data_ptr(), nv, nf, ring.data_ptr(), m, max_edges, edges.data_ptr(),
+                                     vertex_at.data_ptr(), face_at.data_ptr(), centre.data_ptr(), centre_color.data_ptr(),
+                                     new_v, new_f, out["vertices"].data_ptr(), out["colors"].data_ptr(), out["faces"].data_ptr(),
+                                     stream), "cds_mesh_fill_emit")
+    return out, info
+
+
 # ---------------------------------------------------------------------------------------------------------------- sampling
 def check_spacing(spacing, what: str = "sample_mesh") -> float:
     """-> spacing as a float; ValueError unless it is finite and > 0."""
@@ -861,6 +981,13 @@ def _check_simplify(simplify, placement, what: str) -> float:
     return check_cell(simplify, what)
 
 
+def _check_fill(fill_holes, what: str) -> int:
+    """-> 0 for "off" (fill_holes None or 0), else max_edges through :func:`check_fill` (ValueError)."""
+    if fill_holes is None or (not isinstance(fill_holes, bool) and isinstance(fill_holes, (int, np.integer)) and int(fill_holes) == 0):
+        return 0
+    return check_fill(fill_holes, what)
+
+
 def _check_smooth(smooth, lam, mu, max_move, what: str):
     """-> None for "off" (smooth None or 0), else (iterations, lam, mu, max_move) through :func:`check_smooth` (ValueError)."""
     if smooth is None or (not isinstance(smooth, bool) and isinstance(smooth, (int, np.integer)) and int(smooth) == 0):
@@ -868,14 +995,18 @@ def _check_smooth(smooth, lam, mu, max_move, what: str):
     return check_smooth(smooth, lam, mu, max_move, what)
 
 
-def _finish(mesh, plyfilename: str, clean, smooth, simplify: float, placement: str, sample: float, surface_ply) -> Dict[str, object]:
+def _finish(mesh, plyfilename: str, clean, smooth, simplify: float, placement: str, sample: float, surface_ply,
+            fill: int = 0) -> Dict[str, object]:
     """The way of an extracted or loaded mesh into its files: :func:`clean_mesh` with ``clean`` = (min_component, keep_largest)
-    unless it is None, :func:`smooth_mesh` with ``smooth`` = (iterations, lam, mu, max_move) unless it is None,
+    unless it is None, :func:`fill_holes` with ``fill`` = max_edges when it is > 0, :func:`smooth_mesh` with ``smooth`` =
+    (iterations, lam, mu, max_move) unless it is None,
     :func:`simplify_mesh` when ``simplify`` > 0, the mesh PLY, and when ``sample`` > 0 the sampled surface at ``surface_ply``
-    -> {"vertices", "faces", "mesh": the mesh written, on the device[, "clean"][, "smooth"][, "simplify"][, "sample"]}."""
+    -> {"vertices", "faces", "mesh": the mesh written, on the device[, "clean"][, "fill"][, "smooth"][, "simplify"][, "sample"]}."""
     out = {}
     if clean is not None:
         mesh, out["clean"] = clean_mesh(mesh, *clean)
+    if fill > 0:
+        mesh, out["fill"] = fill_holes(mesh, fill)
     if smooth is not None:
         mesh, out["smooth"] = smooth_mesh(mesh, *smooth)
         out["smooth"] = dict(out["smooth"], limit=smooth[3])
@@ -892,7 +1023,7 @@ def mesh_scan(pair_folder: str, scan_folder: str, plyfilename: str, voxel: float
               keep_largest: int = 0, simplify: float = 0.0, placement: str = "quadric", sample: float = 0.0,
               surface_ply: Optional[str] = None, weight: str = "one", interp: bool = False, interp_jump: float = 0.05,
               smooth: int = 0, smooth_lambda: float = 0.5, smooth_mu: float = -0.53, smooth_max_move: float = 0.0,
-              **fusion_options) -> Dict[str, object]:
+              fill_holes: int = 0, **fusion_options) -> Dict[str, object]:
     """One scan from saved depth maps to a mesh at ``plyfilename``: the fusion pass of :func:`fusion.filter_depth` (``method``
     "normal" or "dynamic" and its ``fusion_options``), then allocation from every view's kept points, integration of the fused
     depth maps in ``pair.txt`` order and extraction.  ``cloud_ply``: also write the fused cloud there, from the same pass and byte
@@ -903,9 +1034,11 @@ def mesh_scan(pair_folder: str, scan_folder: str, plyfilename: str, voxel: float
     at ``surface_ply``; at 0 nothing of that runs.  ``weight`` / ``interp`` / ``interp_jump``: the weighted, interpolating
     integration of :func:`mesh_views`; the confidence of the conf modes is the view's last-stage confidence map.
     ``smooth``: iterations > 0 send the mesh, after the clean-up and before the simplification, through :func:`smooth_mesh` with
-    ``smooth_lambda``, ``smooth_mu`` and ``smooth_max_move``; at 0 nothing of that runs.
+    ``smooth_lambda``, ``smooth_mu`` and ``smooth_max_move``; at 0 nothing of that runs.  ``fill_holes``: N > 0 sends
+    the mesh, after the clean-up and before the smoothing, through :func:`fill_holes` with ``max_edges`` N; at 0
+    nothing of that runs.
     -> {"vertices", "faces", "blocks": counts, "cloud": filter_depth's result, "mesh": the mesh dict written, still on the device
-    (render.render_scan takes it)[, "clean": clean_mesh's info][, "smooth": smooth_mesh's info][, "simplify": simplify_mesh's info][, "sample": sample_mesh's
+    (render.render_scan takes it)[, "clean": clean_mesh's info][, "fill": fill_holes' info][, "smooth": smooth_mesh's info][, "simplify": simplify_mesh's info][, "sample": sample_mesh's
     info and the spacing]}."""
     from .fusion import filter_depth
     if method == "gipuma":
@@ -918,31 +1051,35 @@ def mesh_scan(pair_folder: str, scan_folder: str, plyfilename: str, voxel: float
     simplify = _check_simplify(simplify, placement, "mesh_scan")
     sample = _check_sample(sample, surface_ply, "mesh_scan")
     smooth = _check_smooth(smooth, smooth_lambda, smooth_mu, smooth_max_move, "mesh_scan")
+    fill = _check_fill(fill_holes, "mesh_scan")
     interp_jump = _check_weighting(weight, interp, interp_jump, "mesh_scan")
     views: list = []
     cloud = filter_depth(pair_folder, scan_folder, cloud_ply, device=device, method=method, collect=views, **fusion_options)
     mesh, vol = mesh_views(views, voxel, trunc, min_weight, device, weight, interp, interp_jump)
     clean = (min_component, keep_largest) if int(min_component) > 0 or int(keep_largest) > 0 else None
-    return dict(_finish(mesh, plyfilename, clean, smooth, simplify, placement, sample, surface_ply), blocks=vol.n_blocks, cloud=cloud)
+    return dict(_finish(mesh, plyfilename, clean, smooth, simplify, placement, sample, surface_ply, fill), blocks=vol.n_blocks,
+                cloud=cloud)
 
 
 def clean_file(src_ply: str, dst_ply: str, min_component: int = 0, keep_largest: int = 0, device: str = "cuda",
                simplify: float = 0.0, placement: str = "quadric", sample: float = 0.0,
                surface_ply: Optional[str] = None, smooth: int = 0, smooth_lambda: float = 0.5, smooth_mu: float = -0.53,
-               smooth_max_move: float = 0.0) -> Dict[str, object]:
+               smooth_max_move: float = 0.0, fill_holes: int = 0) -> Dict[str, object]:
     """A saved mesh through :func:`clean_mesh`, then, with ``simplify`` > 0, through :func:`simplify_mesh`, and back into a file
     (``dst_ply`` may be ``src_ply``): what one runs while tuning the threshold or the cell, without the fusion.  With ``simplify``
     alone (both clean-up options at 0) the file goes through :func:`simplify_mesh` only, as in :func:`mesh_scan`.  ``sample`` > 0
     also writes the sampled surface of the mesh written to ``surface_ply``, as :func:`mesh_scan` does.  ``smooth`` > 0 sends it
     through :func:`smooth_mesh` before the simplification, as :func:`mesh_scan` does; with ``smooth`` alone, or with ``smooth`` and
-    ``simplify``, the clean-up is skipped as with ``simplify`` alone.
-    -> {"vertices", "faces", "mesh"[, "clean"][, "smooth"][, "simplify"][, "sample"]} as :func:`mesh_scan`."""
+    ``simplify``, the clean-up is skipped as with ``simplify`` alone.  ``fill_holes`` > 0 sends it through :func:`fill_holes` before
+    the smoothing, as :func:`mesh_scan` does, and skips the clean-up in the same way when neither clean-up option is given.
+    -> {"vertices", "faces", "mesh"[, "clean"][, "fill"][, "smooth"][, "simplify"][, "sample"]} as :func:`mesh_scan`."""
     simplify = _check_simplify(simplify, placement, "clean_file")
     sample = _check_sample(sample, surface_ply, "clean_file")
     smooth = _check_smooth(smooth, smooth_lambda, smooth_mu, smooth_max_move, "clean_file")
-    alone = simplify == 0 and smooth is None
+    fill = _check_fill(fill_holes, "clean_file")
+    alone = simplify == 0 and smooth is None and fill == 0
     clean = (min_component, keep_largest) if alone or int(min_component) > 0 or int(keep_largest) > 0 else None
-    return _finish(load_mesh(src_ply, device), dst_ply, clean, smooth, simplify, placement, sample, surface_ply)
+    return _finish(load_mesh(src_ply, device), dst_ply, clean, smooth, simplify, placement, sample, surface_ply, fill)
 
 
 def format_mesh(info: Dict[str, object]) -> str:
@@ -953,6 +1090,10 @@ def format_mesh(info: Dict[str, object]) -> str:
         c = info["clean"]
         text += (f"; removed {c['components'][0] - c['components'][1]} of {c['components'][0]} components and "
                  f"{c['faces'][0] - c['faces'][1]} of {c['faces'][0]} faces (the largest has {c['largest']})")
+    if "fill" in info:
+        h = info["fill"]
+        text += (f"; filled {h['loops']} holes of at most {h['max_edges']} edges (the largest has {h['largest']}), border edges "
+                 f"{h['border_edges'][0]} -> {h['border_edges'][1]}")
     if "smooth" in info:
         s = info["smooth"]
         text += (f"; smoothed {s['iterations']} iterations (lambda {s['lam']:g}, mu {s['mu']:g}): {s['boundary']} boundary, "
@@ -971,7 +1112,7 @@ def format_mesh(info: Dict[str, object]) -> str:
 
 # ---------------------------------------------------------------------------------------------------------------------- CLI
 def add_mesh_args(ap: argparse.ArgumentParser, required: bool = False) -> None:
-    """The options of DESIGN §1.9 and §1.11 to §1.15, shared with ``infer --fuse``."""
+    """The options of DESIGN §1.9, §1.11 to §1.15 and §1.20, shared with ``infer --fuse``."""
     ap.add_argument("--mesh_voxel", type=float, default=None, required=required, metavar="SIZE",
                     help="write <outdir>/<scan>_mesh.ply: a triangle mesh from a TSDF volume with this lattice spacing (world units)")
     ap.add_argument("--mesh_trunc", type=float, default=None, metavar="T",
@@ -988,6 +1129,9 @@ def add_mesh_args(ap: argparse.ArgumentParser, required: bool = False) -> None:
     ap.add_argument("--mesh_simplify_placement", default="quadric", choices=list(PLACEMENTS),
                     help="--mesh_simplify: a cell's vertex at the minimiser of its faces' quadric error (edges and corners "
                          "survive) or at the mean of its vertices")
+    ap.add_argument("--mesh_fill_holes", type=int, default=None, metavar="N",
+                    help=f"--mesh_voxel: close the holes of the mesh whose rim has at most N border edges (3..{MAX_FILL_EDGES}), after "
+                         "the clean-up and before the smoothing: one face for a hole of 3, else a fan around the mean of the rim")
     ap.add_argument("--mesh_smooth", type=int, default=None, metavar="ITER",
                     help="--mesh_voxel: smooth the mesh before it is simplified and written: ITER iterations (1..1000) of the "
                          "lambda|mu filter, which moves the vertices and nothing else")
@@ -1029,8 +1173,9 @@ def check_weight_args(ap: argparse.ArgumentParser, args, allowed: bool) -> float
 
 
 def check_clean_args(ap: argparse.ArgumentParser, args, allowed: bool) -> None:
-    """ap.error for a negative clean-up option, a non-positive --mesh_simplify or --mesh_sample, bad --mesh_smooth values, one of
-    --mesh_smooth's options without it, or for any of them given where no mesh is made (``allowed`` false)."""
+    """ap.error for a negative clean-up option, a non-positive --mesh_simplify or --mesh_sample, a --mesh_fill_holes outside its
+    range, bad --mesh_smooth values, one of --mesh_smooth's options without it, or for any of them given where no mesh is made
+    (``allowed`` false)."""
     if args.mesh_min_component < 0 or args.mesh_keep_largest < 0:
         ap.error(f"--mesh_min_component and --mesh_keep_largest must be >= 0, got {args.mesh_min_component} and "
                  f"{args.mesh_keep_largest}")
@@ -1046,6 +1191,14 @@ def check_clean_args(ap: argparse.ArgumentParser, args, allowed: bool) -> None:
             ap.error(str(e))
         if not allowed:
             ap.error(f"--{option} {does} the mesh of --mesh_voxel: give --mesh_voxel SIZE (or, in mesh, --from_mesh FILE) as well")
+    if args.mesh_fill_holes is not None:
+        try:
+            check_fill(args.mesh_fill_holes, "--mesh_fill_holes")
+        except ValueError as e:
+            ap.error(str(e))
+        if not allowed:
+            ap.error("--mesh_fill_holes fills the holes of the mesh of --mesh_voxel: give --mesh_voxel SIZE (or, in mesh, --from_mesh "
+                     "FILE) as well")
     given = [name for name in ("mesh_smooth", "mesh_smooth_lambda", "mesh_smooth_mu", "mesh_smooth_max_move")
              if getattr(args, name) is not None]
     if given and not allowed:
@@ -1085,7 +1238,7 @@ def main(argv=None) -> Dict[str, Dict[str, object]]:
     add_mesh_args(ap)
     ap.add_argument("--from_mesh", default=None, metavar="FILE",
                     help="instead of --mesh_voxel: clean this saved mesh ({scan} is replaced) with --mesh_min_component / "
-                         "--mesh_keep_largest, smooth it with --mesh_smooth, simplify it with --mesh_simplify, and write <outdir>/<scan>_mesh.ply, without any "
+                         "--mesh_keep_largest, fill its holes with --mesh_fill_holes, smooth it with --mesh_smooth, simplify it with --mesh_simplify, and write <outdir>/<scan>_mesh.ply, without any "
                          "fusion")
     args = ap.parse_args(argv)
     if args.mesh_voxel is None and args.from_mesh is None and args.mesh_sample is not None:
@@ -1107,7 +1260,7 @@ def main(argv=None) -> Dict[str, Dict[str, object]]:
                                    args.mesh_min_component, args.mesh_keep_largest, device=args.device,
                                    simplify=args.mesh_simplify or 0.0, placement=args.mesh_simplify_placement,
                                    sample=args.mesh_sample or 0.0, surface_ply=os.path.join(args.outdir, f"{scan}_surface.ply"),
-                                   **dict(zip(SMOOTH_KEYS, smooth_args(args))))
+                                   **dict(zip(SMOOTH_KEYS, smooth_args(args))), fill_holes=args.mesh_fill_holes or 0)
             print(f"{scan}_mesh.ply: {format_mesh(out[scan])}", flush=True)
         return out
     for scan in scans:
@@ -1118,6 +1271,7 @@ def main(argv=None) -> Dict[str, Dict[str, object]]:
                          placement=args.mesh_simplify_placement, sample=args.mesh_sample or 0.0,
                          surface_ply=os.path.join(args.outdir, f"{scan}_surface.ply"), weight=args.mesh_weight,
                          interp=args.mesh_interp, interp_jump=interp_jump, **dict(zip(SMOOTH_KEYS, smooth_args(args))),
+                         fill_holes=args.mesh_fill_holes or 0,
                          conf=_floats(args.conf, 3, "--conf"),
                          thres_disp=args.thres_disp, thres_view=args.thres_view, dist_base=args.dyn_dist_base,
                          rel_base=args.dyn_rel_base, n_views=tuple(int(v) for v in _floats(args.dyn_views, 2, "--dyn_views")))

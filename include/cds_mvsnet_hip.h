@@ -945,6 +945,70 @@ int cds_mesh_smooth_limit_f32(const float* original, float* vertices, long long 
                               unsigned char* clamped_out, void* stream);
 
 /*
+ * Filling the small holes of a triangle mesh with centroid fans (csrc/mesh_fill.hip).  The result is a function of
+ * the input mesh alone.  The input's vertex, colour and face rows stay bit for bit; rows are only added.
+ *
+ * Inputs.  vertices float32 [V][3]; colors uint8 [V][3]; faces int32 [F][3]; max_edges in 3..CDS_MESH_FILL_MAX_EDGES.
+ * 1. Valid faces.  A face is valid when its three indices are in [0, V) and pairwise distinct.  A valid face (a, b, c) holds the
+ *      directed half-edges a->b, b->c, c->a.  An invalid face holds none, is never touched and is copied through.
+ * 2. Border half-edges.  a->b is a border half-edge iff the undirected edge {a,b} is held by exactly one face slot over all valid
+ *      faces.  An edge held by three or more slots is no border, nor is one held twice in the same direction.
+ * 3. Regular vertices.  A vertex is regular iff exactly one border half-edge leaves it and exactly one enters it; next[a] = b for
+ *      the border half-edge a->b of a regular a.
+ * 4. Loops.  A loop is a cycle v0, v1 = next[v0], ..., v(n-1) with next[v(n-1)] = v0, every vertex on it regular; v0 is its
+ *      smallest vertex and its label, n its edge count.  A walk that meets a vertex that is not regular belongs to no loop (two
+ *      holes that touch in a vertex, the end of a non-manifold fin).  A loop is filled iff 3 <= n <= max_edges.  The outer rim of
+ *      an open scan is a loop too: max_edges is what leaves it alone.
+ * 5. The fill.  n == 3: the one face (v0, v2, v1), no new vertex.  n >= 4: one new vertex c and the n faces (v(k+1), v(k), c),
+ *      k = 0..n-1 with v(n) = v0: every new face runs its border edge backwards, which is the orientation of the surface around
+ *      the hole.  Position of c, per coordinate: the sum of (double)p over v0, v1, ..., v(n-1) in that order, sequential in fp64
+ *      from +0.0, divided by (double)n, rounded once to fp32; a mean that is a NaN is written as 0x7fc00000, whatever the NaNs
+ *      that went in.  Colour of c, per channel, in integers: (2 sum + n) / (2 n), floored.
+ * 6. Order.  The V input vertices first, then the new vertices in ascending label order.  The F input faces first, invalid ones
+ *      included, then the new faces loop by loop in ascending label order, within a loop in the order of rule 5.  V + new
+ *      vertices and F + new faces stay below 2^31 (the host refuses before anything is written).
+ *
+ * A key is ((min(a,b) << 31 | max(a,b)) << 1) | direction, direction 0 for a < b: 63 bits, so that a signed sort orders it; the
+ * key of an invalid face's slots is 2^63 - 1.  The caller sorts the 3 F keys ascending.
+ * cds_mesh_fill_max_edges: CDS_MESH_FILL_MAX_EDGES.  The walk of a loop is one thread's serial chain: that is the limit's reason.
+ * cds_mesh_fill_keys: keys int64 [3 F].
+ * cds_mesh_fill_borders: over the sorted keys; out, in int32 [V] zeroed by the caller (integer atomics): the border half-edges
+ *   that leave and enter each vertex; next, prev int32 [V]: next[a] = b, meaningful where out[a] == 1 only, and prev[b] = a,
+ *   meaningful where in[b] == 1 only.  A key that decodes to an index outside [0, V) is skipped.
+ * cds_mesh_fill_init: regular uint8 [V] (rule 3); next = prev = -1 where the vertex is not regular; the start of the pointer
+ *   doubling in both pairs of arrays, int32 [2][V] each, row 0 the chain along next and row 1 the chain along prev: label = v and
+ *   jump = next[v] (prev[v]) for a regular v, label = -1 and jump = v for another.
+ * cds_mesh_fill_double: one round over list int32 [n_list], the regular vertices, in both rows: label_out[v] = min(label_in[v],
+ *   label_in[jump_in[v]]), jump_out[v] = jump_in[jump_in[v]].  After r rounds label[0][v] is the minimum over v and its 2^r - 1
+ *   successors and label[1][v] that over v and its 2^r - 1 predecessors, -1 if one of them is not regular.  With 2^r >= max_edges
+ *   only a v with label[0][v] == label[1][v] == v can be the v0 of a loop that is filled, and a rim of any length and any
+ *   numbering has at most one such v per 2^r vertices: the pruning saves walks and decides nothing.
+ * cds_mesh_fill_walk: per entry i of list: edges[i] = n of the filled loop whose v0 is list[i], else 0; centre float32
+ *   [n_list][3] and centre_color uint8 [n_list][3]: rule 5's vertex where n >= 4.
+ * cds_mesh_fill_emit: vertex_at, face_at int64 [n_list]: the exclusive prefix sums of (edges >= 4) and of (edges == 3 ? 1 :
+ *   edges); writes the new vertex of entry i at row V + vertex_at[i] of vertices_out / colors_out and its faces from row
+ *   F + face_at[i] of faces_out.  An offset outside [0, new_vertices) / [0, new_faces] writes nothing.
+ *   CDS_EINVAL: a count < 0 or >= 2^31; 3 n_faces >= 2^31; n_list > n_vertices; max_edges outside 3..CDS_MESH_FILL_MAX_EDGES; the
+ *   same array for both sides of a round; a null required pointer (an empty input returns 0 first).
+ */
+#define CDS_MESH_FILL_MAX_EDGES 4096
+int cds_mesh_fill_max_edges(void);
+int cds_mesh_fill_keys(const int* faces, long long n_faces, long long n_vertices, long long* keys, void* stream);
+int cds_mesh_fill_borders(const long long* keys, long long n_keys, long long n_vertices, int* out, int* in, int* next, int* prev,
+                          void* stream);
+int cds_mesh_fill_init(long long n_vertices, const int* out, const int* in, int* next, int* prev, unsigned char* regular,
+                       int* label_a, int* jump_a, int* label_b, int* jump_b, void* stream);
+int cds_mesh_fill_double(const int* list, long long n_list, long long n_vertices, const int* label_in, const int* jump_in,
+                         int* label_out, int* jump_out, void* stream);
+int cds_mesh_fill_walk(const float* vertices, const unsigned char* colors, long long n_vertices, const int* next,
+                       const unsigned char* regular, const int* label, const int* list, long long n_list, int max_edges, int* edges,
+                       float* centre, unsigned char* centre_color, void* stream);
+int cds_mesh_fill_emit(const int* next, const unsigned char* regular, long long n_vertices, long long n_faces, const int* list,
+                       long long n_list, int max_edges, const int* edges, const long long* vertex_at, const long long* face_at,
+                       const float* centre, const unsigned char* centre_color, long long new_vertices, long long new_faces,
+                       float* vertices_out, unsigned char* colors_out, int* faces_out, void* stream);
+
+/*
  * Surface samples of a triangle mesh: a dense, deterministic point set from the faces (csrc/mesh_sample.hip).
  *
  * Inputs.  vertices float32 [V][3]; colors uint8 [V][3]; faces int32 [F][3], every index in [0, V) (the host refuses another

@@ -67,6 +67,9 @@ SIGNATURES = {
     "cds_deconv_prob_zm_sf16_f32": [P, P, P, P, P, P, I, I, I, P, F, P],
     "cds_deconv_prob_zm_sf16_mfma_f32": [P, P, P, P, P, P, P, I, I, I, P, F, P, F, F, P],
     "cds_deconv3d_zm_f32": [P, P, P, P, P, I, I, I, I, I, I, P],
+    "cds_zm_partition": [I, I, I, I, I, I, P],
+    "cds_zm_partition_all": [I, I, I, I, I, I, P],
+    "cds_zm_plan": [I, I, I, I, I, I, I, P],
     "cds_deconv3d_k3s2_f32": [P, P, P, P, P, I, I, I, I, I, I, P],
     "cds_conv2d_f32": [P, P, P, P, I, I, I, I, I, I, I, I, I, P],
     "cds_conv2d_affine_f32": [P, P, P, P, P, I, I, I, I, I, I, I, I, I, P],

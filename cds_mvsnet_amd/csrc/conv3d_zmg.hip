@@ -22,8 +22,11 @@
 // Reference: models/module.py:80-116 (Conv3d + BatchNorm3d + ReLU), :270-315 (CostRegNet).
 #include <stdlib.h>
 
+#include <type_traits>
+
 #include "cds_common.hpp"
 #include "sbf_common.hpp"
+#include "zm_common.hpp"
 
 namespace {
 
@@ -45,9 +48,11 @@ __device__ __attribute__((aligned(32))) float g_zmg_zeros[8];   // what an out-o
 // [term 0 | term 1 | unused] position: the ring shrinks by a third (conv5: 163 200 -> 108 800 B, which is what lets a stride-2
 // column of 32 input channels fit at all), 16 lanes on 16 consecutive x still read 16 different 16-byte bank groups, and the tap
 // offsets stay compile-time constants.
+// BALANCED: the layer may run in the balanced cutting (zm_common.hpp), whose walk over pieces keeps one or two more registers
+// alive across the stage loop; false where the configuration has none left.
 struct ZGDefaults {
   static constexpr int S = 1, RD = 1, MB = 1, TXO = 16, TYO = 8, G = 1, NG = 1, CW = 8, RPW = 1, YS = 1, PF = 1;
-  static constexpr bool PAIR = false, F16 = false, P32 = false;
+  static constexpr bool PAIR = false, F16 = false, P32 = false, BALANCED = true;
 };
 // the split-f16 sibling of a split-bf16 configuration that differs in nothing else
 template <class P>
@@ -99,15 +104,18 @@ struct ZgConv4F16 : ZgF16<ZGDefaults> {
 // 48 bytes per position 163 200 B: no stride-2 column of 32 channels fits), K split in two with two rounds of weights per wave
 // x the four cout blocks = 8 consumer waves of 84 MFMAs per stage (2 x 8 KB exchange), 167 VGPRs; operand reads two K-steps
 // ahead (PF = 2) would spill 14 of them.  profiles/zmarch_conv5.md: 133-139 us tiled -> 68-80 us in the M1 step
+// Uniform cutting only: at 167 of 168 VGPRs the walk over pieces spills 19 registers (56 bytes of scratch).
 struct ZgConv5F16 : ZgF16<ZGDefaults> {
   static constexpr int S = 2, RD = 4, MB = 4, TYO = 2, RPW = 2;
-  static constexpr bool P32 = true;
+  static constexpr bool P32 = true, BALANCED = false;
 };
 // conv6 (64 -> 64): two rounds of weights per wave (K split over four waves), two cout blocks per workgroup and two workgroups
 // (gridDim.y) per 16 x 2 column: the input is staged twice from L2 / the memory-side cache, against four times and stages of 42
 // MFMAs per wave for a K split over eight waves with one cout block per workgroup (ring 108 KB + 2 x 16 KB exchange)
+// Uniform cutting only: at 168 VGPRs the walk over pieces spills 6 registers (28 bytes of scratch).
 struct ZgConv6F16 : ZgF16<ZGDefaults> {
   static constexpr int RD = 8, MB = 4, TYO = 2, RPW = 2, YS = 2;
+  static constexpr bool BALANCED = false;
 };
 
 // The geometry that follows from a configuration P.
@@ -162,7 +170,18 @@ struct ZG {
   static constexpr int PT = PW * 64, PPT = (NITEM + PT - 1) / PT;
 };
 
-template <class Cfg>
+// The uniform cutting has no walk: one unit per workgroup, from the index arithmetic in the kernel.
+struct ZmgNoWalk {
+  __device__ __forceinline__ ZmgNoWalk(int, int, int, int) {}
+  __device__ __forceinline__ bool empty() const { return false; }
+  __device__ __forceinline__ ZmColumn column(int) const { return {0, 0, 0, 0}; }
+  __device__ __forceinline__ bool next_piece() { return false; }
+};
+
+// BAL: the balanced cutting (zm_common.hpp; a stage = G output planes, a column = tiles_x x tiles_y of them per cout split
+// blockIdx.y): the workgroup walks the pieces of its range, one march each.  The consumer waves' weights, the bias and the running
+// bound stay; the producers' item tables, lane_ok and the output bases are set up again for every piece.
+template <class Cfg, bool BAL>
 __global__ __launch_bounds__(Cfg::THREADS, 1) void conv3d_zmg_kernel(const float* __restrict__ x, const uint4* __restrict__ wsp,
                                                                   const float* __restrict__ bias, float* __restrict__ out, int Cout,
                                                                   int D, int H, int W, int Do, int Ho, int Wo, int act,
@@ -179,16 +198,30 @@ __global__ __launch_bounds__(Cfg::THREADS, 1) void conv3d_zmg_kernel(const float
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  // unit = (column tx, ty; z segment): the z segments of a column are consecutive workgroups
-  const int nseg = (Do + zseg - 1) / zseg;
-  int unit = cds_xcd_remap(blockIdx.x, gridDim.x);
-  const int seg = unit % nseg;
-  unit /= nseg;
-  const int tx_i = unit % tiles_x, ty_i = unit / tiles_x;
-  const int z0 = seg * zseg, z1 = min(Do, z0 + zseg);             // output planes of this unit
-  const int nstages = (z1 - z0 + G - 1) / G;
-  const int gx0 = tx_i * Cfg::TXO * S - 1, gy0 = ty_i * Cfg::TYO * S - 1;
-  const int zin0 = S * z0 - 1;                                    // input plane in ring slot 0; plane p lives in slot (p - zin0) % R
+  std::conditional_t<BAL, ZmWalk<true>, ZmgNoWalk> walk(tiles_x * tiles_y, (Do + G - 1) / G, 0, ZM_MINLEN_ZMG);
+  if (BAL && walk.empty()) return;
+  // what a march derives from its unit.  Uniform cutting: unit = (column tx, ty; z segment), the z segments of a column are
+  // consecutive workgroups; balanced: a piece of the walk (set again behind the barrier between two pieces).  [z0, z1): its output
+  // planes; input plane zin0 is in ring slot 0 and plane p lives in slot (p - zin0) % R
+  int tx_i, ty_i, z0, z1, nstages, gx0, gy0, zin0;
+  auto set_piece = [&] {
+    if constexpr (BAL) {
+      const ZmColumn zc = walk.column(tiles_x);
+      tx_i = zc.tx_i, ty_i = zc.ty_i, z0 = zc.a0 * G, z1 = min(Do, zc.a1 * G);
+    } else {
+      const int nseg = (Do + zseg - 1) / zseg;
+      int unit = cds_xcd_remap(blockIdx.x, gridDim.x);
+      const int seg = unit % nseg;
+      unit /= nseg;
+      tx_i = unit % tiles_x, ty_i = unit / tiles_x;
+      z0 = seg * zseg, z1 = min(Do, z0 + zseg);
+    }
+    nstages = (z1 - z0 + G - 1) / G;
+    gx0 = tx_i * Cfg::TXO * S - 1, gy0 = ty_i * Cfg::TYO * S - 1;
+    zin0 = S * z0 - 1;
+    return true;
+  };
+  set_piece();
 
   if (wave >= Cfg::CW) {
     // ============================== producers ==============================
@@ -201,6 +234,7 @@ __global__ __launch_bounds__(Cfg::THREADS, 1) void conv3d_zmg_kernel(const float
     __builtin_amdgcn_s_setprio(CDS_ZMG_PPRIO);
     constexpr int PT = Cfg::PT, PPT = Cfg::PPT;
     const int ptid = tid - Cfg::CW * 64;
+    do {
     // item = one 8-channel position of the stage's NNEW new planes: x fastest, then slice, row, plane
     int s_pl[PPT], s_dst[PPT];
     long long s_off[PPT];                                         // element offset in x[] for plane index 0 of the volume
@@ -278,6 +312,7 @@ __global__ __launch_bounds__(Cfg::THREADS, 1) void conv3d_zmg_kernel(const float
       }
       __syncthreads();                                 // #(st + 2)
     }
+    } while (BAL && walk.next_piece() && set_piece());
     return;
   }
 
@@ -316,27 +351,34 @@ __global__ __launch_bounds__(Cfg::THREADS, 1) void conv3d_zmg_kernel(const float
   float amax = 0.f;                                    // running maximum of the magnitudes this lane stores (split-f16: the output's bound)
   const int co = PAIR ? 4 * (g & 1) : mbg * 16 + 4 * g;
   const float4 bv = (bias && co < Cout) ? *reinterpret_cast<const float4*>(bias + co) : make_float4(0.f, 0.f, 0.f, 0.f);
+  // Balanced: of the lane's place in a column only xl (its x inside the column's first run) and its output offset inside the
+  // column's first row stay in registers across the pieces; a piece adds wave-uniform values to them (one register more than the
+  // uniform form keeps, none where that holds a 64-bit address per lane)
+  const int xl = PAIR ? 2 * j + (g >> 1) : j;
+  do {
   // N-tile n of this wave = (row r, x run xt, plane i): n = (r XT + xt) G + i
   constexpr int XW = PAIR ? 32 : 16;
+  constexpr bool UBASE = Cfg::P32 || BAL;                // output address = wave-uniform 64-bit part + 32-bit lane offset
   const int oy0 = ty_i * Cfg::TYO + part * Cfg::ROWS;
-  const int ox0 = tx_i * Cfg::TXO + (PAIR ? 2 * j + (g >> 1) : j);
+  const int ox0 = tx_i * Cfg::TXO + xl;
+  const int x_left = Wo - tx_i * Cfg::TXO;               // (wave-uniform) voxels from the column's first to the end of the row
   float* const obase = out + ((size_t)((size_t)z0 * Ho + oy0) * Wo + ox0) * Cout + co;   // this lane's voxel of N-tile 0, stage 0
   // P32 configurations (168-register budget, 112 of them weights): the same address as a wave-uniform 64-bit part (SGPRs) + a 32-bit
   // lane offset inside the column's first row, instead of 64-bit per-lane addresses that the compiler keeps in VGPRs across the stage
   // loop (the no-K-split conv2 spilled four registers for them)
   float* const obase_u = out + ((size_t)((size_t)z0 * Ho + oy0) * Wo + tx_i * Cfg::TXO) * Cout;
-  const unsigned olane = (unsigned)((ox0 - tx_i * Cfg::TXO) * Cout + co);
+  const unsigned olane = BAL ? (unsigned)(xl * Cout + co) : (unsigned)((ox0 - tx_i * Cfg::TXO) * Cout + co);
   auto out_ptr = [&](int pl, int r, int xt) -> float* {
     const size_t o = ((size_t)((size_t)pl * Ho + r) * Wo + xt * XW) * Cout;
-    return Cfg::P32 ? obase_u + o + olane : obase + o;
+    return UBASE ? obase_u + o + olane : obase + o;
   };
   bool lane_ok[Cfg::XT];
 #pragma unroll
-  for (int xt = 0; xt < Cfg::XT; ++xt) lane_ok[xt] = ox0 + xt * XW < Wo && co < Cout;
+  for (int xt = 0; xt < Cfg::XT; ++xt) lane_ok[xt] = (BAL ? xl + xt * XW < x_left : ox0 + xt * XW < Wo) && co < Cout;
   // the epilogue of N-tile n of stage st.  in_x(xt): is this lane's voxel of x run xt inside the volume - from the table where n is a
   // compile-time constant, computed where it is known only at run time (K split in four: n = 4 j + k)
   auto in_x_ct = [&](int xt) { return lane_ok[xt]; };
-  auto in_x_rt = [&](int xt) { return ox0 + xt * XW < Wo && co < Cout; };
+  auto in_x_rt = [&](int xt) { return (BAL ? xl + xt * XW < x_left : ox0 + xt * XW < Wo) && co < Cout; };
   auto store_tile = [&](int n, int st, const f32x4& a, auto in_x) {
     const int i = n % G, rx = n / G, xt = rx % Cfg::XT, r = rx / Cfg::XT;
     if (z0 + st * G + i >= z1 || oy0 + r >= Ho) return;            // wave-uniform
@@ -477,13 +519,16 @@ __global__ __launch_bounds__(Cfg::THREADS, 1) void conv3d_zmg_kernel(const float
     __syncthreads();                                   // #(st + 1)
   }
   if (Cfg::KSPL >= 2 || late) finish(nstages - 1);
+  } while (BAL && walk.next_piece() && set_piece());
   if (F16) sf16_publish_bound(amax, out_bound);       // this wave's largest stored magnitude -> the bound the next layer scales by
 }
 
 // z segments per column: enough workgroups for the 256 CUs (one workgroup per CU: the ring takes most of the LDS) with full
 // rounds of them, against the two or three stage times a segment spends filling its pipeline.
-inline int zmg_pick_nseg(int cols, int Do, int G) {
+// cost_out: the model cost of the choice, < 0 where the knob forced it (the layer then keeps the uniform cutting).
+inline int zmg_pick_nseg(int cols, int Do, int G, double* cost_out = nullptr) {
   const int nseg_env = cds_env_int("CDS_ZMG_NSEG", 0);   // A/B knob
+  if (cost_out) *cost_out = -1.0;
   if (nseg_env > 0) return nseg_env;
   const int stages = cds_ceil_div(Do, G);
   int best = 1;
@@ -494,7 +539,23 @@ inline int zmg_pick_nseg(int cols, int Do, int G) {
     const double cost = (double)cds_ceil_div(cols * cds_ceil_div(stages, per), 256) * (per + 2.5);
     if (cost < best_cost - 1e-9) { best_cost = cost; best = n; }
   }
+  if (cost_out) *cost_out = best_cost;
   return best;
+}
+
+// The cutting of a layer of `cols` columns x ys cout splits: the uniform chooser's segments, and whether the balanced cutting runs
+// instead (zm_common.hpp): each cout split is then cut over ncu / ys workgroups, so a workgroup keeps its weights.
+struct ZmgPlan {
+  int nseg, nwg;
+  bool balanced;
+  double ucost, bcost;
+};
+inline ZmgPlan zmg_plan(int cols, int ys, int Do, int G, int ncu, int balance) {
+  ZmgPlan p;
+  p.nseg = zmg_pick_nseg(cols * ys, Do, G, &p.ucost);
+  p.nwg = max(1, ncu / ys);
+  p.balanced = zm_choose_balanced(balance, p.ucost, cols, cds_ceil_div(Do, G), p.nwg, ZM_MINLEN_ZMG, 2.5, &p.bcost);
+  return p;
 }
 
 template <class P>
@@ -504,16 +565,29 @@ int launch_zmg(const float* x, const void* wsp, const float* b, float* out, int 
   constexpr int S = Cfg::S;
   const int Do = (D - 1) / S + 1, Ho = (H - 1) / S + 1, Wo = (W - 1) / S + 1;
   const int tx = cds_ceil_div(Wo, Cfg::TXO), ty = cds_ceil_div(Ho, Cfg::TYO);
-  int nseg = zmg_pick_nseg(tx * ty * Cfg::YS, Do, Cfg::G);
+  const ZmgPlan plan = zmg_plan(tx * ty, Cfg::YS, Do, Cfg::G, zm_ncu(), zm_balance_knob());
+  int nseg = plan.nseg;
   const int zseg = cds_ceil_div(cds_ceil_div(Do, nseg), Cfg::G) * Cfg::G;
   nseg = cds_ceil_div(Do, zseg);
   if (min_wgs > 0 && tx * ty * nseg * Cfg::YS < min_wgs) return CDS_ZMG_UNSUPPORTED;   // too few columns to fill the chip
-  return cds_launch_lds<conv3d_zmg_kernel<Cfg>>(Cfg::LDSB, dim3(tx * ty * nseg, Cfg::YS), dim3(Cfg::THREADS), Cfg::LDSB, st, x,
-                                                reinterpret_cast<const uint4*>(wsp), b, out, Cout, D, H, W, Do, Ho, Wo, act, tx, ty, zseg,
-                                                in_bound, w_inv, out_bound);
+  if constexpr (P::BALANCED)
+    if (plan.balanced)
+      return cds_launch_lds<conv3d_zmg_kernel<Cfg, true>>(Cfg::LDSB, dim3(plan.nwg, Cfg::YS), dim3(Cfg::THREADS), Cfg::LDSB, st, x,
+                                                          reinterpret_cast<const uint4*>(wsp), b, out, Cout, D, H, W, Do, Ho, Wo, act, tx,
+                                                          ty, zseg, in_bound, w_inv, out_bound);
+  return cds_launch_lds<conv3d_zmg_kernel<Cfg, false>>(Cfg::LDSB, dim3(tx * ty * nseg, Cfg::YS), dim3(Cfg::THREADS), Cfg::LDSB, st, x,
+                                                       reinterpret_cast<const uint4*>(wsp), b, out, Cout, D, H, W, Do, Ho, Wo, act, tx, ty,
+                                                       zseg, in_bound, w_inv, out_bound);
 }
 
 }  // namespace
+
+// The plan of a layer for cds_zm_plan (deconv3d_zm.hip), on the host.
+int cds_zmg_plan(int cols, int ys, int Do, int G, int ncu, int balance, int* nseg, double* ucost, double* bcost) {
+  const ZmgPlan p = zmg_plan(cols, ys, Do, G, ncu, balance);
+  *nseg = p.nseg, *ucost = p.ucost, *bcost = p.bcost;
+  return p.balanced;
+}
 
 // Dispatch for cds_conv3d_sbf_f32 (conv3d_sbf.hip): returns CDS_ZMG_UNSUPPORTED when the shape stays on the tiled kernels.
 // pair != 0: Cout == 8 with the pair-packed weights (ops.split_pack_conv3d_pair), stride 1.

@@ -53,7 +53,9 @@ __device__ __forceinline__ void dzm_produce(const float* __restrict__ x, unsigne
 }
 
 // F16: split-f16 arithmetic (sbf_common.hpp): two fp16 terms, three products per K-step, tensor scales from device bounds.
-template <int ROUNDS, bool F16>
+// BAL: the balanced cutting (zm_common.hpp): the workgroup walks the pieces of its range, one march each; the weights, the bias and
+// the running bound stay, what follows from the column is set up again for every piece.
+template <int ROUNDS, bool F16, bool BAL>
 __global__ __launch_bounds__((DZC<ROUNDS>::THREADS), 3) void deconv3d_zm_kernel(
     const float* __restrict__ x, const uint4* __restrict__ wcls, const float* __restrict__ bias, const float* __restrict__ skip,
     float* __restrict__ out, int D, int H, int W, int tiles_x, int ncols, int seg_len, int act, const float* __restrict__ in_bound,
@@ -67,14 +69,15 @@ __global__ __launch_bounds__((DZC<ROUNDS>::THREADS), 3) void deconv3d_zm_kernel(
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const ZmColumn zc = zm_column(tiles_x, ncols, seg_len, D);
-  const int a0 = zc.a0, a1 = zc.a1;
-  if (a0 >= a1) return;
-  const int X0 = zc.tx_i * C::TX, Y0 = zc.ty_i * C::TY;
+  ZmWalk<BAL> walk(ncols, D, seg_len, ZM_MINLEN_CELL);
+  if (walk.empty()) return;
   const int Ho = 2 * H, Wo = 2 * W;
 
   if (wave >= C::CW) {
-    dzm_produce<C, F16>(x, lds, tid - C::CW * 64, X0, Y0, D, H, W, a0, a1, xs);
+    do {
+      const ZmColumn zc = walk.column(tiles_x);
+      dzm_produce<C, F16>(x, lds, tid - C::CW * 64, zc.tx_i * C::TX, zc.ty_i * C::TY, D, H, W, zc.a0, zc.a1, xs);
+    } while (BAL && walk.next_piece());
     return;
   }
 
@@ -95,10 +98,14 @@ __global__ __launch_bounds__((DZC<ROUNDS>::THREADS), 3) void deconv3d_zm_kernel(
   }
   const float4 bv = bias ? *reinterpret_cast<const float4*>(bias + 4 * g) : make_float4(0.f, 0.f, 0.f, 0.f);
   const int b_off = (((g >> 1) * C::IXP) + j + (g & 1)) * POSB;       // slot g = (dy, dx)
-  const int xv = 2 * (X0 + j) + px;
-  const bool x_ok = X0 + j < W;
   const size_t zstride = (size_t)Ho * Wo * Cout;
   float amax = 0.f;                                   // split-f16: running maximum of the magnitudes this lane stores
+  do {
+  const ZmColumn zc = walk.column(tiles_x);
+  const int a0 = zc.a0, a1 = zc.a1;
+  const int X0 = zc.tx_i * C::TX, Y0 = zc.ty_i * C::TY;
+  const int xv = 2 * (X0 + j) + px;
+  const bool x_ok = X0 + j < W;
   __syncthreads();                                    // #0
   for (int a = a0; a < a1; ++a) {
     const unsigned char* lo = lds + (a % C::NSLOT) * C::SLOTB + b_off;
@@ -151,6 +158,7 @@ __global__ __launch_bounds__((DZC<ROUNDS>::THREADS), 3) void deconv3d_zm_kernel(
     }
     __syncthreads();
   }
+  } while (BAL && walk.next_piece());
   if (F16) sf16_publish_bound(amax, out_bound);
 }
 
@@ -163,6 +171,7 @@ __global__ __launch_bounds__((DZC<ROUNDS>::THREADS), 3) void deconv3d_zm_kernel(
 // are two workgroups of a column (gridDim.y): a wave's weights are 8 rounds x 2 terms x 4 = 64 VGPRs, 128 for class 7 - both blocks in
 // one workgroup would be 256 for that wave.  The column's input is then staged twice, the second time from L2 / the memory-side cache.
 constexpr int DZM64_W1L = 2;                          // rounds of class 7's second operand kept in LDS (1 KB per round and term)
+template <bool BAL>
 __global__ __launch_bounds__((DZC<8, 4>::THREADS), 3) void deconv3d_zm64_kernel(
     const float* __restrict__ x, const uint4* __restrict__ wsp, const float* __restrict__ bias, const float* __restrict__ skip,
     float* __restrict__ out, int D, int H, int W, int tiles_x, int ncols, int seg_len, int act, const float* __restrict__ in_bound,
@@ -175,15 +184,16 @@ __global__ __launch_bounds__((DZC<8, 4>::THREADS), 3) void deconv3d_zm64_kernel(
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const ZmColumn zc = zm_column(tiles_x, ncols, seg_len, D);
-  const int a0 = zc.a0, a1 = zc.a1;
-  if (a0 >= a1) return;
+  ZmWalk<BAL> walk(ncols, D, seg_len, ZM_MINLEN_CELL);
+  if (walk.empty()) return;
   const int mbtot = gridDim.y, mb0 = blockIdx.y;      // this workgroup's 16-cout block
-  const int X0 = zc.tx_i * C::TX, Y0 = zc.ty_i * C::TY;
   const int Ho = 2 * H, Wo = 2 * W;
 
   if (wave >= C::CW) {
-    dzm_produce<C, true>(x, lds, tid - C::CW * 64, X0, Y0, D, H, W, a0, a1, xs);
+    do {
+      const ZmColumn zc = walk.column(tiles_x);
+      dzm_produce<C, true>(x, lds, tid - C::CW * 64, zc.tx_i * C::TX, zc.ty_i * C::TY, D, H, W, zc.a0, zc.a1, xs);
+    } while (BAL && walk.next_piece());
     return;
   }
 
@@ -215,11 +225,15 @@ __global__ __launch_bounds__((DZC<8, 4>::THREADS), 3) void deconv3d_zm64_kernel(
   const bool live = g < (1 + pz) * ny * nx;
   const int dz = live ? g / (ny * nx) : 0, dy = live ? (g / nx) % ny : 0, dx = live ? g % nx : 0;
   const int b_off = ((dy * C::IXP) + j + dx) * POSB;
+  const size_t zstride = (size_t)Ho * Wo * Cout;
+  float amax = 0.f;                                   // running maximum of the magnitudes this lane stores
+  do {
+  const ZmColumn zc = walk.column(tiles_x);
+  const int a0 = zc.a0, a1 = zc.a1;
+  const int X0 = zc.tx_i * C::TX, Y0 = zc.ty_i * C::TY;
   const int xv = 2 * (X0 + j) + px;
   const bool x_ok = X0 + j < W;
-  const size_t zstride = (size_t)Ho * Wo * Cout;
   const int nrows = min(C::TY, H - Y0);
-  float amax = 0.f;                                   // running maximum of the magnitudes this lane stores
   __syncthreads();                                    // #0
   for (int a = a0; a < a1; ++a) {
     const unsigned char* p0 = lds + (a % C::NSLOT) * C::SLOTB + b_off;
@@ -267,6 +281,7 @@ __global__ __launch_bounds__((DZC<8, 4>::THREADS), 3) void deconv3d_zm64_kernel(
     }
     __syncthreads();
   }
+  } while (BAL && walk.next_piece());
   sf16_publish_bound(amax, out_bound);
 }
 
@@ -283,12 +298,19 @@ int cds_deconv3d_zm64_dispatch(const float* x, const void* wsp, const float* bia
   using C = DZC<8, 4>;
   const int tiles_x = cds_ceil_div(W, C::TX), tiles_y = cds_ceil_div(H, C::TY);
   const int ncols = tiles_x * tiles_y;
-  const int seg_len = cds_ceil_div(D, zm_pick_nseg(ncols * 2, D, 24, "CDS_DZM_NSEG"));
+  double ucost;
+  const int seg_len = cds_ceil_div(D, zm_pick_nseg(ncols * 2, D, 24, "CDS_DZM_NSEG", &ucost));
   const int nseg = cds_ceil_div(D, seg_len);
   if (deep == 1 && ncols * nseg * 2 < 256) return CDS_ZMG_UNSUPPORTED;
-  return cds_launch_lds<deconv3d_zm64_kernel>(160 * 1024, dim3(ncols * nseg, 2), dim3(C::THREADS), C::LDS + DZM64_W1L * 2 * 1024, st, x,
-                                              reinterpret_cast<const uint4*>(wsp), bias, skip, out, D, H, W, tiles_x, ncols, seg_len, act,
-                                              in_bound, w_inv, out_bound);
+  // balanced: each of the two cout blocks (gridDim.y) is cut over half of the CUs, so a workgroup keeps its block's weights
+  const int nwg = max(1, zm_ncu() / 2);
+  const bool bal = zm_choose_balanced(zm_balance_knob(), ucost, ncols, D, nwg, ZM_MINLEN_CELL, 1.5);
+  auto launch = [&](auto b) {
+    return cds_launch_lds<deconv3d_zm64_kernel<decltype(b)::value>>(
+        160 * 1024, dim3(b ? nwg : ncols * nseg, 2), dim3(C::THREADS), C::LDS + DZM64_W1L * 2 * 1024, st, x,
+        reinterpret_cast<const uint4*>(wsp), bias, skip, out, D, H, W, tiles_x, ncols, seg_len, act, in_bound, w_inv, out_bound);
+  };
+  return bal ? launch(std::true_type()) : launch(std::false_type());
 }
 
 // ConvTranspose3d k3 s2 p1 op1 (+bias +ReLU +residual) 32 -> 16 in split-bf16 arithmetic, channels-last: x [D][H][W][32] ->
@@ -301,15 +323,70 @@ static int dzm_entry(const float* x, const void* weight_cls, const float* bias, 
   hipStream_t st = (hipStream_t)stream;
   const int tiles_x = cds_ceil_div(W, C::TX), tiles_y = cds_ceil_div(H, C::TY);
   const int ncols = tiles_x * tiles_y;
-  const int seg_len = cds_ceil_div(D, zm_pick_nseg(ncols, D, 24, "CDS_DZM_NSEG"));
+  double ucost;
+  const int seg_len = cds_ceil_div(D, zm_pick_nseg(ncols, D, 24, "CDS_DZM_NSEG", &ucost));
   const int nseg = cds_ceil_div(D, seg_len);
+  const int nwg = zm_ncu();
+  const bool bal = zm_choose_balanced(zm_balance_knob(), ucost, ncols, D, nwg, ZM_MINLEN_CELL, 1.5);
   // split-f16 where the caller gave the input's bound (the split-bf16 entry passes no bounds and w_inv = 1; its kernel reads none of them)
-  auto launch = [&](auto f16) {
-    return cds_launch_lds<deconv3d_zm_kernel<4, decltype(f16)::value>>(160 * 1024, dim3(ncols * nseg), dim3(C::THREADS), C::LDS, st, x,
-                                                                       reinterpret_cast<const uint4*>(weight_cls), bias, skip, out, D, H, W,
-                                                                       tiles_x, ncols, seg_len, act, in_bound, w_inv, out_bound);
+  auto launch = [&](auto f16, auto b) {
+    return cds_launch_lds<deconv3d_zm_kernel<4, decltype(f16)::value, decltype(b)::value>>(
+        160 * 1024, dim3(b ? nwg : ncols * nseg), dim3(C::THREADS), C::LDS, st, x, reinterpret_cast<const uint4*>(weight_cls), bias, skip,
+        out, D, H, W, tiles_x, ncols, seg_len, act, in_bound, w_inv, out_bound);
   };
-  return in_bound ? launch(std::true_type()) : launch(std::false_type());
+  if (bal) return in_bound ? launch(std::true_type(), std::true_type()) : launch(std::false_type(), std::true_type());
+  return in_bound ? launch(std::true_type(), std::false_type()) : launch(std::false_type(), std::false_type());
+}
+
+// The cutting of zm_common.hpp for the tests, on the host (no GPU call).  cds_zm_partition: the pieces of workgroup wg as
+// (column, first plane, one past the last plane) triples in out[3 * 8], a stage being `unit` planes of the `planes` of a column
+// (conv3d_zmg: G output planes; the cell-plane kernels: 1); returns their number, which exceeds 8 where the layer keeps the uniform
+// cutting (only the first 8 are then stored).  cds_zm_plan: what the host would run for a layer of `cols` columns of `planes`
+// planes and ys cout splits (gridDim.y) on ncu workgroups under CDS_ZM_BALANCE = balance; family 0 = conv3d_zmg (stages of `unit`
+// planes), 1 = the transposed convolutions (nseg cap 24), 2 = the fused tail (cap 16); out = {balanced?, segments of the uniform form, uniform cost, balanced
+// cost} (costs in stages x 1000); returns 0.
+extern "C" int cds_zm_partition(int cols, int planes, int unit, int nwg, int wg, int min_len, int* out) {
+  if (cols < 1 || planes < 1 || unit < 1 || nwg < 1 || wg < 0 || wg >= nwg || min_len < 1 || !out) return CDS_EINVAL;
+  ZmPiece pc[ZM_MAX_PIECES];
+  const int n = zm_partition(cols, cds_ceil_div(planes, unit), nwg, wg, min_len, pc);
+  for (int i = 0; i < min(n, ZM_MAX_PIECES); ++i) {
+    out[3 * i] = pc[i].col;
+    out[3 * i + 1] = pc[i].s0 * unit;
+    out[3 * i + 2] = min(planes, pc[i].s1 * unit);
+  }
+  return n;
+}
+// the same for all nwg workgroups at once, up to cap pieces each: out[wg][1 + 3 cap] = {number of pieces, triples}
+extern "C" int cds_zm_partition_all(int cols, int planes, int unit, int nwg, int min_len, int cap, int* out) {
+  if (cols < 1 || planes < 1 || unit < 1 || nwg < 1 || min_len < 1 || cap < 1 || !out) return CDS_EINVAL;
+  const int stages = cds_ceil_div(planes, unit);
+  for (int wg = 0; wg < nwg; ++wg) {
+    int* o = out + (size_t)wg * (1 + 3 * cap);
+    const ZmRange r = zm_range(cols, stages, nwg, wg, min_len);
+    int n = 0;
+    for (int pos = r.lo; pos < r.hi; ++n) {
+      const ZmPiece p = zm_piece_at(pos, r.hi, stages);
+      if (n < cap) o[1 + 3 * n] = p.col, o[2 + 3 * n] = p.s0 * unit, o[3 + 3 * n] = min(planes, p.s1 * unit);
+      pos = p.col * stages + p.s1;
+    }
+    o[0] = n;
+  }
+  return 0;
+}
+int cds_zmg_plan(int cols, int ys, int Do, int G, int ncu, int balance, int* nseg, double* ucost, double* bcost);   // conv3d_zmg.hip
+extern "C" int cds_zm_plan(int family, int cols, int planes, int unit, int ys, int ncu, int balance, int* out) {
+  if (family < 0 || family > 2 || cols < 1 || planes < 1 || unit < 1 || ys < 1 || ncu < 1 || !out) return CDS_EINVAL;
+  int nseg = 0, bal = 0;
+  double ucost = 0, bcost = 0;
+  if (family == 0) {
+    bal = cds_zmg_plan(cols, ys, planes, unit, ncu, balance, &nseg, &ucost, &bcost);
+  } else {
+    nseg = zm_pick_nseg(cols * ys, planes, family == 1 ? 24 : 16, "", &ucost);
+    bal = zm_choose_balanced(balance, ucost, cols, planes, max(1, ncu / ys), ZM_MINLEN_CELL, 1.5, &bcost,
+                             family == 2 ? ZM_BALANCE_MARGIN_TAIL : ZM_BALANCE_MARGIN);
+  }
+  out[0] = bal, out[1] = nseg, out[2] = (int)lrint(ucost * 1000), out[3] = (int)lrint(bcost * 1000);
+  return 0;
 }
 
 extern "C" int cds_deconv3d_zm_f32(const float* x, const void* weight_cls, const float* bias, const float* skip, float* out,

@@ -87,7 +87,10 @@ __device__ __forceinline__ float dpz_row_shl1(float v) {
   } while (0)
 // MF: prob on the matrix cores (header comment).  pw is then the operand table of ops.split_pack_prob ([3 R][3 ky][64 lanes] x 16 B),
 // p_inv 1 / its scale, and y is scaled by s_y from the bound skip_bound + y_gain * in_bound + max |bias| >= max |y|.
-template <bool F16, bool MF>
+// BAL: the balanced cutting (zm_common.hpp): the workgroup walks the pieces of its range, one march each.  The LDS weight image, the
+// prob waves' operands and the consumers' bias stay; the staging tables, the output and residual offsets, the border flag and the
+// prob accumulators are set up again for every piece.
+template <bool F16, bool MF, bool BAL>
 __global__ __launch_bounds__(DPZ::THREADS, 3) void deconv_prob_zm_kernel(
     const float* __restrict__ x, const uint4* __restrict__ wsp, const float* __restrict__ bias, const float* __restrict__ skip,
     const float* __restrict__ pw, float* __restrict__ out, int D, int H, int W, int tiles_x, int ncols, int seg_len,
@@ -108,14 +111,18 @@ __global__ __launch_bounds__(DPZ::THREADS, 3) void deconv_prob_zm_kernel(
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const ZmColumn zc = zm_column(tiles_x, ncols, seg_len, D);
-  const int tx_i = zc.tx_i, ty_i = zc.ty_i, a0 = zc.a0, a1 = zc.a1;
-  if (a0 >= a1) return;
-  const int X0 = tx_i * C::CXR - 1, Y0 = ty_i * C::CYR - 1;     // first computed cell
+  ZmWalk<BAL> walk(ncols, D, seg_len, ZM_MINLEN_CELL);
+  if (walk.empty()) return;
   const int Do = 2 * D, Ho = 2 * H, Wo = 2 * W;
-  const int qs = a0 > 0 ? 2 * a0 - 1 : 0;                        // first y plane this segment needs
-  const int qe = min(Do - 1, 2 * a1);                            // last one
-  const int te = 2 * a1 + 1;                                     // last half-step
+  // what a march derives from its column and planes: set up by each branch for each of its pieces (set up once ahead of the branch
+  // and updated between the pieces, the matrix-core form needs 8 more registers in the uniform cutting and spills in the balanced)
+#define DPZ_PIECE()                                                                                               \
+  const ZmColumn zc = walk.column(tiles_x);                                                                       \
+  const int tx_i = zc.tx_i, ty_i = zc.ty_i, a0 = zc.a0, a1 = zc.a1;                                               \
+  const int X0 = tx_i * C::CXR - 1, Y0 = ty_i * C::CYR - 1; /* first computed cell */                             \
+  const int qs = a0 > 0 ? 2 * a0 - 1 : 0;                   /* first y plane this segment needs */                \
+  const int qe = min(Do - 1, 2 * a1);                       /* last one */                                        \
+  const int te = 2 * a1 + 1;                                /* last half-step */
   {
     uint4* wdst = reinterpret_cast<uint4*>(lds);
     for (int i = tid; i < C::WB / 16; i += C::THREADS) wdst[i] = wsp[i];
@@ -127,7 +134,6 @@ __global__ __launch_bounds__(DPZ::THREADS, 3) void deconv_prob_zm_kernel(
     const int ptid = tid - C::CW * 64;
     // ---- staging of input cell planes ----
     ZmCellStage<C, C::PW * 64, F16, true> stage;    // (the prologue of a segment; inside the march the consumers stage)
-    stage.init(ptid, X0, Y0, H, W);
     auto issue = [&](int plane) { stage.issue(x, plane, D, H, W); };
     auto deposit = [&](int plane) { stage.deposit(inring + (plane & 1) * C::SLOTB, xs); };
     if constexpr (MF) {
@@ -139,24 +145,15 @@ __global__ __launch_bounds__(DPZ::THREADS, 3) void deconv_prob_zm_kernel(
       for (int r = 0; r < 3; ++r)
 #pragma unroll
         for (int ky = 0; ky < 3; ++ky) wa[r][ky].u = pwm[(r * 3 + ky) * 64 + lane];
-      const int oy0 = ty_i * 2 * C::CYR + C::PR * rg;
       int b_off[C::MT];                                // operand byte offset inside a y row
 #pragma unroll
       for (int t = 0; t < C::MT; ++t) {
         const int xl = C::MSTEP * t + n;               // y-plane x of this lane's read; its output is owned column xl - 2
         b_off[t] = (g & 1) * C::YTERMB + (xl & 1) * C::YPARB + (((xl >> 1) ^ ((xl & 1) << 3)) << 4);
       }
-      // outputs: tile t of row oy0 + r is element st_lane of the (wave-uniform) row pointer + MSTEP t, where x < Wo: MSTEP t < st_lim
-      const int ox0 = tx_i * 2 * C::CXR + n - 2;
       const bool st_ok = g < 3 && n >= 2 && n <= 13;
-      const unsigned st_lane = st_ok ? oy0 * Wo + ox0 : 0;
-      const int st_lim = st_ok ? Wo - ox0 : 0;
       const float inv = p_inv / ys;
       float A[C::MT][C::PR];
-#pragma unroll
-      for (int t = 0; t < C::MT; ++t)
-#pragma unroll
-        for (int r = 0; r < C::PR; ++r) A[t][r] = 0.f;
       const int yrow0 = (C::PR * rg + 1) * C::YROWB;   // first of the PR + 2 input rows
       auto load_b = [&](BV (&b)[C::PR + 2], const unsigned char* yb, int t) {
 #pragma unroll
@@ -185,6 +182,18 @@ __global__ __launch_bounds__(DPZ::THREADS, 3) void deconv_prob_zm_kernel(
           }
         }
       };
+      do {
+      DPZ_PIECE()
+      stage.init(ptid, X0, Y0, H, W);
+      const int oy0 = ty_i * 2 * C::CYR + C::PR * rg;
+      // outputs: tile t of row oy0 + r is element st_lane of the (wave-uniform) row pointer + MSTEP t, where x < Wo: MSTEP t < st_lim
+      const int ox0 = tx_i * 2 * C::CXR + n - 2;
+      const unsigned st_lane = st_ok ? oy0 * Wo + ox0 : 0;
+      const int st_lim = st_ok ? Wo - ox0 : 0;
+#pragma unroll
+      for (int t = 0; t < C::MT; ++t)
+#pragma unroll
+        for (int r = 0; r < C::PR; ++r) A[t][r] = 0.f;
       const int ap = qs >> 1;
       issue(ap);
       deposit(ap);
@@ -219,22 +228,14 @@ __global__ __launch_bounds__(DPZ::THREADS, 3) void deconv_prob_zm_kernel(
           for (int r = 0; r < C::PR; ++r) A[tt][r] = own ? 0.f : A[tt][r];
         __syncthreads();
       }
+      } while (BAL && walk.next_piece());
       return;
     }
     // ---- prob: lane = x column c of the owned 60, wave = 3 output rows ----
     const int c = ptid & 63, rg = ptid >> 6;
-    const int ox = tx_i * 2 * C::CXR + c;
-    const int oy0 = ty_i * 2 * C::CYR + C::PR * rg;
-    const bool lane_ok = c < 2 * C::CXR && ox < Wo;
     const int yoff = (C::PR * rg + 1) * C::YROWB + (c + 1) * 16;    // window origin: local row 3 rg + 1, local x c + 1
     int st_off[C::PR];                                              // element offsets of this lane's outputs inside a plane
-#pragma unroll
-    for (int r = 0; r < C::PR; ++r) st_off[r] = (lane_ok && oy0 + r < Ho) ? (oy0 + r) * Wo + ox : -1;
     float A[3][C::PR];
-#pragma unroll
-    for (int s = 0; s < 3; ++s)
-#pragma unroll
-      for (int r = 0; r < C::PR; ++r) A[s][r] = 0.f;
     // Six batches b = (dx, channel half) of 5 window rows x 4 channels and their 9 (ky, kz) x 4 weights.  The weights come
     // through the scalar cache into SGPRs; scalar and LDS loads share lgkmcnt and return out of order with respect to each
     // other, so every wait on either is a wait for ALL of both: the loads of batch b + 1 are therefore issued right AFTER the
@@ -289,6 +290,18 @@ __global__ __launch_bounds__(DPZ::THREADS, 3) void deconv_prob_zm_kernel(
       DPZ_BATCH(5, d1, wq1, d0, wq0)
 #undef DPZ_BATCH
     };
+    do {
+    DPZ_PIECE()
+    stage.init(ptid, X0, Y0, H, W);
+    const int ox = tx_i * 2 * C::CXR + c;
+    const int oy0 = ty_i * 2 * C::CYR + C::PR * rg;
+    const bool lane_ok = c < 2 * C::CXR && ox < Wo;
+#pragma unroll
+    for (int r = 0; r < C::PR; ++r) st_off[r] = (lane_ok && oy0 + r < Ho) ? (oy0 + r) * Wo + ox : -1;
+#pragma unroll
+    for (int s = 0; s < 3; ++s)
+#pragma unroll
+      for (int r = 0; r < C::PR; ++r) A[s][r] = 0.f;
     // prologue: the input planes of the first half-step
     const int ap = qs >> 1;
     issue(ap);
@@ -317,6 +330,7 @@ __global__ __launch_bounds__(DPZ::THREADS, 3) void deconv_prob_zm_kernel(
       }
       __syncthreads();
     }
+    } while (BAL && walk.next_piece());
     return;
   }
 
@@ -329,6 +343,8 @@ __global__ __launch_bounds__(DPZ::THREADS, 3) void deconv_prob_zm_kernel(
   const int b_h1 = ((wave + (g >> 1)) * C::IXP + j + (g & 1)) * POSB;
   const int b_h2a = (wave * C::IXP + j + (g & 1)) * POSB;
   const int b_h2b = b_h2a + C::IXP * POSB;
+  do {
+  DPZ_PIECE()
   // output voxels of this lane: x = 2 (X0 + 16 q + j) + px, y = 2 (Y0 + wave) + py
   int sk_off[2][C::NT];      // residual element offsets inside a z plane, -1 outside the volume
 #pragma unroll
@@ -456,6 +472,8 @@ __global__ __launch_bounds__(DPZ::THREADS, 3) void deconv_prob_zm_kernel(
     }
     __syncthreads();
   }
+  } while (BAL && walk.next_piece());
+#undef DPZ_PIECE
 }
 
 }  // namespace
@@ -473,16 +491,22 @@ static int dpz_entry(const float* x, const void* weight_split, const float* bias
   hipStream_t st = (hipStream_t)stream;
   const int tiles_x = cds_ceil_div(W, C::CXR), tiles_y = cds_ceil_div(H, C::CYR);
   const int ncols = tiles_x * tiles_y;
-  const int seg_len = cds_ceil_div(D, zm_pick_nseg(ncols, D, 16, "CDS_DPZ_NSEG"));
+  double ucost;
+  const int seg_len = cds_ceil_div(D, zm_pick_nseg(ncols, D, 16, "CDS_DPZ_NSEG", &ucost));
   const int nseg = cds_ceil_div(D, seg_len);
+  const int nwg = zm_ncu();
+  const bool bal = zm_choose_balanced(zm_balance_knob(), ucost, ncols, D, nwg, ZM_MINLEN_CELL, 1.5, nullptr, ZM_BALANCE_MARGIN_TAIL);
   // the form follows from the bounds the caller gave (the forms without them ignore the arguments that go with them)
-  auto launch = [&](auto f16, auto mf) {
-    return cds_launch_lds<deconv_prob_zm_kernel<decltype(f16)::value, decltype(mf)::value>>(
-        160 * 1024, dim3(ncols * nseg), dim3(C::THREADS), C::LDS, st, x, reinterpret_cast<const uint4*>(weight_split), bias, skip, prob_table,
-        out, D, H, W, tiles_x, ncols, seg_len, in_bound, w_inv, skip_bound, y_gain, p_inv);
+  auto launch = [&](auto f16, auto mf, auto b) {
+    return cds_launch_lds<deconv_prob_zm_kernel<decltype(f16)::value, decltype(mf)::value, decltype(b)::value>>(
+        160 * 1024, dim3(b ? nwg : ncols * nseg), dim3(C::THREADS), C::LDS, st, x, reinterpret_cast<const uint4*>(weight_split), bias, skip,
+        prob_table, out, D, H, W, tiles_x, ncols, seg_len, in_bound, w_inv, skip_bound, y_gain, p_inv);
   };
-  if (skip_bound) return launch(std::true_type(), std::true_type());
-  return in_bound ? launch(std::true_type(), std::false_type()) : launch(std::false_type(), std::false_type());
+  auto forms = [&](auto b) {
+    if (skip_bound) return launch(std::true_type(), std::true_type(), b);
+    return in_bound ? launch(std::true_type(), std::false_type(), b) : launch(std::false_type(), std::false_type(), b);
+  };
+  return bal ? forms(std::true_type()) : forms(std::false_type());
 }
 
 extern "C" int cds_deconv_prob_zm_f32(const float* x, const void* weight_split, const float* bias, const float* skip,

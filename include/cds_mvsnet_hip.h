@@ -278,6 +278,24 @@ int cds_deconv_prob_zm_sf16_mfma_f32(const float* x, const void* weight_split, c
                                      const float* in_bound, float w_inv_scale, const float* skip_bound, float y_gain, float p_inv_scale,
                                      void* stream);
 
+/* How the z-marching CostRegNet kernels (conv3d_zmg, deconv3d_zm, deconv_prob_zm) cut a layer into workgroups, on the host (no GPU
+ * call; for tests).  Uniform cutting: columns x z segments equal units.  Balanced cutting (csrc/zm_common.hpp): workgroup wg of nwg
+ * owns one contiguous range of the column-major (column, stage) sequence, cut at the column boundaries into pieces; a piece shorter
+ * than min_len stages goes to the neighbour that holds the rest of its column.  CDS_ZM_BALANCE (read per launch): 0 = uniform only,
+ * 1 (default) = balanced where the cost model says it is cheaper, 2 = balanced wherever a workgroup has at most 8 pieces and the
+ * kernel has the registers; CDS_ZM_NCU overrides the number of workgroups (default: the device's CU count).  Results do not depend
+ * on either.
+ * cds_zm_partition: the pieces of workgroup wg for `cols` columns of `planes` planes, `unit` planes per stage, as (column, first
+ * plane, one past the last plane) triples in out[24]; returns their number - more than 8 (of which the first 8 are stored) where
+ * the layer keeps the uniform cutting.
+ * cds_zm_plan: what a launch would choose for such a layer with ys cout splits on ncu workgroups under CDS_ZM_BALANCE = balance;
+ * family 0 = conv3d_zmg, 1 = deconv3d_zm (ys = 2: conv7), 2 = the fused tail; out[4] = {balanced?, z segments of the uniform form,
+ * its model cost, the balanced cutting's model cost}, the costs in 1/1000 stage. */
+int cds_zm_partition(int cols, int planes, int unit, int nwg, int wg, int min_len, int* out);
+/* cds_zm_partition for all nwg workgroups at once, up to cap pieces each: out[nwg][1 + 3 cap] = {number of pieces, triples}. */
+int cds_zm_partition_all(int cols, int planes, int unit, int nwg, int min_len, int cap, int* out);
+int cds_zm_plan(int family, int cols, int planes, int unit, int ys, int ncu, int balance, int* out);
+
 
 /*
  * K4 (module.py:125-160): ConvTranspose3d k=3, stride 2, padding 1, output_padding 1 (doubles
